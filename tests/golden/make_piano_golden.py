@@ -7,8 +7,8 @@ recording stand-in of `dm_control.mjcf` (attribute get/set, `.add(tag, **kw)`), 
 `piano_constants.py` loaded by path as well.  The dump is the resolved per-key layout (default
 classes applied) and every constant of piano_constants.py and music/constants.py.  Nothing from the
 reference is copied into the repo: this script only READS /root/reference (or $RP_REFERENCE) at
-generation time; tests/test_model.py compares the in-tree piano model with the committed JSON, and
-re-runs this script when the reference is present to check that the JSON is current.
+generation time; tests/test_model.py compares the in-tree piano model with the committed JSON.
+`--check` (run by hand next to a reference checkout) reports whether the JSON is current.
 
 Usage:  python tests/golden/make_piano_golden.py [--check]
 """

@@ -4,6 +4,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -50,6 +51,27 @@ def test_config_definitions_follow_the_survey():
     from robopianist_amd.music import midi_file
     tables = {midi_file.NoteTrajectory.from_midi(m, 0.05).to_goal_tables()[0].tobytes() for m in bank}
     assert len(tables) >= 140   # (distinct goal tables; a few stretch / shift draws may coincide)
+
+
+def test_dump_outputs_keeps_float_dtypes_and_samples_the_same_envs_above_the_limit(tmp_path, monkeypatch):
+    sys.path.insert(0, ROOT)
+    import bench
+    E = 10
+    arrays = {"reward": np.arange(E, dtype=np.float64), "piano/state": np.arange(4 * E, dtype=np.float32).reshape(E, 4),
+              "step_type": np.arange(E, dtype=np.int32)}
+    bench.dump_outputs(str(tmp_path / "all"), arrays)
+    got = {f: np.load(tmp_path / "all" / f) for f in os.listdir(tmp_path / "all")}
+    assert sorted(got) == ["env_index.npy", "piano__state.npy", "reward.npy", "step_type.npy"]
+    assert got["piano__state.npy"].dtype == np.float32 and got["step_type.npy"].dtype == np.float64
+    assert np.array_equal(got["env_index.npy"], np.arange(E)) and np.array_equal(got["piano__state.npy"], arrays["piano/state"])
+    # per env 8 + 16 + 4 bytes (+ 8 for the index): a 100-byte budget keeps 2 envs, the same rows in every file and run
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 100)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    idx = np.load(tmp_path / "a" / "env_index.npy")
+    assert len(idx) == 2 and np.array_equal(idx, np.load(tmp_path / "b" / "env_index.npy"))
+    assert np.array_equal(np.load(tmp_path / "a" / "reward.npy"), idx)
+    assert np.array_equal(np.load(tmp_path / "a" / "piano__state.npy"), arrays["piano/state"][idx.astype(int)])
 
 
 @pytest.mark.gpu
@@ -102,11 +124,16 @@ def test_eight_ranks_sharing_one_gpu_keep_up_with_one_rank():
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("config", [2, 3, 4, 5])
-def test_bench_configs_emit_the_contract_line(config):
+def test_bench_configs_emit_the_contract_line(config, tmp_path):
     r = _run(["--config", str(config), "--envs", "128", "--steps", "6", "--warmup", "1", "--aux-fp32", "0",
-              "--host-io", "0", "--no-cpu-baseline"], timeout=900)
+              "--host-io", "0", "--no-cpu-baseline", "--dump-outputs", str(tmp_path)], timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
+    # a plain run measures the headline only: nothing of what --full adds
+    assert "aux" not in out and "cpu_baseline" not in out and out["steps"] == 6
+    dumped = {f[:-4]: np.load(tmp_path / f) for f in os.listdir(tmp_path)}
+    assert {"reward", "discount", "step_type", "goal", "physics_qpos", "physics_qvel"} <= set(dumped)
+    assert all(v.dtype == np.float64 and v.shape[0] == 128 and np.isfinite(v).all() for v in dumped.values())
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline"):
         assert k in out
@@ -122,7 +149,7 @@ def test_bench_configs_emit_the_contract_line(config):
 def test_bench_config2_reports_both_fingertip_colliders():
     """config 2 runs with the notebook's mesh-fingertip setting (stand-in hulls through MPR) and
     with primitive_fingertip_collisions=True; `--fingertips` picks which one is `value`, the other is aux."""
-    r = _run(["--config", "2", "--envs", "128", "--steps", "4", "--warmup", "1", "--aux-fp32", "0", "--host-io", "0",
+    r = _run(["--full", "--config", "2", "--envs", "128", "--steps", "4", "--warmup", "1", "--aux-fp32", "0", "--host-io", "0",
               "--no-cpu-baseline", "--fingertips", "hull"], timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])

@@ -24,5 +24,5 @@ run c4_s2 env RP_STREAM_SLICES=2 python bench.py $Q --config 4 --steps 150
 run c4_s1 env RP_STREAM_SLICES=1 python bench.py $Q --config 4 --steps 150
 run c5_s1 env RP_STREAM_SLICES=1 RP_FUSED=0 python bench.py $Q --config 5 --steps 150
 run c5_s2 env RP_STREAM_SLICES=2 RP_FUSED=0 python bench.py $Q --config 5 --steps 150
-run c2_rccl python bench.py --no-cpu-baseline --aux-fp32 0 --host-io 0 --aux-fingertips 0 --aux-large-hulls 0 --steps 60; python -c "import json;d=json.loads(open(\"$R/c2_rccl.json\").read().strip().splitlines()[-1]);print(d[\"aux\"][\"rccl_single_rank\"])"
+run c2_rccl python bench.py --full --no-cpu-baseline --aux-fp32 0 --host-io 0 --aux-fingertips 0 --aux-large-hulls 0 --steps 60; python -c "import json;d=json.loads(open(\"$R/c2_rccl.json\").read().strip().splitlines()[-1]);print(d[\"aux\"][\"rccl_single_rank\"])"
 timeout 300 python -m pytest tests/test_distributed.py -m gpu -q 2>&1 | tail -3

@@ -10,9 +10,9 @@ if [ -z "$SKIP_TESTS" ]; then
 timeout 1500 python -m pytest tests -m gpu -q > $R/pytest_gpu.log 2>&1; tail -2 $R/pytest_gpu.log
 timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $R/smoke.log 2>&1; tail -1 $R/smoke.log
 fi
-timeout 1200 python bench.py > $R/bench_plain.json 2> $R/bench_plain.err
+timeout 1200 python bench.py --full > $R/bench_plain.json 2> $R/bench_plain.err
 if [ -z "$SKIP_CONFIGS" ]; then
-for c in 3 4 5; do timeout 600 python bench.py --config $c --steps 150 > $R/bench_c$c.json 2> $R/bench_c$c.err; done
+for c in 3 4 5; do timeout 600 python bench.py --full --config $c --steps 150 > $R/bench_c$c.json 2> $R/bench_c$c.err; done
 timeout 600 python bench.py --config 2 --envs 2048 --steps 158 --no-cpu-baseline --aux-fp32 0 --host-io 0 --aux-fingertips 0 --aux-large-hulls 0 --aux-rccl 0 > $R/bench_c2_2048envs.json 2> $R/bench_c2_2048envs.err
 fi
 if [ -z "$SKIP_SOAK" ]; then
