@@ -268,6 +268,7 @@ struct Engine : EngineBase {
   bool mesh = false;    // the model has convex-hull geoms: position / sensor stages with MPR
   bool graph = false;   // ... some of them with a vertex graph (more than 32 vertices): the MESH = 2 builds
   bool deep = false;    // a trunk of 5..8 links (more than two forearm dofs): the RPK_MAXD_DEEP builds
+  int dense_joint = 0;  // RPK_LEAN_JOINT when RP_DENSE_HANDS=0 (goes to the kernels in S.lean)
   bool lean = false;    // light envs are stepped by rp_lean_solver_kernel (rp_solver2.hpp), the others by the full build
   // the position stage of the substeps as three launches: front part, pooled narrow phase (rp_collide.hpp), back part
   // split_mode: 0 = never, 1 = in every per-stage schedule, 2 = automatic: the schedule "three slices, split stage, no
@@ -287,7 +288,7 @@ struct Engine : EngineBase {
   }
   int lean_solver(int on) override {
     if (on && (deep || sizeof(T) != 8)) return fail("rp_set_lean_solver: the lean solver stage exists for the fp64 default builds only");
-    lean = on != 0; S.lean = on > 0 ? on : 0;   // (on > 1: the light class capped at that many Jacobian entries)
+    lean = on != 0; S.lean = on > 0 ? ((on & RPK_LEAN_CAP) | dense_joint) : 0;   // (on > 1: the light class capped at that many Jacobian entries)
     return 0;
   }
   int md() const { return deep ? RPK_MAXD_DEEP : RPK_MAXD; }
@@ -540,8 +541,12 @@ struct Engine : EngineBase {
     {
       const char* le = getenv("RP_LEAN");
       lean = sizeof(T) == 8 && !deep && !(le && le[0] == '0');
-      S.lean = lean ? 1 : 0;
-      if (lean && le && atoi(le) > 1) S.lean = atoi(le);   // (RP_LEAN=n > 1: the light class capped at n Jacobian entries, as rp_set_lean_solver(e, n))
+      // RP_DENSE_HANDS=0: the lean solver stage keeps the dirty rows of both hands in ONE dense block whatever the
+      // contacts (default: a block per hand, side by side, when no contact couples the hands -- same bits)
+      const char* dh = getenv("RP_DENSE_HANDS");
+      dense_joint = (dh && dh[0] == '0') ? RPK_LEAN_JOINT : 0;
+      S.lean = lean ? (1 | dense_joint) : 0;
+      if (lean && le && atoi(le) > 1) S.lean = (atoi(le) & RPK_LEAN_CAP) | dense_joint;   // (RP_LEAN=n > 1: the light class capped at n Jacobian entries, as rp_set_lean_solver(e, n))
     }
     // The fills and uploads above went through the null stream, which is NOT ordered with the
     // engine's non-blocking stream: everything must have landed before the first kernel.

@@ -2581,7 +2581,7 @@ __device__ __forceinline__ void rp_stage_body(const RpModel<T>& M, const RpState
         if (lane == 0) {
           B.hdr[env * 8 + 4] = nent; B.hdr[env * 8 + 5] = maxm;
           // capacity class of this env's solve (rp_solver2.hpp): light = fits the lean solver stage
-          B.hdr[env * 8 + 6] = (S.lean && MD == RPK_MAXD && M.ntree <= 2 && ncon <= LeanCaps::NC && nent <= (S.lean > 1 && S.lean < LeanCaps::NE ? S.lean : LeanCaps::NE) &&
+          B.hdr[env * 8 + 6] = (S.lean && MD == RPK_MAXD && M.ntree <= 2 && ncon <= LeanCaps::NC && nent <= ((S.lean & RPK_LEAN_CAP) > 1 && (S.lean & RPK_LEAN_CAP) < LeanCaps::NE ? (S.lean & RPK_LEAN_CAP) : LeanCaps::NE) &&
                                 __popcll(dirty_mask) <= LeanCaps::HMAX && nkt <= LeanCaps::NK && nl + nkt <= 64) ? 1 : 0;
         }
       }

@@ -184,6 +184,8 @@ struct RpModel {
   }
 };
 
+#define RPK_LEAN_CAP 0xffff
+#define RPK_LEAN_JOINT 0x10000
 template <typename T>
 struct RpState {
   int nenv;
@@ -207,7 +209,8 @@ struct RpState {
   int *cost_pos, *cost_sol;
   // capacity classes of the solver stage: when set, the position stage marks every env whose constraint system
   // fits rpk::LeanCaps as "light" (hdr[6] = 1); rp_lean_solver_kernel (two waves per SIMD) steps those and the
-  // full-capacity solver stage skips them
+  // full-capacity solver stage skips them.  (RPK_LEAN_CAP: the bits of the on / entry-cap value; RPK_LEAN_JOINT: the lean
+  // stage keeps ONE dense block for the dirty rows of both hands, rp_solver2.hpp)
   int lean;
   // may be null: the envs of this launch outside the light class, compacted (rp_order_kernel builds the list from
   // the hand-over headers).  The full-capacity solver stage then runs as a small grid that walks the list -- its

@@ -244,6 +244,22 @@ __device__ __forceinline__ void rp_lean_solver_body(const RpModel<T>& M, const R
     o.salink = t & 255; o.sTL = (t >> 8) & 15; o.sTB = (t >> 12) & 63; o.sdepth = ((t >> 18) & 15) - 1;
     return o;
   };
+  // the split of the dense block by hand (bits 28 / 29 of spk, set below), for the dirty rows `dm`: is it split, is my row
+  // the second hand's, the dirty rows of my hand (not split: all of them), the rows of either hand and where the second
+  // hand's packed matrix starts in sm.H (behind the first hand's n0 + 1 rows)
+  struct HSplit { bool on, mine1; unsigned long long dmh; int n0, n1, off1; };
+  auto hand_split = [&](const unsigned long long dm) -> HSplit {
+    int t = spk;
+    asm volatile("" : "+v"(t));
+    HSplit o;
+    o.on = uni((t >> 29) & 1) != 0;
+    const unsigned long long m1 = o.on ? __ballot((t >> 28) & 1) : 0ull;
+    o.mine1 = o.on && ((t >> 28) & 1);
+    o.dmh = o.on ? (o.mine1 ? dm & m1 : dm & ~m1) : dm;
+    o.n0 = __popcll(dm & ~m1); o.n1 = __popcll(dm & m1);
+    o.off1 = o.on ? tri(o.n0 + 1, 0) : 0;
+    return o;
+  };
   // which touched keys hang under me (bit s: the anchor chain of slot s passes through this link)
   {
     const int* sl = B.slots + (size_t)env * 64;
@@ -252,11 +268,20 @@ __device__ __forceinline__ void rp_lean_solver_body(const RpModel<T>& M, const R
       if (isl && ((am >> lane) & 1)) kpk |= 1 << (10 + s);
     }
   }
+  // which tree ("hand") every row belongs to: a link by its trunk, a key's solver slot by its anchor link's.  (`tm1`: the
+  // lanes of the second tree; a model with one tree has none)
+  unsigned long long tm1;
+  {
+    const int tb_ = isl ? (tpk >> 7) & 63 : (lane < nl + nkt ? (spk >> 12) & 63 : -1);
+    const int tb0 = bcast(tb_, 0), tb1 = bcast(tb_, nl - 1);
+    tm1 = __ballot(tb1 != tb0 && tb_ == tb1);
+  }
   WSYNC();
   // the contacts that touch my row (bit c; `crossm`, uniform: the cross-chain ones), for the Hessian gather and
   // J^T f: a lane then walks ITS contacts, and the wave takes as many trips as the busiest lane has contacts (a
   // trunk link: the contacts of its hand) instead of one trip per contact of the env
   unsigned call = 0, crossm = 0;
+  int span = 0;   // a contact whose entries lie in both trees: the dirty rows of the two hands are coupled
   for (int c0 = 0; c0 < ncon; c0 += 4) {
 #pragma unroll
     for (int u = 0; u < 4; u++) {
@@ -265,9 +290,21 @@ __device__ __forceinline__ void rp_lean_solver_body(const RpModel<T>& M, const R
       const unsigned long long sup = sm.csup[c];
       if (c0 + u < ncon && ((sup >> lane) & 1)) call |= 1u << c;
       if (c0 + u < ncon && ((inf >> 16) & 1)) crossm |= 1u << c;
+      if (c0 + u < ncon && (sup & tm1) != 0ull && (sup & ~tm1) != 0ull) span = 1;
     }
   }
   crossm = (unsigned)uni((int)crossm);
+  // The dense block per hand (docs/LAB_NOTEBOOK.md 4g): when no contact couples the two trees, the dirty rows of each hand form a
+  // diagonal block of their own, and the two blocks are factored side by side (dense_factor_solve_pair) instead of one
+  // pivot after the other.  Both hands must have dirty rows (one hand alone IS the joint block), and a hand's rows and
+  // its right-hand side must fit half a wave.  Kept for the Newton loop in two spare bits of `spk`: 28 = my row
+  // belongs to the second tree, 29 (uniform) = the block is split.
+  bool hsplit;
+  {
+    const int n0_ = __popcll(dirty_mask & ~tm1), n1_ = __popcll(dirty_mask & tm1);
+    hsplit = !(S.lean & RPK_LEAN_JOINT) && uni(span) == 0 && n0_ > 0 && n1_ > 0 && n0_ < 32 && n1_ < 32;
+    spk |= (int)((tm1 >> lane) & 1) << 28 | (hsplit ? 1 : 0) << 29;
+  }
   // contact Jacobian entries, rotated into the contact frame of their contact
   auto put_entry = [&](const int i, const T j0, const T j1, const T j2, const int h0, const int h1) {
     // (the hand-over's records, rp_model.hpp, repacked into this stage's narrower fields: lane | contact << 6 |
@@ -275,8 +312,11 @@ __device__ __forceinline__ void rp_lean_solver_body(const RpModel<T>& M, const R
     // < 256 entries)
     // (round 6: ... | the row of the entry's dof in the packed dense block << 16 -- its rank among the dirty rows, which the
     // cross-contact pass used to recount, one 64-bit population count per visited entry and Newton iteration)
+    // (split block: the rank among the dirty rows of the entry's OWN hand, and that hand << 22)
+    const int eh = hsplit ? (int)((tm1 >> RPK_EM_LANE(h0)) & 1) : 0;
+    const unsigned long long ehm = hsplit ? (eh ? tm1 : ~tm1) : ~0ull;
     const int m0 = RPK_EM_LANE(h0) | (RPK_EM_CON(h0) << 6) | (RPK_EM_COL(h0) << 11) | (RPK_EM_CROSS(h0) << 15) |
-                   (__popcll(dirty_mask & lanemask_lt(RPK_EM_LANE(h0))) << 16);
+                   (__popcll(dirty_mask & ehm & lanemask_lt(RPK_EM_LANE(h0))) << 16) | (eh << 22);
     const int m1 = RPK_EM_BASE(h1) | (RPK_EM_CNT(h1) << 8) | (RPK_EM_RANK(h1) << 16);
     const T* fr = sm.R[(m0 >> 6) & 31];
     sm.entJ[i][0] = fr[0] * j0 + fr[1] * j1 + fr[2] * j2;
@@ -594,35 +634,40 @@ __device__ __forceinline__ void rp_lean_solver_body(const RpModel<T>& M, const R
     T xcur = 0;   // my row's x once its level has passed (dirty rows: from the dense block)
     // ---- dense block on the dirty rows (Schur complement + cross-contact terms)
     if (dm) {
-      const int nD = __popcll(dm);
-      auto cidx = [&](int l) -> int { return __popcll(dm & lanemask_lt(l)); };
+      // (split by hand: a row's compact index is its rank among the dirty rows of ITS hand -- the ancestors of a row are
+      // rows of the same hand --, in its hand's packed matrix; the solve leaves the second hand's x in lanes 32 ..)
+      const HSplit hs = hand_split(dm);
+      const int nD = hs.on ? (hs.mine1 ? hs.n1 : hs.n0) : __popcll(dm);   // rows of my block
+      T* const Hh = sm.H + (hs.mine1 ? hs.off1 : 0);
+      auto cidx = [&](int l) -> int { return __popcll(hs.dmh & lanemask_lt(l)); };
       const int ci = cidx(lane);
       // every (row, ancestor) element has exactly one owner lane: plain read-modify-write
       if (dirty) {
         if (isl) {
 #pragma unroll
-          for (int k = 0; k < MD; k++) if (col_valid(k)) lds_add(&sm.H[tri(ci, cidx(col_lane(k)))], Rr[k]);   // (one owner per element: conflict-free, no round trip)
+          for (int k = 0; k < MD; k++) if (col_valid(k)) lds_add(&Hh[tri(ci, cidx(col_lane(k)))], Rr[k]);   // (one owner per element: conflict-free, no round trip)
         } else {
-          lds_add(&sm.H[tri(ci, ci)], sdiag);
+          lds_add(&Hh[tri(ci, ci)], sdiag);
 #pragma unroll
           for (int e = 0; e < MD; e++) {
             if (e <= sdepth) {
               const int a_ = anc_of(salink, sdepth, sTL, sTB, e);
-              if ((dm >> a_) & 1) lds_add(&sm.H[tri(ci, cidx(a_))], Rr[e]);
+              if ((dm >> a_) & 1) lds_add(&Hh[tri(ci, cidx(a_))], Rr[e]);
             }
           }
         }
         // the rhs of compact row r is row nD of the packed block
-        sm.H[tri(nD, 0) + ci] = rhs;
+        Hh[tri(nD, 0) + ci] = rhs;
       }
       WSYNC();
       PROF(22);
       // (four columns per step also in fp64: this build has the registers for it; +0.8 ... 1.7 %)
-      const T xr = dense_factor_solve<T, true>(sm.H, nD, lane, &warn);
+      const T xr = hs.on ? dense_factor_solve_pair<T>(sm.H, hs.n0, hs.n1, hs.off1, lane, &warn)
+                         : dense_factor_solve<T, true>(sm.H, nD, lane, &warn);
       WSYNC();
-      if (lane < nD) sm.vec[lane] = xr;
+      sm.vec[lane] = xr;   // (x of compact row r: lane r, the second hand's in lane 32 + r)
       WSYNC();
-      const T xd = sm.vec[dirty ? ci : 0];
+      const T xd = sm.vec[dirty ? ci + (hs.mine1 ? 32 : 0) : 0];
       if (dirty) xcur = xd;
       WSYNC();
     }
@@ -1089,6 +1134,7 @@ __device__ __forceinline__ void rp_lean_solver_body(const RpModel<T>& M, const R
       // Schur complement of the clean rows): entry lane a holds u = C_c J_a and walks the entries b <= a
       if (dmx) {
         auto cidx = [&](int l) -> int { return __popcll(dmx & lanemask_lt(l)); };
+        const HSplit hs = hand_split(dmx);   // (split block: the second hand's packed matrix starts at hs.off1)
         WSYNC();
         for (int e0 = 0; e0 < nent; e0 += 64) {
           const bool valid = e0 + lane < nent;
@@ -1109,6 +1155,7 @@ __device__ __forceinline__ void rp_lean_solver_body(const RpModel<T>& M, const R
 #else
           const int cia = cross ? ((m0 >> 16) & 63) : 0;
 #endif
+          T* const Ha = sm.H + (((m0 >> 22) & 1) ? hs.off1 : 0);   // (the entries of a contact belong to one hand)
           for (int k0 = 0; k0 < maxm; k0 += 4) {
             int mb[4];
             T val[4], jq[4][3];
@@ -1126,7 +1173,7 @@ __device__ __forceinline__ void rp_lean_solver_body(const RpModel<T>& M, const R
 #ifdef RPK_NO_T7
               if (valid && cross && k0 + u <= rank) lds_add(&sm.H[tri(cia, cidx(mb[u] & 63))], val[u]);
 #else
-              if (valid && cross && k0 + u <= rank) lds_add(&sm.H[tri(cia, (mb[u] >> 16) & 63)], val[u]);
+              if (valid && cross && k0 + u <= rank) lds_add(&Ha[tri(cia, (mb[u] >> 16) & 63)], val[u]);
 #endif
             }
           }
