@@ -1,7 +1,7 @@
 """Batched, headless counterpart of the reference's examples/piano_with_shadow_hands_env.py.
 
-Same flags (argparse instead of absl; no viewer / recording: rendering and audio are out of
-scope), plus --n_envs / --precision.  Replays an action sequence (or holds zeros) for one
+Same flags (argparse instead of absl; no viewer / recording: the interactive viewer and audio are out of
+scope), plus --n_envs / --precision and --pixels (camera images in the observation: wrappers/pixels.py).  Replays an action sequence (or holds zeros) for one
 episode in every env and prints the musical metrics and the throughput, e.g. BASELINE config #2:
 
     python examples/piano_with_shadow_hands_env.py \\
@@ -20,7 +20,7 @@ import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from robopianist_amd import suite  # noqa: E402
-from robopianist_amd.wrappers import CanonicalSpecWrapper, MidiEvaluationWrapper  # noqa: E402
+from robopianist_amd.wrappers import CanonicalSpecWrapper, MidiEvaluationWrapper, PixelWrapper  # noqa: E402
 
 
 def main() -> None:
@@ -41,6 +41,8 @@ def main() -> None:
     ap.add_argument("--n_envs", type=int, default=1024)
     ap.add_argument("--precision", type=int, default=64, choices=(32, 64))
     ap.add_argument("--seed", type=int, default=42)
+    ap.add_argument("--pixels", action="store_true",
+                    help="wrap the env in PixelWrapper (84 x 84 images of the piano/back camera) and print the pixels spec")
     args = ap.parse_args()
 
     with warnings.catch_warnings():
@@ -60,6 +62,10 @@ def main() -> None:
     if args.canonicalize:
         env = CanonicalSpecWrapper(env)
     env = MidiEvaluationWrapper(env)
+    if args.pixels:
+        env = PixelWrapper(env, render_kwargs=dict(height=84, width=84, camera_id="piano/back"))
+        spec = env.observation_spec()["pixels"]
+        print(f"Pixels spec: shape {spec.shape} dtype {spec.dtype} (collision geometry, camera piano/back)")
 
     action_spec = env.action_spec()
     E, dev = args.n_envs, env.physics.device

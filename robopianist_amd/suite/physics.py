@@ -76,6 +76,41 @@ class TorchPhysics:
         idx = torch.as_tensor([self._site_modelid[int(s)] for s in model_site_ids], dtype=torch.long, device=self.device)
         return self.sens_touch.index_select(1, idx)
 
+    # -- pixels ----------------------------------------------------------------
+    def renderer(self, colorize_fingertips: bool = False):
+        """The camera renderer of this batch (robopianist_amd/render.py), created at the first call: an env that never
+        renders allocates nothing and loads no second library.  The fingertip colours are part of the renderer's tables,
+        so each value of `colorize_fingertips` that is used gets a renderer of its own, with its own frame buffer
+        ([E][ngeom][12] floats) and output tensors: a caller that alternates between the two doubles that memory.  A task
+        has one value (`task.colorize_fingertips`), which is what PixelWrapper passes."""
+        key = bool(colorize_fingertips)
+        cache = self.__dict__.setdefault("_renderers", {})
+        if key not in cache:
+            from robopianist_amd import render as _render
+            cache[key] = _render.Renderer(self.scene, self.n_envs, device_id=self.device.index,
+                                          precision=32 if self.dtype == torch.float32 else 64,
+                                          colorize_fingertips=key)
+        return cache[key]
+
+    def render(self, height: int = 240, width: int = 320, camera_id=-1, depth: bool = False,
+               segmentation: bool = False, key_rgb=None, colorize_fingertips: bool = False):
+        """dm_control's `physics.render` for the whole batch: a device tensor [E,H,W,3] uint8, or [E,H,W] float32
+        (depth=True: distance along the camera's -z axis, +inf on background) / int32 (segmentation=True: model geom
+        id, `ngeom` = floor, -1 = background).  camera_id: -1 (free camera), 0-5 or a name ("back", "piano/back"), or
+        (pos, rot, fovy).  key_rgb: uint8 [E,88,3] key colours (`task.key_rgb(physics)`).  The image shows the
+        scene's COLLISION geometry.  Runs on torch's current stream from the engine's own qpos / tree-offset arrays;
+        the returned tensor is the renderer's cached buffer for this image size (clone it to keep it)."""
+        if depth and segmentation:
+            raise ValueError("depth and segmentation are mutually exclusive (dm_control's rule)")
+        r = self.renderer(colorize_fingertips)
+        if key_rgb is not None:
+            key_rgb = torch.as_tensor(key_rgb, device=self.device).to(torch.uint8).contiguous()
+        with torch.cuda.device(self.device):
+            out = r.render(self.qpos, height, width, camera=camera_id, tree_offset=self._tree_offset, key_rgb=key_rgb,
+                           rgb=not (depth or segmentation), depth=depth, segmentation=segmentation)
+        self._render_key_rgb = key_rgb   # keep alive until the kernel has run
+        return out[1] if depth else (out[2] if segmentation else out[0])
+
     # -- reads -----------------------------------------------------------------
     def refresh(self):
         """Views alias engine memory; nothing to copy."""

@@ -157,7 +157,8 @@ class PianoOnlyTask:
                  physics_timestep: float = _PHYSICS_TIMESTEP,
                  control_timestep: float = _CONTROL_TIMESTEP, _hands: Sequence[str] = (),
                  **scene_kwargs):
-        del change_color_on_activation  # cosmetic (piano.py:194-206), headless engine
+        # piano.py:194-206: what a camera sees of a pressed key (key_rgb below); no effect on the step path
+        self._change_color_on_activation = bool(change_color_on_activation)
         self.physics_timestep = physics_timestep
         self.control_timestep = control_timestep
         n = control_timestep / physics_timestep
@@ -185,6 +186,33 @@ class PianoOnlyTask:
 
     def get_discount(self, physics):
         return torch.ones(self._E, device=self._physics_device, dtype=self._dtype)
+
+    # -- key colours (what a camera sees of the piano's state) -------------------------------
+    @property
+    def colorize_fingertips(self) -> bool:
+        """True when the fingertip geoms carry FINGERTIP_COLORS (piano_with_shadow_hands.py:121-122)."""
+        return False
+
+    def _key_colour_tables(self):
+        """(base colours uint8 [88, 3], activation colour uint8 [3], fingertip colours uint8 [5, 3]) on the device."""
+        if getattr(self, "_key_colours", None) is None or self._key_colours[0].device != self._physics_device:
+            from robopianist_amd.model import render_tables as rt
+            u8 = lambda c: torch.as_tensor(np.floor(255.0 * np.asarray(c, np.float64) + 0.5).astype(np.uint8),
+                                           device=self._physics_device)
+            base = [rt.BLACK_KEY_COLOR if self._piano.is_key_black(k) else rt.WHITE_KEY_COLOR
+                    for k in range(self._piano.n_keys)]
+            self._key_colours = (u8(base), u8(rt.ACTIVATION_COLOR), u8(rt.FINGERTIP_COLORS))
+        return self._key_colours
+
+    def key_rgb(self, physics=None) -> torch.Tensor:
+        """Colour of every key as a camera sees it, uint8 [E][88][3] (Piano._update_key_color, piano.py:194-206): an
+        active key is (0.2, 0.8, 0.2) when `change_color_on_activation`, every other key has its base colour.
+        Computed only when rendering asks for it."""
+        base, active, _ = self._key_colour_tables()
+        rgb = base[None].expand(self._E, -1, -1)
+        if self._change_color_on_activation:
+            rgb = torch.where(self._piano.activation[:, :, None], active[None, None, :], rgb)
+        return rgb.contiguous()
 
 
 class PianoTask(PianoOnlyTask):

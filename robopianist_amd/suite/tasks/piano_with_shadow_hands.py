@@ -59,7 +59,7 @@ class PianoWithShadowHands(base.PianoTask):
         # extension (not in the reference): keep the tables of every env's NEXT episode ready in a
         # second bank slot, so that augmentations need no device->host read per step
         self._prefetch = bool(augmentation_prefetch) and augmentations is not None
-        del disable_colorization  # cosmetic (:451-474)
+        self._disable_colorization = bool(disable_colorization)   # (:121-122,197-201: fingertip / key colours, key_rgb below)
         self._augmentations = list(augmentations) if augmentations is not None else None
         midis = list(midi) if isinstance(midi, (list, tuple)) else [midi]
         if trim_silence:
@@ -623,6 +623,27 @@ class PianoWithShadowHands(base.PianoTask):
 
     def get_discount(self, physics=None):
         return self._discount
+
+    # -- key colours ---------------------------------------------------------------------------
+    @property
+    def colorize_fingertips(self) -> bool:
+        """:121-122 -- the fingertips carry FINGERTIP_COLORS unless colourisation or the fingering reward is off."""
+        return not self._disable_fingering_reward and not self._disable_colorization
+
+    def key_rgb(self, physics=None) -> torch.Tensor:
+        """uint8 [E][88][3], in the reference's order (piano.py:194-206, then :197-201,462-474): a key of the current
+        step's fingering set that is not active takes its finger's colour (unless colourisation or the fingering
+        reward is disabled); otherwise an active key is (0.2, 0.8, 0.2) when `change_color_on_activation`; otherwise the
+        key has its base colour.  Torch, and only when rendering asks for it: the step path does not call it."""
+        rgb = super().key_rgb(physics)
+        if not self.colorize_fingertips:
+            return rgb
+        _, _, tips = self._key_colour_tables()
+        f = self._finger_current                                     # [E, 88] finger id of each goal key, -1 = none
+        in_set = self._goal_current[:, :-1] > 0
+        fid = torch.where(f < 0, torch.full_like(f, 4), f) % 5       # (-1 -> the little finger, as in _compute_fingering_reward)
+        paint = in_set & ~self.piano.activation
+        return torch.where(paint[:, :, None], tips[fid], rgb).contiguous()
 
     def should_terminate_episode(self, physics=None):
         """:213-220."""

@@ -1,5 +1,6 @@
 from robopianist_amd.wrappers.canonical import CanonicalSpecWrapper
 from robopianist_amd.wrappers.evaluation import MidiEvaluationWrapper
 from robopianist_amd.wrappers.graphed import GraphedStepWrapper
+from robopianist_amd.wrappers.pixels import PixelWrapper
 
-__all__ = ["CanonicalSpecWrapper", "MidiEvaluationWrapper", "GraphedStepWrapper"]
+__all__ = ["CanonicalSpecWrapper", "MidiEvaluationWrapper", "GraphedStepWrapper", "PixelWrapper"]
