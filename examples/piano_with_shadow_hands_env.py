@@ -1,7 +1,8 @@
 """Batched, headless counterpart of the reference's examples/piano_with_shadow_hands_env.py.
 
-Same flags (argparse instead of absl; no viewer / recording: the interactive viewer and audio are out of
-scope), plus --n_envs / --precision and --pixels (camera images in the observation: wrappers/pixels.py).  Replays an action sequence (or holds zeros) for one
+Same flags (argparse instead of absl; no viewer: the interactive viewer and video are out of scope; --record writes
+the first env's sound as a WAV file: wrappers/sound.py), plus --n_envs / --precision, --record_dir and --pixels (camera
+images in the observation: wrappers/pixels.py).  Replays an action sequence (or holds zeros) for one
 episode in every env and prints the musical metrics and the throughput, e.g. BASELINE config #2:
 
     python examples/piano_with_shadow_hands_env.py \\
@@ -20,7 +21,8 @@ import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from robopianist_amd import suite  # noqa: E402
-from robopianist_amd.wrappers import CanonicalSpecWrapper, MidiEvaluationWrapper, PixelWrapper  # noqa: E402
+from robopianist_amd.wrappers import (CanonicalSpecWrapper, MidiEvaluationWrapper, PianoSoundWrapper,  # noqa: E402
+                                      PixelWrapper)
 
 
 def main() -> None:
@@ -43,13 +45,16 @@ def main() -> None:
     ap.add_argument("--seed", type=int, default=42)
     ap.add_argument("--pixels", action="store_true",
                     help="wrap the env in PixelWrapper (84 x 84 images of the piano/back camera) and print the pixels spec")
+    ap.add_argument("--record", action="store_true",
+                    help="record env 0 with PianoSoundWrapper and write its episode as a WAV file")
+    ap.add_argument("--record_dir", default="recordings")
     args = ap.parse_args()
 
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")
         env = suite.load(
             environment_name=args.env_name, midi_file=args.midi_file, stretch=args.stretch, shift=args.shift,
-            seed=args.seed, n_envs=args.n_envs, precision=args.precision,
+            seed=args.seed, n_envs=args.n_envs, precision=args.precision, record_key_trace=args.record,
             task_kwargs=dict(
                 change_color_on_activation=True, trim_silence=args.trim_silence,
                 control_timestep=args.control_timestep, gravity_compensation=args.gravity_compensation,
@@ -66,6 +71,9 @@ def main() -> None:
         env = PixelWrapper(env, render_kwargs=dict(height=84, width=84, camera_id="piano/back"))
         spec = env.observation_spec()["pixels"]
         print(f"Pixels spec: shape {spec.shape} dtype {spec.dtype} (collision geometry, camera piano/back)")
+
+    if args.record:
+        env = PianoSoundWrapper(env, record_dir=args.record_dir, record_envs=(0,), record_every=1)
 
     action_spec = env.action_spec()
     E, dev = args.n_envs, env.physics.device
@@ -97,6 +105,8 @@ def main() -> None:
     for k, v in env.get_musical_metrics().items():
         print(f"\t{k}: {v:.4f}")
     print(f"warn flags: {int(env.physics.warn.max())}")
+    if args.record:
+        print("recorded: " + (", ".join(str(p) for p in env.written) or "nothing (the episode has no note)"))
 
 
 if __name__ == "__main__":

@@ -2,7 +2,7 @@
 
 Mirror of robopianist/music/midi_file.py (same names, argument meaning and error
 behaviour) on top of `sequence.NoteSequence` instead of note_seq protos.
-Synthesis / playback (FluidSynth, PyAudio) is out of scope.
+Synthesis lives in music/synthesizer.py (a HIP synthesiser instead of FluidSynth); playback (PyAudio) is out of scope.
 """
 
 from __future__ import annotations
@@ -187,16 +187,46 @@ class MidiFile:
             raise ValueError(f"Unsupported file extension {filename.suffix}.")
         return cls(seq=seq)
 
+    @classmethod
+    def from_events(cls, events) -> "MidiFile":
+        """A played episode as a song: `events` are MidiModule messages with absolute times
+        (MidiModule.get_all_midi_messages, midi_module.events_from_trace).  A NoteOff closes the open note of its
+        pitch; a NoteOn of a pitch that is still open closes it first; a note still open at the last event ends
+        there.  Sustain events become CC64 values 127 / 0.  (This is the MIDI stream as played: how long a string
+        rings under the pedal is the synthesiser's business, music/synthesizer.py.)"""
+        from robopianist_amd.music import midi_module as mm
+        seq = NoteSequence()
+        open_notes = {}
+        end = 0.0
+        for e in events:
+            end = max(end, float(e.time))
+            if isinstance(e, (mm.NoteOn, mm.NoteOff)):
+                if e.note in open_notes:
+                    start, vel = open_notes.pop(e.note)
+                    seq.notes.add(pitch=e.note, velocity=vel, start_time=start, end_time=float(e.time))
+                if isinstance(e, mm.NoteOn):
+                    open_notes[e.note] = (float(e.time), int(e.velocity))
+            elif isinstance(e, (mm.SustainOn, mm.SustainOff)):
+                seq.control_changes.add(time=float(e.time), control_number=consts.SUSTAIN_PEDAL_CC_NUMBER,
+                                        control_value=consts.MAX_CC_VALUE if isinstance(e, mm.SustainOn) else consts.MIN_CC_VALUE)
+            else:
+                raise ValueError(f"Unknown event type: {e}")
+        for pitch, (start, vel) in open_notes.items():
+            seq.notes.add(pitch=pitch, velocity=vel, start_time=start, end_time=end)
+        seq.notes.sort(key=lambda n: (n.start_time, n.pitch))
+        seq.total_time = max((n.end_time for n in seq.notes), default=0.0)
+        return cls(seq=seq)
+
     def save(self, filename: Union[str, Path]) -> None:
-        """Saves the song as a serialized NoteSequence (`.proto`); midi_file.py:191-201.  Writing
-        Standard MIDI files is not implemented (nothing on the path consumes them)."""
+        """Saves the song as a serialized NoteSequence (`.proto`; midi_file.py:191-201) or as a format-0 Standard
+        MIDI File (`.mid`: note on / off and control changes, sequence.write_midi_file)."""
         filename = Path(filename)
         if filename.suffix == ".proto":
             from robopianist_amd.music import note_seq_proto
             with open(filename, "wb") as f:
                 f.write(note_seq_proto.serialize(self.seq))
         elif filename.suffix == ".mid":
-            raise NotImplementedError("writing .mid files is not supported; save as .proto")
+            seqlib.write_midi_file(self.seq, filename)
         else:
             raise ValueError(f"Unsupported file extension {filename.suffix}.")
 

@@ -5,7 +5,9 @@ The reference's MidiModule (robopianist/models/piano/midi_module.py:47-98) runs 
 NoteOn / NoteOff / SustainOn / SustainOff messages.  The batched engine instead records
 the activation of every substep as bit masks on the device (`rp_step(key_trace)`,
 `Environment(record_key_trace=True)`); this module applies the same edge detection to
-that trace, lazily and per env, on the host.  Only audio / MIDI export consume it."""
+that trace, lazily and per env, on the host.  Its consumers are the MIDI export (`MidiFile.from_events(...).save("x.mid")`)
+and the host side of the synthesiser (music/synthesizer.py: `notes_from_events`, `Synthesizer.get_samples`); the
+synthesiser's device path reads the trace itself (include/audio/rp_audio.h) and follows this module's conventions."""
 
 from __future__ import annotations
 

@@ -196,6 +196,47 @@ def read_midi_file(path) -> NoteSequence:
     return seq
 
 
+def _varlen(v: int) -> bytes:
+    out = [v & 0x7F]
+    v >>= 7
+    while v:
+        out.append((v & 0x7F) | 0x80)
+        v >>= 7
+    return bytes(reversed(out))
+
+
+# 120 qpm at 1000 ticks per quarter: one tick is half a millisecond
+_WRITE_DIVISION = 1000
+_WRITE_US_PER_QUARTER = 500000
+
+
+def write_midi_file(seq: NoteSequence, path) -> None:
+    """Writes `seq` as a format-0 Standard MIDI File: one tempo (120 qpm, 1000 ticks per quarter, so times are
+    rounded to 0.5 ms), note on / note off on channel 0 and the control changes.  At equal ticks note-offs come
+    first, so a note that ends where the next one of its pitch starts reads back as two notes; a note shorter than a
+    tick is given one tick."""
+    ticks_per_second = _WRITE_DIVISION * 1e6 / _WRITE_US_PER_QUARTER
+    tick = lambda t: int(round(t * ticks_per_second))
+    ev = []   # (tick, order, bytes)
+    for n in seq.notes:
+        a = tick(n.start_time)
+        b = max(tick(n.end_time), a + 1)
+        ev.append((a, 2, bytes([0x90, n.pitch & 0x7F, max(1, min(127, int(n.velocity)))])))
+        ev.append((b, 0, bytes([0x80, n.pitch & 0x7F, 0])))
+    for c in seq.control_changes:
+        ev.append((tick(c.time), 1, bytes([0xB0, c.control_number & 0x7F, c.control_value & 0x7F])))
+    ev.sort(key=lambda e: (e[0], e[1]))   # (stable: the list order of equal events is kept)
+    body = bytearray(b"\x00\xff\x51\x03" + _WRITE_US_PER_QUARTER.to_bytes(3, "big"))
+    last = 0
+    for tk, _, msg in ev:
+        body += _varlen(tk - last) + msg
+        last = tk
+    body += b"\x00\xff\x2f\x00"
+    with open(path, "wb") as f:
+        f.write(b"MThd" + struct.pack(">IHHH", 6, 0, 1, _WRITE_DIVISION))
+        f.write(b"MTrk" + struct.pack(">I", len(body)) + bytes(body))
+
+
 # ----------------------------------------------------- sequences_lib equivalents
 def stretch_note_sequence(seq: NoteSequence, factor: float) -> NoteSequence:
     """note_seq.sequences_lib.stretch_note_sequence (no-op for factor == 1)."""

@@ -4,7 +4,7 @@
 `precision` (64 by default: the reference computes in float64, and only the fp64
 engine tracks the CPU path to the teacher-forced 1e-9; 32 selects the fp32 build, which is NOT faster -- it has
 no lean solver / split-stage schedule, measured 664 k against 705 k env-steps/s -- and exists for memory-bound batch
-sizes).  It returns a batched dm_env-style Environment whose physics is the HIP engine."""
+sizes), and `record_key_trace` (the per-substep key activations that wrappers.PianoSoundWrapper records).  It returns a batched dm_env-style Environment whose physics is the HIP engine."""
 
 from pathlib import Path
 from typing import Any, Dict, Mapping, Optional, Union
@@ -39,6 +39,7 @@ def load(
     n_envs: int = 1,
     device_id: int = 0,
     precision: int = 64,
+    record_key_trace: bool = False,
 ) -> environment.Environment:
     """Loads a (batched) RoboPianist environment; raises ValueError for unknown names."""
     del recompile_physics  # the model is compiled once and uploaded to the GPU
@@ -52,7 +53,8 @@ def load(
     task_kwargs = dict(task_kwargs or {})
     task = piano_with_shadow_hands.PianoWithShadowHands(midi=midi, **task_kwargs)
     return environment.Environment(task, n_envs=n_envs, random_state=seed, device_id=device_id,
-                                   precision=precision, legacy_step=legacy_step)
+                                   precision=precision, legacy_step=legacy_step,
+                                   record_key_trace=record_key_trace)
 
 
 __all__ = ["ALL", "DEBUG", "ETUDE_12", "REPERTOIRE_150", "load"]

@@ -2,5 +2,6 @@ from robopianist_amd.wrappers.canonical import CanonicalSpecWrapper
 from robopianist_amd.wrappers.evaluation import MidiEvaluationWrapper
 from robopianist_amd.wrappers.graphed import GraphedStepWrapper
 from robopianist_amd.wrappers.pixels import PixelWrapper
+from robopianist_amd.wrappers.sound import PianoSoundWrapper
 
-__all__ = ["CanonicalSpecWrapper", "MidiEvaluationWrapper", "GraphedStepWrapper", "PixelWrapper"]
+__all__ = ["CanonicalSpecWrapper", "MidiEvaluationWrapper", "GraphedStepWrapper", "PixelWrapper", "PianoSoundWrapper"]
