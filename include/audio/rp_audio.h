@@ -29,8 +29,8 @@
  *
  * Output.  Sample n is at t = n/sr; n_samples_e = ceil(sr (T_e dt + 1.0)) (one second of tail).
  *   wave  float32 [E][n_cap]: the plain sum of the voices in list order; samples from n_samples_e on are 0.
- *   pcm   int16   [E][n_cap], optional: trunc(32767 wave / peak_e), peak_e = max |wave| of that environment;
- *         peak_e == 0 gives all zeros.
+ *   pcm   int16   [E][n_cap], optional: trunc(32767 (wave / peak_e)), peak_e = max |wave| of that environment, the
+ *         quotient formed first, so the loudest sample is exactly +-32767; peak_e == 0 gives all zeros.
  * All per-sample arithmetic is float32; t, u and u - u_off are formed in float64 and then rounded, and a phase is
  * reduced as frac(f_h u) in float64 before any float32 sine.
  *

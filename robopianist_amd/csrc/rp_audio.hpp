@@ -307,8 +307,10 @@ RPA_INLINE void rpa_accumulate(const RpaModel& M, const RpaVoice* vs, int nv, in
   }
 }
 
+// The quotient first: w / peak is exactly +-1 at the peak, so the loudest sample is exactly +-32767 (the product first,
+// 32767 w rounded and then divided by peak, can come out just below 32767 and truncate to 32766).
 RPA_INLINE short rpa_pcm(float w, float peak) {
-  return peak > 0.f ? (short)truncf(32767.0f * w / peak) : (short)0;
+  return peak > 0.f ? (short)truncf(32767.0f * (w / peak)) : (short)0;
 }
 
 // ---- the whole call on the host (tests) -------------------------------------------------------------------------

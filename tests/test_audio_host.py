@@ -174,6 +174,114 @@ def test_host_build_matches_the_reference(name):
         assert len(ar.case_references("b")[0][0]) > h._L.rpah_dim(h._h, b"chunk_notes")
 
 
+# ---- the wider cases (audio_reference.py), the CPU twins of the GPU tests ---------------------------------------------
+def test_wide_reference_rounding_supports_the_wide_tolerance():
+    """The same rule over the wider cases alone: WIDE_TOL is 4 x the reference's own float32 rounding on them."""
+    worst, per_run = ar.measure_wide_reference_rounding()
+    for label, r in per_run.items():
+        print(f"reference rounding, {label}: {r:.4e} of the peak")
+    assert worst <= ar.MEASURED_WIDE_ROUNDING * 1.0005, "the recorded measurement no longer holds: re-measure"
+    assert worst >= ar.MEASURED_WIDE_ROUNDING * 0.5, "the recorded measurement is padded: re-measure"
+    assert ar.WIDE_TOL == 4 * ar.MEASURED_WIDE_ROUNDING
+    assert 4 * ar.MEASURED_WIDE_ROUNDING * 32767 < 0.5      # so pcm differs from the reference's by at most one step
+
+
+def _host_run(run, max_notes=None):
+    E = len(run["lists"])
+    h = ar.HostAudio(n_envs=E, max_substeps=run["T"], max_notes=run["max_notes"] if max_notes is None else max_notes,
+                     timbre=run["timbre"], sr=run["sr"])
+    for e, notes in enumerate(run["lists"]):
+        h.set_notes(e, notes)
+    return h
+
+
+@pytest.mark.parametrize("name", ar.WIDE_CASES)
+def test_host_build_matches_the_reference_on_the_wide_cases(name):
+    for run, refs in zip(ar.wide_case(name), ar.wide_references(name)):
+        h = _host_run(run)
+        w, p = h.synthesize([run["T"]] * len(refs), run["T"], dt=run["dt"])
+        ar.check_rows(run, refs, w, p, "host")
+    if name == "crowd":
+        busiest, silent = ar.crowd_presence(h._L.rpah_dim(h._h, b"block_samples"))
+        print(f"crowd: up to {busiest} notes audible in one block, {silent:.1%} of the entries do not sound")
+        assert busiest > h._L.rpah_dim(h._h, b"chunk_notes")
+        assert silent >= 0.2
+    if name == "long":
+        assert ar.n_samples(run["T"]) > 900 * h._L.rpah_dim(h._h, b"block_samples")
+    if name == "rates":
+        assert [ar.n_samples(r["T"], r["dt"], r["sr"]) for r in ar.case_rates()][3] == 1320      # 1000 Hz: two blocks
+
+
+def test_edges_are_what_they_claim_and_count_is_clamped_on_the_host():
+    """The edge list's times are sample times to the bit; count > max_notes reads max_notes entries, count < 0 none."""
+    for (run, (ref,)), (tau_rel, cut) in zip(zip(ar.case_edges(), ar.wide_references("edges")), ((0.05, 5 * 4096), (0.01, 4096))):
+        full, valid = ar.edges_lists(tau_rel, cut)
+        assert ar.sounding(full) == valid and len(full) == 2 * len(valid) == 16 == run["max_notes"]
+        t = np.arange(len(ref)) / ar.SR
+        for n in (1023, 1024, 1025, 2047, 2048, 2049, 3072):
+            assert sum(x[1] == t[n] for x in valid) + sum(x[2] == t[n] for x in valid) >= 1
+        assert sorted(x[3] for x in valid if x[3] != 127)[:1] == [1] and {1, 64, 100, 127} <= {x[3] for x in valid}
+        k25 = [x for x in valid if x[0] == 25][0]
+        last = int(np.flatnonzero(ar.reference_wave([k25], run["T"], run["timbre"]))[-1])
+        print(f"{run['label']}: key 25's cut-off was put on sample {cut}, its last sounding sample is {last}")
+        assert abs(k25[2] + 8 * tau_rel - cut / ar.SR) < 1e-12 and last in (cut - 1, cut) and cut % 1024 == 0
+        h = _host_run(run)
+        w, p = h.synthesize([run["T"]], run["T"])
+        h.notes["count"][0] = run["max_notes"] + 7
+        w2, p2 = h.synthesize([run["T"]], run["T"])
+        assert (w2.view(np.uint32) == w.view(np.uint32)).all() and (p2 == p).all()
+        h.notes["count"][0] = -3
+        w3, p3 = h.synthesize([run["T"]], run["T"])
+        assert (w3 == 0).all() and (p3 == 0).all()
+
+
+def test_notes_fuzz_on_the_host():
+    """Random traces through rpa_notes_host against the Python twin, the cap included."""
+    batches = ar.notes_fuzz_batches()
+    for b, batch in enumerate(batches):
+        h = ar.HostAudio(n_envs=5, max_substeps=ar.FUZZ_T_CAP, max_notes=batch["max_notes"])
+        got = h.notes_from_trace(batch["trace"], batch["lengths"])
+        for e, (notes, dropped) in enumerate(batch["want"]):
+            assert got[e] == notes, f"batch {b} env {e}"
+            assert h.notes["dropped"][e] == dropped, f"batch {b} env {e}"
+    _fuzz_presence(batches)
+
+
+def _fuzz_presence(batches):
+    crossing = sum(sum(b["crossing"]) for b in batches)
+    print(f"notes fuzz: {crossing} environments whose cap falls inside a substep with onsets on both sides of key 64")
+    assert len(batches) == 40 and crossing >= 1
+    assert {b["max_notes"] for b in batches} == {1, 7, 64, 4096}
+    assert all(int(b["lengths"].max()) == b["trace"].shape[1] for b in batches)
+    assert any(d == 0 and len(n) > 64 for b in batches for n, d in b["want"])      # and long lists that fit
+
+
+def test_peak_rows_on_the_host():
+    run, targets = ar.case_peak()
+    refs = ar.peak_references()
+    h = _host_run(run)
+    w, p = h.synthesize(ar.PEAK_LENGTHS, ar.T_CAP)
+    ar.check_rows(run, refs, w, p, "host")
+    assert [i % 256 for i, _ in targets][1] == 255 and targets[0][0] == ar.n_samples(ar.PEAK_LENGTHS[0]) - 1 and targets[2][1] == -1
+    for e, (index, sign) in enumerate(targets):
+        assert p[e, index] == sign * 32767 and int(np.abs(p[e].astype(np.int32)).argmax()) == index
+
+
+def test_slices_rows_on_the_host():
+    """The 48 distinct rows of the GPU suite's 65 537-environment run."""
+    S = ar.SLICES
+    E = S["n_keys"]
+    h = ar.HostAudio(n_envs=E, max_substeps=1, max_notes=S["max_notes"], sr=S["sr"])
+    got = h.notes_from_trace(ar.slices_trace(np.arange(E)), np.ones(E, np.int32), dt=S["dt"])
+    w, p = h.synthesize(np.ones(E, np.int32), 1, dt=S["dt"])
+    assert w.shape == (E, 1005)
+    run = dict(label="slices")
+    assert [g for g in got] == [n for n, _ in ar.slices_references()] and all(len(g) == 1 for g in got)
+    ar.check_rows(run, [r for _, r in ar.slices_references()], w, p, "host")
+    f, amp, _ = ar.partials(synthesizer.DEFAULT_TIMBRE, S["sr"])
+    assert (amp[:E, 0] != 0).all() and f[E - 1, 0] < 450.0
+
+
 def test_env_window_leaves_other_rows_alone_on_the_host():
     trace, lengths = ar.case_a()
     h = ar.HostAudio(n_envs=3, max_notes=32)
