@@ -1,8 +1,8 @@
 """Batched, headless counterpart of the reference's examples/piano_with_shadow_hands_env.py.
 
-Same flags (argparse instead of absl; no viewer: the interactive viewer and video are out of scope; --record writes
-the first env's sound as a WAV file: wrappers/sound.py), plus --n_envs / --precision, --record_dir and --pixels (camera
-images in the observation: wrappers/pixels.py).  Replays an action sequence (or holds zeros) for one
+Same flags (argparse instead of absl; no viewer: the interactive viewer is out of scope; --record writes the first
+env's sound as a WAV file, --record --video its picture and sound as an AVI file: wrappers/sound.py), plus --n_envs /
+--precision, --record_dir and --pixels (camera images in the observation: wrappers/pixels.py).  Replays an action sequence (or holds zeros) for one
 episode in every env and prints the musical metrics and the throughput, e.g. BASELINE config #2:
 
     python examples/piano_with_shadow_hands_env.py \\
@@ -21,8 +21,8 @@ import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from robopianist_amd import suite  # noqa: E402
-from robopianist_amd.wrappers import (CanonicalSpecWrapper, MidiEvaluationWrapper, PianoSoundWrapper,  # noqa: E402
-                                      PixelWrapper)
+from robopianist_amd.wrappers import (CanonicalSpecWrapper, MidiEvaluationWrapper, PianoSoundVideoWrapper,  # noqa: E402
+                                      PianoSoundWrapper, PixelWrapper)
 
 
 def main() -> None:
@@ -47,8 +47,12 @@ def main() -> None:
                     help="wrap the env in PixelWrapper (84 x 84 images of the piano/back camera) and print the pixels spec")
     ap.add_argument("--record", action="store_true",
                     help="record env 0 with PianoSoundWrapper and write its episode as a WAV file")
+    ap.add_argument("--video", action="store_true",
+                    help="with --record: film env 0 as well (PianoSoundVideoWrapper) and write an AVI file with picture and sound")
     ap.add_argument("--record_dir", default="recordings")
     args = ap.parse_args()
+    if args.video and not args.record:
+        ap.error("--video needs --record")
 
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")
@@ -72,7 +76,10 @@ def main() -> None:
         spec = env.observation_spec()["pixels"]
         print(f"Pixels spec: shape {spec.shape} dtype {spec.dtype} (collision geometry, camera piano/back)")
 
-    if args.record:
+    if args.record and args.video:
+        env = PianoSoundVideoWrapper(env, record_dir=args.record_dir, record_envs=(0,), record_every=1,
+                                     camera_id="piano/back", height=480, width=640)
+    elif args.record:
         env = PianoSoundWrapper(env, record_dir=args.record_dir, record_envs=(0,), record_every=1)
 
     action_spec = env.action_spec()

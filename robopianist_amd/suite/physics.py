@@ -93,13 +93,15 @@ class TorchPhysics:
         return cache[key]
 
     def render(self, height: int = 240, width: int = 320, camera_id=-1, depth: bool = False,
-               segmentation: bool = False, key_rgb=None, colorize_fingertips: bool = False):
+               segmentation: bool = False, key_rgb=None, colorize_fingertips: bool = False, env_first: int = 0,
+               env_count=None):
         """dm_control's `physics.render` for the whole batch: a device tensor [E,H,W,3] uint8, or [E,H,W] float32
         (depth=True: distance along the camera's -z axis, +inf on background) / int32 (segmentation=True: model geom
         id, `ngeom` = floor, -1 = background).  camera_id: -1 (free camera), 0-5 or a name ("back", "piano/back"), or
         (pos, rot, fovy).  key_rgb: uint8 [E,88,3] key colours (`task.key_rgb(physics)`).  The image shows the
         scene's COLLISION geometry.  Runs on torch's current stream from the engine's own qpos / tree-offset arrays;
-        the returned tensor is the renderer's cached buffer for this image size (clone it to keep it)."""
+        the returned tensor is the renderer's cached buffer for this image size (clone it to keep it).  env_first /
+        env_count: only these envs are rendered; the other rows of the buffer keep what they held."""
         if depth and segmentation:
             raise ValueError("depth and segmentation are mutually exclusive (dm_control's rule)")
         r = self.renderer(colorize_fingertips)
@@ -107,9 +109,34 @@ class TorchPhysics:
             key_rgb = torch.as_tensor(key_rgb, device=self.device).to(torch.uint8).contiguous()
         with torch.cuda.device(self.device):
             out = r.render(self.qpos, height, width, camera=camera_id, tree_offset=self._tree_offset, key_rgb=key_rgb,
-                           rgb=not (depth or segmentation), depth=depth, segmentation=segmentation)
+                           rgb=not (depth or segmentation), depth=depth, segmentation=segmentation,
+                           env_first=env_first, env_count=env_count)
         self._render_key_rgb = key_rgb   # keep alive until the kernel has run
         return out[1] if depth else (out[2] if segmentation else out[0])
+
+    def jpeg_encoder(self, height: int, width: int, max_frames: int, quality: int = 90):
+        """The JPEG encoder (robopianist_amd/video.py) of `max_frames` images of this size and quality, created at the
+        first call, as `renderer()` is."""
+        key = (int(height), int(width), int(max_frames), int(quality))
+        cache = self.__dict__.setdefault("_jpeg_encoders", {})
+        if key not in cache:
+            from robopianist_amd import video as _video
+            cache[key] = _video.Encoder(key[0], key[1], key[2], quality=key[3], device_id=self.device.index or 0)
+        return cache[key]
+
+    def render_jpeg(self, height: int = 240, width: int = 320, camera_id=-1, quality: int = 90, envs=None,
+                    **render_kwargs):
+        """`render` (colour image; `render_kwargs`: key_rgb, colorize_fingertips), then the JPEG encoder on the device:
+        a list of `bytes`, one baseline JPEG file (include/video/rp_video.h) per env of `envs` (default: every env).
+        The files come to the host with one read-back of their lengths and one copy each."""
+        if render_kwargs.get("depth") or render_kwargs.get("segmentation"):
+            raise ValueError("render_jpeg encodes the colour image")
+        rgb = self.render(height, width, camera_id, **render_kwargs)
+        if envs is not None:
+            index = torch.as_tensor([int(e) for e in envs], dtype=torch.long, device=self.device)
+            rgb = rgb.index_select(0, index).contiguous()
+        with torch.cuda.device(self.device):
+            return self.jpeg_encoder(height, width, rgb.shape[0], quality).frames(rgb)
 
     # -- reads -----------------------------------------------------------------
     def refresh(self):

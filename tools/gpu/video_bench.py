@@ -1,0 +1,121 @@
+"""Cost of the JPEG encoder next to the render of the same images (bench.py is left as it is).
+
+Three workloads on the TwinkleTwinkle scene after a few control steps of the scripted replay, so the images are what a
+recording holds (hands over the keys): 4096 frames of 84 x 84, 64 frames of 240 x 320, 4 frames of 480 x 640, camera
+piano/back, quality 90.  Per workload, timed with device events after a warm-up, in windows of at least `--seconds`,
+the two alternating in one process:
+
+    A  physics.render(H, W)               (with task.key_rgb, as the wrappers call it)
+    B  Encoder.encode(rendered images)    (the four launches of rp_video_encode; no read-back)
+
+Writes profiles/video_bench.json: ms per call, frames/s, input and output MB/s, bytes per frame.
+
+    python tools/gpu/video_bench.py [--windows 3] [--seconds 0.5] [--out profiles/video_bench.json]
+"""
+import argparse
+import json
+import os
+import sys
+import warnings
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, ROOT)
+
+WORKLOADS = ((4096, 84, 84), (64, 240, 320), (4, 480, 640))
+
+
+def window(fn, seconds):
+    """ms per call over a window of at least `seconds` (device events around the whole window)."""
+    n, calls, total = 4, 0, 0.0
+    while total < seconds * 1e3:
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(n):
+            fn()
+        b.record()
+        b.synchronize()
+        total += a.elapsed_time(b); calls += n
+        n *= 2
+    return total / calls
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--windows", type=int, default=3, help="timed windows per workload (each at least --seconds long)")
+    ap.add_argument("--seconds", type=float, default=0.5)
+    ap.add_argument("--quality", type=int, default=90)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "video_bench.json"))
+    args = ap.parse_args()
+
+    from robopianist_amd import suite
+    from robopianist_amd.suite.scripted import ScriptedActions
+    from robopianist_amd.wrappers import CanonicalSpecWrapper
+    actions = np.load(os.path.join(ROOT, "tests", "golden", "twinkle_twinkle_actions.npy"))
+    results = []
+    for E, H, W in WORKLOADS:
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            base = suite.load("RoboPianist-debug-TwinkleTwinkleRousseau-v0", seed=12345, n_envs=E,
+                              task_kwargs=dict(trim_silence=True, control_timestep=0.05, gravity_compensation=True,
+                                               primitive_fingertip_collisions=True, change_color_on_activation=True))
+        env = CanonicalSpecWrapper(base)
+        phys, task = base.physics, base.task
+        dev = phys.device
+        script = ScriptedActions(torch.as_tensor(actions, dtype=phys.dtype, device=dev),
+                                 torch.zeros(E, dtype=torch.long, device=dev))
+        env.reset()
+        for _ in range(40):   # untimed: the hands are over the keys, some keys are down and coloured
+            env.step(script)
+        enc = phys.jpeg_encoder(H, W, E, args.quality)
+
+        def render():
+            return phys.render(H, W, "piano/back", key_rgb=task.key_rgb(phys), colorize_fingertips=task.colorize_fingertips)
+
+        rgb = render()
+
+        def encode():
+            enc.encode(rgb)
+
+        for fn in (render, encode):
+            for _ in range(3):
+                fn()
+        torch.cuda.synchronize()
+        r_ms, e_ms = [], []
+        for _ in range(args.windows):
+            r_ms.append(window(render, args.seconds))
+            e_ms.append(window(encode, args.seconds))
+        _, length = enc.encode(rgb)
+        n = length.cpu().numpy().astype(np.int64)
+        assert (n > 0).all()
+        r, e = float(np.median(r_ms)), float(np.median(e_ms))
+        results.append({
+            "frames": E, "height": H, "width": W, "quality": args.quality,
+            "render_ms": r, "encode_ms": e, "encode_over_render": e / r,
+            "encode_frames_per_s": E / (e * 1e-3),
+            "encode_input_MB_per_s": E * H * W * 3 / (e * 1e-3) / 1e6,
+            "encode_output_MB_per_s": float(n.sum()) / (e * 1e-3) / 1e6,
+            "bytes_per_frame_mean": float(n.mean()), "bytes_per_frame_max": int(n.max()), "bytes_cap": enc.max_bytes,
+            "compression": E * H * W * 3 / float(n.sum()),
+            "windows_ms": {"render": r_ms, "encode": e_ms},
+        })
+        del env, base, enc, rgb
+        torch.cuda.empty_cache()
+    out = {
+        "device": torch.cuda.get_device_name(0),
+        "scene": "TwinkleTwinkle scripted replay after 40 control steps, camera piano/back, task.key_rgb",
+        "method": f"device events, {args.windows} windows of >= {args.seconds} s per workload, alternating; medians",
+        "encode": "rp_video_encode: transform, sizing, layout and writing launches; no read-back",
+        "workloads": results,
+    }
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(out, f, indent=1)
+    for w in results:
+        print(json.dumps({k: v for k, v in w.items() if k != "windows_ms"}))
+
+
+if __name__ == "__main__":
+    main()
