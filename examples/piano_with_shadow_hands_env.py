@@ -2,7 +2,8 @@
 
 Same flags (argparse instead of absl; no viewer: the interactive viewer is out of scope; --record writes the first
 env's sound as a WAV file, --record --video its picture and sound as an AVI file: wrappers/sound.py), plus --n_envs /
---precision, --record_dir and --pixels (camera images in the observation: wrappers/pixels.py).  Replays an action sequence (or holds zeros) for one
+--precision, --record_dir, --pixels (camera images in the observation: wrappers/pixels.py) and --hear (what every env hears in the
+observation: wrappers/hearing.py).  Replays an action sequence (or holds zeros) for one
 episode in every env and prints the musical metrics and the throughput, e.g. BASELINE config #2:
 
     python examples/piano_with_shadow_hands_env.py \\
@@ -21,8 +22,8 @@ import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from robopianist_amd import suite  # noqa: E402
-from robopianist_amd.wrappers import (CanonicalSpecWrapper, MidiEvaluationWrapper, PianoSoundVideoWrapper,  # noqa: E402
-                                      PianoSoundWrapper, PixelWrapper)
+from robopianist_amd.wrappers import (AudioObservationWrapper, CanonicalSpecWrapper, MidiEvaluationWrapper,  # noqa: E402
+                                      PianoSoundVideoWrapper, PianoSoundWrapper, PixelWrapper)
 
 
 def main() -> None:
@@ -45,6 +46,9 @@ def main() -> None:
     ap.add_argument("--seed", type=int, default=42)
     ap.add_argument("--pixels", action="store_true",
                     help="wrap the env in PixelWrapper (84 x 84 images of the piano/back camera) and print the pixels spec")
+    ap.add_argument("--hear", action="store_true",
+                    help="wrap the env in AudioObservationWrapper (88 magnitudes of the last 2048 samples at 16 kHz) and print "
+                         "the observation's shape and the loudest bin's key of env 0 every step")
     ap.add_argument("--record", action="store_true",
                     help="record env 0 with PianoSoundWrapper and write its episode as a WAV file")
     ap.add_argument("--video", action="store_true",
@@ -58,7 +62,7 @@ def main() -> None:
         warnings.simplefilter("ignore")
         env = suite.load(
             environment_name=args.env_name, midi_file=args.midi_file, stretch=args.stretch, shift=args.shift,
-            seed=args.seed, n_envs=args.n_envs, precision=args.precision, record_key_trace=args.record,
+            seed=args.seed, n_envs=args.n_envs, precision=args.precision, record_key_trace=args.record or args.hear,
             task_kwargs=dict(
                 change_color_on_activation=True, trim_silence=args.trim_silence,
                 control_timestep=args.control_timestep, gravity_compensation=args.gravity_compensation,
@@ -75,6 +79,10 @@ def main() -> None:
         env = PixelWrapper(env, render_kwargs=dict(height=84, width=84, camera_id="piano/back"))
         spec = env.observation_spec()["pixels"]
         print(f"Pixels spec: shape {spec.shape} dtype {spec.dtype} (collision geometry, camera piano/back)")
+    if args.hear:
+        env = AudioObservationWrapper(env)
+        spec = env.observation_spec()["audio"]
+        print(f"Audio spec: shape {spec.shape} dtype {spec.dtype} (one magnitude per key fundamental)")
 
     if args.record and args.video:
         env = PianoSoundVideoWrapper(env, record_dir=args.record_dir, record_envs=(0,), record_every=1,
@@ -103,6 +111,10 @@ def main() -> None:
         timestep = env.step(torch.as_tensor(a, device=dev, dtype=env.physics.dtype).expand(E, -1))
         ret += timestep.reward
         n_steps += 1
+        if args.hear:   # (a demonstration: the read-back is this print's, not the wrapper's)
+            audio = timestep.observation["audio"]
+            loud = int(audio[0].argmax())
+            print(f"step {n_steps}: audio {tuple(audio.shape)}, env 0 loudest bin: key {loud} at {float(audio[0, loud]):.4f}")
         if bool(timestep.last().all()):   # all envs play the same song: they finish together
             break
     torch.cuda.synchronize()
