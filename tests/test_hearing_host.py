@@ -3,7 +3,8 @@ the g++ build of csrc/rp_hear.hpp against the twin and the float64 definition, t
 
 Tolerances (tests/hear_reference.py): the float32 restatement against the float64 one over every call of the stream of
 case_a and the five analyses differs by at most 4.73e-07 of the peak of the sound so far in the window and 3.57e-07 in the
-spectrum; WINDOW_TOL and SPECTRUM_TOL are 4 x that.
+spectrum; WINDOW_TOL and SPECTRUM_TOL are 4 x that.  Over the wider cases (other rates, timesteps and timbres, forgetting
+banks, late episodes) it differs by at most 7.00e-07 and 6.36e-07; WIDE_TOLS is 4 x that.
 """
 import ctypes
 import os
@@ -165,6 +166,13 @@ def test_measured_rounding_is_what_the_constants_say():
     print(f"float32 vs float64 restatement: window {w:.3e}, spectrum {s:.3e} of the peak")
     assert w <= hr.MEASURED_WINDOW_ROUNDING and w >= 0.5 * hr.MEASURED_WINDOW_ROUNDING
     assert s <= hr.MEASURED_SPECTRUM_ROUNDING and s >= 0.5 * hr.MEASURED_SPECTRUM_ROUNDING
+    (w, s), per_case = hr.measure_wide_rounding()
+    for name, (cw, cs) in per_case.items():
+        print(f"{name}: window {cw:.3e}, spectrum {cs:.3e} of the peak")
+    assert set(per_case) == set(hr.WIDE_CASES) and all(cw > 0 and cs > 0 for cw, cs in per_case.values())
+    assert 0.5 * hr.MEASURED_WIDE_WINDOW_ROUNDING <= w <= hr.MEASURED_WIDE_WINDOW_ROUNDING
+    assert 0.5 * hr.MEASURED_WIDE_SPECTRUM_ROUNDING <= s <= hr.MEASURED_WIDE_SPECTRUM_ROUNDING
+    assert hr.WIDE_TOLS == (4 * hr.MEASURED_WIDE_WINDOW_ROUNDING, 4 * hr.MEASURED_WIDE_SPECTRUM_ROUNDING)
 
 
 def test_env_window_on_the_host_leaves_other_rows_alone():
@@ -176,6 +184,165 @@ def test_env_window_on_the_host_leaves_other_rows_alone():
         h.track(trace[:, :8], env_first=2, env_count=2)
     with pytest.raises(RuntimeError, match="exceeds max_substeps_per_call"):
         hr.HostHearing(3, hr.analysis("small"), max_substeps_per_call=4).track(trace[:, :8])
+
+
+# ---- the wider cases (hear_reference.py), on the host build ------------------------------------------------------------
+def test_windowed_reference_equals_the_full_one():
+    """reference_window evaluates samples N - W + 1 .. N alone; on case_a it is the slice of the sound from sample 0, to
+    the bit, in float64 and in the float32 restatement, with and without leading zeros."""
+    n = 0
+    for envs in hr.stream_reference():
+        for r in envs:
+            sound32 = hr.reference_sound(r["t_on"], r["t_off"], r["T"], dtype=np.float32)
+            for W in (64, 128, 2048):
+                assert hr.same_bits(hr.reference_window(r["t_on"], r["t_off"], r["T"], W), hr.window_of(r["sound64"], r["T"], W))
+                assert hr.same_bits(hr.reference_window(r["t_on"], r["t_off"], r["T"], W, dtype=np.float32),
+                                    hr.window_of(sound32, r["T"], W))
+                n += bool(r["peak"])
+            if r["peak"]:
+                near = abs(hr.peak_so_far(r["t_on"], r["t_off"], r["T"]) - float(np.abs(r["sound64"][:hr.last_sample(r["T"]) + 1]).max()))
+                assert near == 0.0
+    assert n >= 90
+
+
+def _same_bank(h, e, tw, label):
+    assert hr.same_bits(h.t_on[e], tw.t_on) and hr.same_bits(h.t_off[e], tw.t_off), label
+    assert (h.state[e] == tw.state()).all(), label
+
+
+def test_host_build_on_the_fuzz_traces_in_every_call_shape():
+    """One call of n_sub = max_substeps_per_call, and calls of 1, 0, 3, 10, 0, 32 rows: t_on, t_off and the 8 state words."""
+    lengths, some_forgotten = set(), 0
+    for b, tr in enumerate(hr.fuzz_traces()):
+        E, T = tr.shape[:2]
+        one = hr.HostHearing(E, hr.analysis("small"), max_substeps_per_call=T)
+        one.track(tr)
+        twins = [hr.TrackerTwin() for _ in range(E)]
+        cut = hr.HostHearing(E, hr.analysis("small"), max_substeps_per_call=32)
+        for a, z in hr.call_spans(T):
+            before = (cut.t_on.copy(), cut.t_off.copy(), cut.state.copy())
+            cut.track(tr[:, a:z])
+            lengths.add(z - a)
+            for e, tw in enumerate(twins):
+                tw.track(tr[e, a:z])
+                _same_bank(cut, e, tw, f"fuzz {b}/{e} rows {a}..{z}")
+                held = tw.held
+                assert (tw.t_off[held, 0] == tw.T * hr.DT).all()
+            if z == a:
+                assert all(hr.same_bits(x, y) for x, y in zip(before, (cut.t_on, cut.t_off, cut.state)))
+        for e, tw in enumerate(twins):
+            _same_bank(one, e, tw, f"fuzz {b}/{e} in one call")
+            some_forgotten += tw.forgotten > 0
+    assert hr.fuzz_traces()[0].shape == (5, 46, 4) and hr.call_spans(46) == [(0, 1), (1, 1), (1, 4), (4, 14), (14, 14), (14, 46)]
+    assert {0, 1, 3, 10, 32} <= lengths and some_forgotten >= 5
+
+
+def test_host_build_forgets_six_keys_in_one_call():
+    tr = hr.forget_trace()
+    h = hr.HostHearing(3, hr.analysis("small"))
+    for c, envs in enumerate(hr.forget_reference()):
+        h.track(tr)
+        assert [int(x) for x in h.state[:, 7]] == [r["forgotten"] for r in envs]
+        for e, r in enumerate(envs):
+            assert hr.same_bits(h.t_on[e], r["t_on"]) and hr.same_bits(h.t_off[e], r["t_off"]) and (h.state[e] == r["state"]).all()
+    assert [r["forgotten"] for r in hr.forget_reference()[0]] == [6, 1, 0]
+    h.track(tr, restart=[1, 0, 0])
+    assert (h.state[0] == 0).all() and h.state[1, 7] > hr.forget_reference()[1][1]["forgotten"]
+
+
+@pytest.mark.parametrize("timbre, want", [(None, 0), ("tau_rel=0.2", 1), ("tau_rel=0.1", 0)])
+def test_the_release_tail_decides_what_is_forgotten(timbre, want):
+    """Three strikes 0.5 s apart: with 8 tau_rel = 1.6 s the first still sounds at the third, with 0.4 s or 0.8 s not."""
+    rows = hr.far_strikes()
+    tw = hr.TrackerTwin(hr.timbre_of(timbre)["tau_rel"])
+    h = hr.HostHearing(1, hr.analysis("small"), timbre=timbre)
+    for a in range(0, len(rows), 64):
+        tw.track(rows[a:a + 64])
+        h.track(rows[None, a:a + 64])
+    assert tw.forgotten == want and tw.T == 300
+    _same_bank(h, 0, tw, f"{timbre}")
+
+
+@pytest.mark.parametrize("name", hr.MAIN_ANALYSES)
+def test_host_build_on_forgetting_banks(name):
+    """The definition is the bank's sound, whatever was forgotten."""
+    h = hr.HostHearing(3, hr.analysis(name))
+    for c, envs in enumerate(hr.forget_reference()):
+        h.track(hr.forget_trace())
+        spec, window = h.spectrum()
+        for e, r in enumerate(envs):
+            hr.check_observation(r, name, window[e], spec[e], f"host forget {name} call {c} env {e}", tols=hr.WIDE_TOLS)
+    assert np.abs(spec[0]).max() > 0.01
+
+
+@pytest.mark.parametrize("sr", [x[0] for x in hr.RATES])
+def test_host_build_at_other_rates_and_timesteps(sr):
+    case = hr.wide_case(f"rates/{sr}")
+    dt, tables = case["dt"], hr.rate_analysis(sr)
+    trace, _ = ar.case_a()
+    h = hr.HostHearing(3, tables, sr=sr, dt=dt)
+    fractional = 0
+    for c, envs in enumerate(hr.rates_reference(sr)):
+        h.track(trace[:, c * hr.RATES_N_SUB:(c + 1) * hr.RATES_N_SUB])
+        spec, window = h.spectrum()
+        fractional += hr.last_sample(envs[0]["T"], dt, sr) != round(sr * envs[0]["T"] * dt)
+        for e, r in enumerate(envs):
+            assert hr.same_bits(h.t_on[e], r["t_on"]) and hr.same_bits(h.t_off[e], r["t_off"]) and (h.state[e] == r["state"]).all()
+            hr.check_observation(r, tables, window[e], spec[e], f"host {sr} Hz call {c} env {e}", dt=dt, sr=sr,
+                                 tols=hr.WIDE_TOLS)
+    assert c == 20
+    assert (fractional > 0) == (sr != 8000), "floor() must decide some N at a non-integer sr dt"
+    if sr == 8000:    # key 87's partials at or above 0.45 sr are silenced
+        assert (ar.partials(hr.default_timbre(), sr)[1][87] == 0).any() and (ar.partials(hr.default_timbre(), hr.SR)[1][87] != 0).any()
+
+
+def test_host_build_with_the_harsh_timbre():
+    trace, _ = ar.case_a()
+    h = hr.HostHearing(3, hr.analysis("small"), timbre="harsh")
+    for c, envs in enumerate(hr.stream_reference(timbre="harsh")):
+        h.track(trace[:, c * hr.N_SUB:(c + 1) * hr.N_SUB])
+        spec, window = h.spectrum()
+        for e, r in enumerate(envs):
+            assert hr.same_bits(h.t_on[e], r["t_on"]) and (h.state[e] == r["state"]).all()
+            hr.check_observation(r, "small", window[e], spec[e], f"host harsh call {c} env {e}", timbre="harsh", tols=hr.WIDE_TOLS)
+
+
+@pytest.mark.parametrize("key", hr.SINE_KEYS)
+def test_host_build_reads_a_held_pure_sine_as_one(key):
+    """The one check that a table that is transposed or scaled cannot pass while tracker and window are right."""
+    tables, r = hr.sine_analysis(key), hr.sine_reference(key)
+    h = hr.HostHearing(1, tables, timbre="sine")
+    h.track(hr.sine_rows(key)[None])
+    spec, window = h.spectrum()
+    want = float(hr.reference_spectrum(hr.window64_of(r, 2048, "sine"), *tables)[0])
+    print(f"key {key}: the float64 reference reads {want:.6f}, the host build {float(spec[0, 0]):.6f}")
+    assert abs(want - 1.0) <= 1.5e-3
+    hr.check_observation(r, tables, window[0], spec[0], f"host sine key {key}", timbre="sine", tols=hr.WIDE_TOLS)
+
+
+@pytest.mark.parametrize("T0", hr.LATE_T0)
+def test_host_build_late_in_an_episode(T0):
+    trace, _ = ar.case_a()
+    h = hr.HostHearing(3, hr.analysis("default"), T0=T0)
+    for c, envs in enumerate(hr.stream_reference(T0=T0)):
+        h.track(trace[:, c * hr.N_SUB:(c + 1) * hr.N_SUB])
+        spec, window = h.spectrum()
+        for e, r in enumerate(envs):
+            assert r["T"] == T0 + hr.N_SUB * (c + 1)
+            assert hr.same_bits(h.t_on[e], r["t_on"]) and hr.same_bits(h.t_off[e], r["t_off"]) and (h.state[e] == r["state"]).all()
+            hr.check_observation(r, "default", window[e], spec[e], f"host T0 {T0} call {c} env {e}", T0=T0, tols=hr.WIDE_TOLS)
+    N = hr.last_sample(envs[0]["T"])
+    assert N <= 2.0e9 and (T0 != hr.LATE_T0[1] or N == 1_999_997_120)
+
+
+def test_host_analysis_entry_is_the_analysis_of_the_spectrum_call():
+    trace, _ = ar.case_a()
+    h = hr.HostHearing(3, hr.analysis("wide"))
+    h.track(trace[:, :40])
+    spec, window = h.spectrum()
+    again, _ = h.spectrum(of_window=window)
+    assert spec.any() and hr.same_bits(spec, again)
+    assert not h.spectrum(of_window=np.zeros_like(window))[0].any()
 
 
 # ---- the analysis table -------------------------------------------------------------------------------------------------
