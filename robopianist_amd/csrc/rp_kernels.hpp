@@ -179,8 +179,17 @@ __device__ __forceinline__ void rp_stage_body(const RpModel<T>& M, const RpState
   if constexpr (MODE == 1) {
     if (S.lean && B.hdr[env * 8 + 6] == 1) return;   // a light env: rp_lean_solver_kernel steps it
   }
+  // PB: the back part as a kernel of its own (rp_pos_back_kernel: 198 registers, no scratch) has the registers to request the
+  // tables of a phase TOGETHER -- clamped indices, unconditional reads into locals, a scheduling barrier, selects -- where the
+  // register-bound builds of this body read every table where it is used and under its predicate: a branch, one load and a
+  // full drain each, a dependent trip to L2 per table.  Same operations on the same values in the same order: same bits.
+  // (The one-kernel stage, the list / clean-up kernels and the fused kernels keep the reads they had.)
+  constexpr bool PB = MODE == 0 && PART == 2 && !EXT;
+  // PF: the same for the front part as a kernel of its own (rp_pos_front_kernel: 155 registers, no scratch)
+  constexpr bool PF = MODE == 0 && PART == 1 && !EXT;
   if constexpr (MODE == 0) {
-    if constexpr (PART == 2) { if (B.ncand[env] < 0) return; }   // (the front part did not run for this env: masked, or heavy)
+    // (PART 2: the front part did not run for this env, masked or heavy; PB tests it below, behind the prologue's requests)
+    if constexpr (PART == 2) { if constexpr (!PB) { if (B.ncand[env] < 0) return; } }
     else if (S.skip_heavy && S.listed[env]) return;   // (its position stage follows its solve on the companion stream)
   }
   const int env_active = S.active ? S.active[env] : 1;  // tested after the prologue loads are in flight
@@ -215,6 +224,11 @@ __device__ __forceinline__ void rp_stage_body(const RpModel<T>& M, const RpState
   // (the key tables are requested with the topology record -- clamped indices, selected below -- and the state with
   // one more batch: read under their predicates they were seven dependent trips to L2 in front of the first useful instruction)
   int kdof_raw[2], kact_raw[2];
+  // (PB: ... and what the front part left -- the link frames, the first 64 candidate records, the candidate count -- rides
+  // with them: they depend on the env alone.  Every address lies in the env's own records whatever the lane.)
+  T frv[RPK_NFRAME];
+  int cand_pre[3] = {0, 0, 0}, ncand_pre = 0;
+  T r_kacoef[2] = {0, 0};   // (PB: act_coef of the key actuators, read with the limit tables, used by the outputs)
   {
     const int4* rec = (const int4*)(M.lane_topo() + 16 * L);
 #pragma unroll
@@ -226,6 +240,14 @@ __device__ __forceinline__ void rp_stage_body(const RpModel<T>& M, const RpState
     for (int s = 0; s < 2; s++) {
       const int K = (lane + 64 * s) < M.nkey ? lane + 64 * s : 0;
       kdof_raw[s] = M.key_dof()[K]; kact_raw[s] = M.key_act()[K];
+    }
+    if constexpr (PB) {
+      ncand_pre = B.ncand[env];
+      const int2 c_ = ((const int2*)(B.cand + (size_t)env * RPK_NCAND * 2))[lane];
+      cand_pre[0] = c_.x; cand_pre[1] = c_.y; cand_pre[2] = B.cres_n[(size_t)env * RPK_NCAND + lane];
+      const T* fr_ = B.frames + (size_t)env * RPK_NFRAME * 64 + lane;
+#pragma unroll
+      for (int k = 0; k < RPK_NFRAME; k++) frv[k] = fr_[(size_t)k * 64];
     }
     __builtin_amdgcn_sched_barrier(0);
   }
@@ -264,8 +286,35 @@ __device__ __forceinline__ void rp_stage_body(const RpModel<T>& M, const RpState
 // of the substep loop.
 #define RPK_LOAD_GEOMETRY                                                                  \
   T lpos[3], lmat[9], laxis[3], lanchor[3], lipos[3], linert[6], tref[3];                  \
-  T kpos[2][3], khalf[2][3], krb[2];                                                       \
-  {                                                                                        \
+  T kpos[2][3], khalf[2][3], krb[2], lmass_, larm_;                                        \
+  if constexpr (PF) {   /* (one batch: L / ltree / K are 0 for the lanes without; selected behind the barrier) */ \
+    _Pragma("unroll") for (int k = 0; k < 3; k++) {                                        \
+      lpos[k] = M.link_lpos()[3 * L + k]; laxis[k] = M.link_axis()[3 * L + k];             \
+      lanchor[k] = M.link_anchor()[3 * L + k]; lipos[k] = M.link_ipos()[3 * L + k];        \
+      tref[k] = M.tree_ref()[3 * ltree + k];                                               \
+    }                                                                                      \
+    _Pragma("unroll") for (int k = 0; k < 9; k++) lmat[k] = M.link_lmat()[9 * L + k];      \
+    _Pragma("unroll") for (int k = 0; k < 6; k++) linert[k] = M.link_inertia()[6 * L + k]; \
+    lmass_ = M.link_mass()[L]; larm_ = M.link_armature()[L];                               \
+    T toff_[3] = {0, 0, 0};                                                                \
+    if (S.tree_offset) {                                                                   \
+      _Pragma("unroll") for (int k = 0; k < 3; k++)                                        \
+        toff_[k] = S.tree_offset[((size_t)env * M.ntree + ltree) * 3 + k];                 \
+    }                                                                                      \
+    /* (the key constants: with the geom constants, in front of the broad phase that uses them) */ \
+    __builtin_amdgcn_sched_barrier(0);                                                     \
+    _Pragma("unroll") for (int k = 0; k < 3; k++) {                                        \
+      lpos[k] = isl ? lpos[k] : (T)0; laxis[k] = isl ? laxis[k] : (T)0;                    \
+      lanchor[k] = isl ? lanchor[k] : (T)0; lipos[k] = isl ? lipos[k] : (T)0;              \
+      tref[k] = isl ? tref[k] : (T)0;                                                      \
+    }                                                                                      \
+    _Pragma("unroll") for (int k = 0; k < 9; k++) lmat[k] = isl ? lmat[k] : (T)0;          \
+    _Pragma("unroll") for (int k = 0; k < 6; k++) linert[k] = isl ? linert[k] : (T)0;      \
+    lmass_ = isl ? lmass_ : (T)0; larm_ = isl ? larm_ : (T)0;                              \
+    if (isl && parent < 0 && S.tree_offset) {                                              \
+      _Pragma("unroll") for (int k = 0; k < 3; k++) lpos[k] += toff_[k];                   \
+    }                                                                                      \
+  } else {                                                                                 \
     const T *p_lpos = fresh(M.link_lpos()), *p_axis = fresh(M.link_axis()),                    \
             *p_anchor = fresh(M.link_anchor()), *p_ipos = fresh(M.link_ipos()),                \
             *p_tref = fresh(M.tree_ref()), *p_lmat = fresh(M.link_lmat()),                     \
@@ -292,12 +341,22 @@ __device__ __forceinline__ void rp_stage_body(const RpModel<T>& M, const RpState
         khalf[s][k] = isk[s] ? p_khalf[3 * K + k] : (T)0;                                  \
       }                                                                                    \
     }                                                                                      \
+    lmass_ = isl ? fresh(M.link_mass())[L] : (T)0;                                           \
+    larm_ = isl ? fresh(M.link_armature())[L] : (T)0;                                        \
   }                                                                                        \
-  const T lmass = isl ? fresh(M.link_mass())[L] : (T)0;                                      \
-  const T larm = isl ? fresh(M.link_armature())[L] : (T)0;
+  const T lmass = lmass_;                                                                  \
+  const T larm = larm_;
 #define RPK_LOAD_LIMITS                                                                    \
-  T lo[3], hi[3], limK[3], limB[3], limW[3];                                               \
-  {                                                                                        \
+  T lo[3], hi[3], limK[3], limB[3], limW[3], lflB_;                                        \
+  if constexpr (PB) {   /* (requested in front of the subtree-force sums: selected here) */ \
+    _Pragma("unroll") for (int s = 0; s < 3; s++) {                                        \
+      const bool has_ = s == 0 ? isl : isk[s ? s - 1 : 0];                                 \
+      lo[s] = has_ ? r_lo[s] : (T)0; hi[s] = has_ ? r_hi[s] : (T)0;                        \
+      limK[s] = has_ ? r_K[s] : (T)0; limB[s] = has_ ? r_B[s] : (T)0;                      \
+      limW[s] = has_ ? r_W[s] : (T)0;                                                      \
+    }                                                                                      \
+    lflB_ = isl ? r_flB : (T)0;                                                            \
+  } else {                                                                                 \
     const T *p_lr = fresh(M.link_range()), *p_kr = fresh(M.key_range());                       \
     lo[0] = isl ? p_lr[2 * L] : (T)0; hi[0] = isl ? p_lr[2 * L + 1] : (T)0;                \
     limK[0] = isl ? fresh(M.link_lim_K())[L] : (T)0;                                         \
@@ -310,8 +369,9 @@ __device__ __forceinline__ void rp_stage_body(const RpModel<T>& M, const RpState
       limB[1 + s] = isk[s] ? fresh(M.key_lim_B())[K] : (T)0;                                 \
       limW[1 + s] = isk[s] ? fresh(M.key_invw_dof())[K] : (T)0;                              \
     }                                                                                      \
+    lflB_ = isl ? fresh(M.link_fl_B())[L] : (T)0;                                            \
   }                                                                                        \
-  const T lflB = isl ? fresh(M.link_fl_B())[L] : (T)0;
+  const T lflB = lflB_;
 #define RPK_LOAD_DYN                                                                       \
   const T ldamp = isl ? fresh(M.link_damping())[L] : (T)0;                                   \
   const T lstiff = isl ? fresh(M.link_stiffness())[L] : (T)0;                                \
@@ -381,6 +441,7 @@ __device__ __forceinline__ void rp_stage_body(const RpModel<T>& M, const RpState
   }
   T time = S.time[env];
   if (env_active == 0) return;  // masked env (all loads above are speculative and harmless)
+  if constexpr (PB) { if (ncand_pre < 0) return; }   // (the front part did not run for this env: masked, or heavy)
 
 
   PROF(0);
@@ -1332,12 +1393,36 @@ __device__ __forceinline__ void rp_stage_body(const RpModel<T>& M, const RpState
     // (the link's own spatial inertia is formed twice from the link frame in LDS -- here for the composite
     // inertias, and again after the collision phase for the bias forces -- with the same arithmetic, hence the
     // same bits: ten doubles carried across the collision phase instead were spilled inside its loops)
+    // PB: the velocity stage's per-link constants (read in one batch in front of it) and my contact's record
+    T v_tref[3], v_ipos[3], v_inert[6], v_mass = 0, v_gscale = 0;
+    T cfv[11];
+    int civ[2] = {0, 0};
     auto link_inertia = [&](T* cin) {
       const T *p_ipos = fresh(M.link_ipos()), *p_inert = fresh(M.link_inertia()), *p_tref = fresh(M.tree_ref());
-      const T lm_ = isl ? fresh(M.link_mass())[L] : (T)0;
+      T lm_;
+      if constexpr (PB) lm_ = isl ? v_mass : (T)0;
+      else if constexpr (PF) lm_ = M.link_mass()[L];   // (selected below, behind the batch)
+      else lm_ = isl ? fresh(M.link_mass())[L] : (T)0;
       T xm_[9], xp_[3], ip_[3], in_[6], tr_[3];
 #pragma unroll
       for (int k = 0; k < 9; k++) xm_[k] = isl ? sm.xmat[L][k] : (k % 4 == 0 ? (T)1 : (T)0);
+      if constexpr (PB) {
+#pragma unroll
+        for (int k = 0; k < 3; k++) { xp_[k] = isl ? sm.xpos[L][k] : (T)0; ip_[k] = isl ? v_ipos[k] : (T)0; tr_[k] = isl ? v_tref[k] : (T)0; }
+#pragma unroll
+        for (int k = 0; k < 6; k++) in_[k] = isl ? v_inert[k] : (T)0;
+      } else if constexpr (PF) {   // (one batch: L and ltree are 0 for the lanes without a link)
+#pragma unroll
+        for (int k = 0; k < 3; k++) { ip_[k] = M.link_ipos()[3 * L + k]; tr_[k] = M.tree_ref()[3 * ltree + k]; }
+#pragma unroll
+        for (int k = 0; k < 6; k++) in_[k] = M.link_inertia()[6 * L + k];
+        __builtin_amdgcn_sched_barrier(0);
+        lm_ = isl ? lm_ : (T)0;
+#pragma unroll
+        for (int k = 0; k < 3; k++) { xp_[k] = isl ? sm.xpos[L][k] : (T)0; ip_[k] = isl ? ip_[k] : (T)0; tr_[k] = isl ? tr_[k] : (T)0; }
+#pragma unroll
+        for (int k = 0; k < 6; k++) in_[k] = isl ? in_[k] : (T)0;
+      } else {
 #pragma unroll
       for (int k = 0; k < 3; k++) {
         xp_[k] = isl ? sm.xpos[L][k] : (T)0; ip_[k] = isl ? p_ipos[3 * L + k] : (T)0;
@@ -1345,6 +1430,7 @@ __device__ __forceinline__ void rp_stage_body(const RpModel<T>& M, const RpState
       }
 #pragma unroll
       for (int k = 0; k < 6; k++) in_[k] = isl ? p_inert[6 * L + k] : (T)0;
+      }
       T t[3], A9[9], dd[3];
       mat_vec(t, xm_, ip_);
 #pragma unroll
@@ -1374,7 +1460,8 @@ __device__ __forceinline__ void rp_stage_body(const RpModel<T>& M, const RpState
     // field f of MY contact's record (contact lanes): 0-2 position, 3-5 normal, 6 dist, 7 mu, 8 kterm, 9 B, 10 D
     auto conf = [&](const int f) -> T {
       T v = 0;
-      if constexpr (PART != 1) {
+      if constexpr (PB) v = cfv[f];
+      else if constexpr (PART != 1) {
         if (NCX <= RPK_NCL || lane < RPK_NCL)
           v = f < 3 ? sm.cpos[lane][f] : (f < 6 ? sm.cn[lane][f - 3] : (f == 6 ? sm.cdist[lane] : sm.cpar[lane][f - 7]));
         else v = ovf[(size_t)(lane - RPK_NCL) * 12 + f];
@@ -1384,7 +1471,8 @@ __device__ __forceinline__ void rp_stage_body(const RpModel<T>& M, const RpState
     // ... and its integer fields: 0 link A, 1 link B (or RPK_KEYBASE + key), 2 / 3 model geom ids
     auto coni = [&](const int f) -> int {
       int v = 0;
-      if constexpr (PART != 1) {
+      if constexpr (PB) v = civ[f < 2 ? f : 0];   // (the back part asks for the two bodies only)
+      else if constexpr (PART != 1) {
         if (NCX <= RPK_NCL || lane < RPK_NCL) v = f == 0 ? sm.cA[lane] : (f == 1 ? sm.cB[lane] : (f == 2 ? sm.cgA[lane] : sm.cgB[lane]));
         else v = ovi[(size_t)(lane - RPK_NCL) * 4 + f];
       }
@@ -1395,6 +1483,14 @@ __device__ __forceinline__ void rp_stage_body(const RpModel<T>& M, const RpState
       bool bad = !(N::abs(q[0]) < (T)1e10) || !(N::abs(q[1]) < (T)1e10) || !(N::abs(q[2]) < (T)1e10) ||
                  !(N::abs(qd[0]) < (T)1e10) || !(N::abs(qd[1]) < (T)1e10) || !(N::abs(qd[2]) < (T)1e10);
       if (__ballot(bad)) warn |= 1;
+    }
+    int site_l = 0;
+    T site_p[3] = {0, 0, 0};
+    if constexpr (PF) {   // (the site's link and offset ride with the batch below)
+      const int st_ = lane < M.nsite ? lane : 0;
+      site_l = M.site_link()[st_];
+#pragma unroll
+      for (int k = 0; k < 3; k++) site_p[k] = M.site_pos()[3 * st_ + k];
     }
     RPK_LOAD_GEOMETRY
     // ---- forward kinematics by tree level [MJ: mj_kinematics]
@@ -1442,9 +1538,9 @@ __device__ __forceinline__ void rp_stage_body(const RpModel<T>& M, const RpState
       WSYNC();
     }
     if (MODE == 0 && lane < M.nsite && !(S.stale_outputs && substep == nsub - 1)) {  // site positions of this state
-      int sl = M.site_link()[lane];
+      int sl = PF ? site_l : M.site_link()[lane];
       T t[3];
-      mat_vec(t, sm.xmat[sl], M.site_pos() + 3 * lane);
+      mat_vec(t, sm.xmat[sl], PF ? site_p : M.site_pos() + 3 * lane);
 #pragma unroll
       for (int k = 0; k < 3; k++) S.site_xpos[((size_t)env * M.nsite + lane) * 3 + k] = sm.xpos[sl][k] + t[k];
     }
@@ -1534,7 +1630,24 @@ __device__ __forceinline__ void rp_stage_body(const RpModel<T>& M, const RpState
     const T grb_ = M.geom_rbound()[G_];
     const unsigned gpm0_ = (unsigned)M.geom_pairmask()[2 * G_], gpm1_ = (unsigned)M.geom_pairmask()[2 * G_ + 1];
     const auto gkc_ = M.geom_iskeycap()[G_];
+    if constexpr (PF) {   // (... and the key lanes' constants for the key windows)
+#pragma unroll
+      for (int s = 0; s < 2; s++) {
+        const int K = isk[s] ? kid[s] : 0;
+        krb[s] = M.key_rbound()[K];
+#pragma unroll
+        for (int k = 0; k < 3; k++) { kpos[s][k] = M.key_pos()[3 * K + k]; khalf[s][k] = M.key_half()[3 * K + k]; }
+      }
+    }
     __builtin_amdgcn_sched_barrier(0);
+    if constexpr (PF) {
+#pragma unroll
+      for (int s = 0; s < 2; s++) {
+        krb[s] = isk[s] ? krb[s] : (T)0;
+#pragma unroll
+        for (int k = 0; k < 3; k++) { kpos[s][k] = isk[s] ? kpos[s][k] : (T)0; khalf[s][k] = isk[s] ? khalf[s][k] : (T)0; }
+      }
+    }
     if (isg) {
       const int gl = ggl;
       if (gl >= 0) {
@@ -2229,6 +2342,11 @@ __device__ __forceinline__ void rp_stage_body(const RpModel<T>& M, const RpState
       // in which the waves of the launch arrive; the results do not: they return to the candidate's own records.)
       int nc_ = nwork;
       if (nc_ > RPK_NCAND) { warn |= 64; nc_ = RPK_NCAND; }   // (RP_WARN_SPLIT_FULL)
+#ifndef RPK_MARK
+      if constexpr (PF) {   // (slots 30 / 31 as in the one-kernel stage: candidates narrow-phased / passes -- here: one per stage)
+        if (S.prof && env == 0 && lane == 0) { sm.prof[30] += nc_; sm.prof[31] += 1; }
+      }
+#endif
       WSYNC();
       int rbase = 0;
       int* const cl_ = B.cand + (size_t)env * RPK_NCAND * 2;
@@ -2239,16 +2357,24 @@ __device__ __forceinline__ void rp_stage_body(const RpModel<T>& M, const RpState
         const int pair = in ? sm.clist[in ? i : 0] : 0;
         const int ga = pair & 0xffff, gb = (pair >> 16) & 0xffff;
         const int ta = M.geom_type()[ga];
+        // (PF: both geoms' types and vertex addresses in one trip -- they were three, one behind the other)
+        int tyb_ = 0, va_ = 0, vb_ = 0, vlast_ = 0;
+        if constexpr (PF) {
+          const int gbc = gb >= RPK_KEYBASE ? 0 : gb;
+          tyb_ = M.geom_type()[gbc];
+          if (MESH != 0) { va_ = M.geom_vertadr()[ga]; vb_ = M.geom_vertadr()[gbc]; vlast_ = M.geom_vertadr()[M.ngeom > 0 ? M.ngeom - 1 : 0]; }
+          __builtin_amdgcn_sched_barrier(0);
+        }
         int ty;
         if (gb >= RPK_KEYBASE) ty = ta == GEOM_CAPSULE_ ? 1 : (ta == GEOM_BOX_ ? 2 : 3);
         else {
-          const int tb = M.geom_type()[gb];
+          const int tb = PF ? tyb_ : M.geom_type()[gb];
           ty = tb == GEOM_CAPSULE_ ? 0 : ((tb == GEOM_MESH_ || ta == GEOM_MESH_ || (MESH > 1 && (ta == GEOM_CYL_ || tb == GEOM_CYL_))) ? 3 : (ta == GEOM_CAPSULE_ ? 1 : 2));
         }
         if (MESH != 0 && ty == 3) {   // hull pairs: the bucket of lanes that need the same vertex scans (rp_model.hpp)
           const int hb_ = gb >= RPK_KEYBASE ? ga : gb;   // (side B of the refinement: the hull)
-          const int vlast = M.geom_vertadr()[M.ngeom > 0 ? M.ngeom - 1 : 0];   // (geoms are sorted by type: hulls last)
-          ty = 3 + ((gb < RPK_KEYBASE && ta == GEOM_MESH_) ? 1 : 0) + (M.geom_vertadr()[hb_] != vlast ? 2 : 0);
+          const int vlast = PF ? vlast_ : M.geom_vertadr()[M.ngeom > 0 ? M.ngeom - 1 : 0];   // (geoms are sorted by type: hulls last)
+          ty = 3 + ((gb < RPK_KEYBASE && ta == GEOM_MESH_) ? 1 : 0) + ((PF ? (gb >= RPK_KEYBASE ? va_ : vb_) : M.geom_vertadr()[hb_]) != vlast ? 2 : 0);
         }
         const int wdt = ty == 2 ? 8 : (ty >= 3 ? 1 : 2);
         int incl = in ? wdt : 0;
@@ -2292,6 +2418,14 @@ __device__ __forceinline__ void rp_stage_body(const RpModel<T>& M, const RpState
       // ---- split stage, back part: the link frames the front part left, then the narrow phase's contacts in the
       // emission order of the whole stage -- candidates in chunks of 64 (the passes of its work list), within a chunk
       // point 1 of every candidate, then point 2, ... -- so that both ways of running the stage produce the same bits.
+      if constexpr (PB) {   // (requested in the prologue)
+        if (isl) {
+#pragma unroll
+          for (int k = 0; k < 3; k++) { sm.xpos[lane][k] = frv[k]; sm.xaxis[lane][k] = frv[12 + k]; sm.xanchor[lane][k] = frv[15 + k]; }
+#pragma unroll
+          for (int k = 0; k < 9; k++) sm.xmat[lane][k] = frv[3 + k];
+        }
+      } else
       if (isl) {
         const T* fr_ = B.frames + (size_t)env * RPK_NFRAME * 64 + lane;
 #pragma unroll
@@ -2306,14 +2440,24 @@ __device__ __forceinline__ void rp_stage_body(const RpModel<T>& M, const RpState
         if (isk[s]) { N::sincos(q[1 + s], &ksin[s], &kcos[s]); sm.keyslot[kid[s]] = -1; }
       }
       ncon = 0;
-      const int nc_ = B.ncand[env];
+      const int nc_ = PB ? ncand_pre : B.ncand[env];
       const int* const cl_ = B.cand + (size_t)env * RPK_NCAND * 2;
       const T* const res_ = B.cres + (size_t)env * RPK_NRES * 12;
+      int pair_c = cand_pre[0], meta_c = cand_pre[1], n_c = cand_pre[2];   // PB: this chunk's records (the first chunk's: read in the prologue)
       for (int c0 = 0; c0 < nc_; c0 += 64) {
         const int i = c0 + lane;
         const bool in = i < nc_;
-        const int pair = in ? cl_[2 * i] : 0, meta = in ? cl_[2 * i + 1] : 0;
-        const int n = in ? B.cres_n[(size_t)env * RPK_NCAND + i] : 0;
+        int pair, meta, n;
+        if constexpr (PB) {
+          pair = in ? pair_c : 0; meta = in ? meta_c : 0; n = in ? n_c : 0;
+          if (c0 + 64 < nc_) {   // (the next chunk's records are requested ahead, with this chunk's tables and results)
+            const int j = i + 64 < RPK_NCAND ? i + 64 : 0;
+            pair_c = cl_[2 * j]; meta_c = cl_[2 * j + 1]; n_c = B.cres_n[(size_t)env * RPK_NCAND + j];
+          }
+        } else {
+          pair = in ? cl_[2 * i] : 0; meta = in ? cl_[2 * i + 1] : 0;
+          n = in ? B.cres_n[(size_t)env * RPK_NCAND + i] : 0;
+        }
         const int ga = pair & 0xffff, gb = (pair >> 16) & 0xffff, rb = meta & 0xffff;
         const int iA = M.geom_link()[ga], iB = gb >= RPK_KEYBASE ? gb : M.geom_link()[gb >= RPK_KEYBASE ? 0 : gb];
         const int igA = M.geom_modelid()[ga], igB = gb >= RPK_KEYBASE ? M.key_geomid()[gb - RPK_KEYBASE] : M.geom_modelid()[gb >= RPK_KEYBASE ? 0 : gb];
@@ -2390,7 +2534,8 @@ __device__ __forceinline__ void rp_stage_body(const RpModel<T>& M, const RpState
 
     // The position / velocity stages are register-bound around the narrow phase: the state is re-read here
     // (L2 hits) instead of being carried -- that is: spilled to scratch and reloaded -- across the collision.
-    if constexpr (MODE != 1) {
+    // (PB: the back part's collection loop is no collision phase -- the prologue's values are carried, two dependent trips less)
+    if constexpr (MODE != 1 && !PB) {
       {
         const int4* rec = (const int4*)(fresh(M.lane_topo()) + 16 * L);
         const int4 r0 = rec[0], r1 = rec[1], r2 = rec[2];
@@ -2410,6 +2555,23 @@ __device__ __forceinline__ void rp_stage_body(const RpModel<T>& M, const RpState
         q[1 + s] = isk[s] ? p_q[eo + kdof[s]] : (T)0;
         qd[1 + s] = isk[s] ? p_v[eo + kdof[s]] : (T)0;
       }
+    }
+    if constexpr (PB) {
+      // my contact's record, all fields in one go (LDS; the lanes past RPK_NCL: the env's overflow records): fetched field
+      // by field where it was used, every field was a round trip of its own
+      const int a_ = lane < RPK_NCL ? lane : 0;
+#pragma unroll
+      for (int k = 0; k < 3; k++) { cfv[k] = sm.cpos[a_][k]; cfv[3 + k] = sm.cn[a_][k]; }
+      cfv[6] = sm.cdist[a_];
+#pragma unroll
+      for (int k = 0; k < 4; k++) cfv[7 + k] = sm.cpar[a_][k];
+      civ[0] = sm.cA[a_]; civ[1] = sm.cB[a_];
+      if (NCX > RPK_NCL && lane >= RPK_NCL && lane < ncon) {
+#pragma unroll
+        for (int k = 0; k < 11; k++) cfv[k] = ovf[(size_t)(lane - RPK_NCL) * 12 + k];
+        civ[0] = ovi[(size_t)(lane - RPK_NCL) * 4]; civ[1] = ovi[(size_t)(lane - RPK_NCL) * 4 + 1];
+      }
+      __builtin_amdgcn_sched_barrier(0);
     }
     PROF(13);
     // ---- solver slots for touched keys
@@ -2657,6 +2819,16 @@ __device__ __forceinline__ void rp_stage_body(const RpModel<T>& M, const RpState
     // VELOCITY STAGE
     // ======================================================================
     // ---- spatial velocities, axis derivatives [MJ: mj_comVel]
+    if constexpr (PB) {
+      // (what mj_comVel, the RNE and the link inertia read per link, in flight together: L and ltree are 0 for the lanes
+      // without a link)
+#pragma unroll
+      for (int k = 0; k < 3; k++) { v_tref[k] = M.tree_ref()[3 * ltree + k]; v_ipos[k] = M.link_ipos()[3 * L + k]; }
+#pragma unroll
+      for (int k = 0; k < 6; k++) v_inert[k] = M.link_inertia()[6 * L + k];
+      v_mass = M.link_mass()[L]; v_gscale = M.link_gscale()[L];
+      __builtin_amdgcn_sched_barrier(0);
+    }
     if constexpr (MODE != 1) {
       // the motion axis about the tree reference point again, from the link frames in LDS (same arithmetic
       // as in mj_comPos above: same bits), instead of six more registers carried across the collision
@@ -2669,7 +2841,7 @@ __device__ __forceinline__ void rp_stage_body(const RpModel<T>& M, const RpState
         } else {
           T off[3];
 #pragma unroll
-          for (int k = 0; k < 3; k++) off[k] = p_tref[3 * ltree + k] - sm.xanchor[lane][k];
+          for (int k = 0; k < 3; k++) off[k] = (PB ? v_tref[k] : p_tref[3 * ltree + k]) - sm.xanchor[lane][k];
           cdofr[0] = axw[0]; cdofr[1] = axw[1]; cdofr[2] = axw[2];
           cross3(cdofr + 3, axw, off);
         }
@@ -2694,7 +2866,7 @@ __device__ __forceinline__ void rp_stage_body(const RpModel<T>& M, const RpState
     }
     // ---- bias forces: recursive Newton-Euler with gravity as base acceleration [MJ: mj_rne]
     T ca[6] = {0, 0, 0, 0, 0, 0};
-    const T gscale = fresh(M.link_gscale())[L];   // (once, in front of the level loop: inside it every level waited for its own trip to L2)
+    const T gscale = PB ? v_gscale : fresh(M.link_gscale())[L];   // (once, in front of the level loop: inside it every level waited for its own trip to L2)
     for (int d = 0; d < M.maxdepth; d++) {
       if (isl && depth == d) {
         T pa[6] = {0, 0, 0, -M.gx * gscale, -M.gy * gscale, -M.gz * gscale};
@@ -2727,6 +2899,30 @@ __device__ __forceinline__ void rp_stage_body(const RpModel<T>& M, const RpState
       }
     }
     WSYNC();
+    // PB: everything the transmission, the constraint rows and the outputs read from the model -- the actuator's lanes and
+    // coefficients, range / K / B / 1/w / solimp of the link's dof and of the two key dofs, the friction-loss B, the key
+    // actuators' coefficient -- requested here, in flight while the subtree forces are summed.  (solimp was a load under
+    // lim_sign != 0 behind the range's own trip: now it is there when the range is.)
+    int r_alane[2] = {0, -1};
+    T r_acoef[2], r_lo[3], r_hi[3], r_K[3], r_B[3], r_W[3], r_flB = 0, r_si[3][5];
+    if constexpr (PB) {
+      r_alane[0] = M.act_lane()[2 * A]; r_alane[1] = M.act_lane()[2 * A + 1];
+      r_acoef[0] = M.act_coef()[2 * A]; r_acoef[1] = M.act_coef()[2 * A + 1];
+      r_lo[0] = M.link_range()[2 * L]; r_hi[0] = M.link_range()[2 * L + 1];
+      r_K[0] = M.link_lim_K()[L]; r_B[0] = M.link_lim_B()[L]; r_W[0] = M.link_invw_dof()[L]; r_flB = M.link_fl_B()[L];
+#pragma unroll
+      for (int k = 0; k < 5; k++) r_si[0][k] = M.link_lim_solimp()[5 * L + k];
+#pragma unroll
+      for (int s = 0; s < 2; s++) {
+        const int K = isk[s] ? kid[s] : 0, ka = kact[s] >= 0 ? kact[s] : 0;
+        r_lo[1 + s] = M.key_range()[2 * K]; r_hi[1 + s] = M.key_range()[2 * K + 1];
+        r_K[1 + s] = M.key_lim_K()[K]; r_B[1 + s] = M.key_lim_B()[K]; r_W[1 + s] = M.key_invw_dof()[K];
+#pragma unroll
+        for (int k = 0; k < 5; k++) r_si[1 + s][k] = M.key_lim_solimp()[5 * K + k];
+        r_kacoef[s] = M.act_coef()[2 * ka];
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    }
     for (int d = M.maxdepth - 1; d >= 1; d--) {
       if (isl && depth == d) {
 #pragma unroll
@@ -2743,8 +2939,8 @@ __device__ __forceinline__ void rp_stage_body(const RpModel<T>& M, const RpState
     WSYNC();
     if (isa) {
       // (read here, not in the prologue: nothing else needs them and the stage is register-bound)
-      const int alane0 = fresh(M.act_lane())[2 * A], alane1 = fresh(M.act_lane())[2 * A + 1];
-      const T acoef0 = fresh(M.act_coef())[2 * A], acoef1 = fresh(M.act_coef())[2 * A + 1];
+      const int alane0 = PB ? r_alane[0] : fresh(M.act_lane())[2 * A], alane1 = PB ? r_alane[1] : fresh(M.act_lane())[2 * A + 1];
+      const T acoef0 = PB ? r_acoef[0] : fresh(M.act_coef())[2 * A], acoef1 = PB ? r_acoef[1] : fresh(M.act_coef())[2 * A + 1];
       alen = acoef0 * sm.vec[0][alane0] + (alane1 >= 0 ? acoef1 * sm.vec[0][alane1] : (T)0);
       avel = acoef0 * sm.vec[1][alane0] + (alane1 >= 0 ? acoef1 * sm.vec[1][alane1] : (T)0);
     }
@@ -2760,7 +2956,12 @@ __device__ __forceinline__ void rp_stage_body(const RpModel<T>& M, const RpState
         if (dl < 0) { lim_sign[s] = 1; dist = dl; }
         else if (du < 0) { lim_sign[s] = -1; dist = du; }
         if (lim_sign[s] != 0) {
-          const T* si = (s == 0) ? (M.link_lim_solimp() + 5 * L) : (M.key_lim_solimp() + 5 * kid[s - 1]);
+          T sil[5] = {0, 0, 0, 0, 0};
+          if constexpr (PB) {
+#pragma unroll
+            for (int k = 0; k < 5; k++) sil[k] = r_si[s][k];
+          }
+          const T* si = PB ? sil : ((s == 0) ? (M.link_lim_solimp() + 5 * L) : (M.key_lim_solimp() + 5 * kid[s - 1]));
           T imp = impedance(si, dist);
           T R = fmax(RPK_MINVAL, ((T)1 - imp) * limW[s] / imp);
           lim_D[s] = (T)1 / R;
@@ -2942,7 +3143,7 @@ __device__ __forceinline__ void rp_stage_body(const RpModel<T>& M, const RpState
   if (!(S.stale_outputs && substep == nsub - 1)) {   // (legacy_step = False: see RpState::stale_outputs)
 #pragma unroll
   for (int s = 0; s < 2; s++) if (isk[s]) {
-    if (kact[s] >= 0) S.act_vel[(size_t)env * nu + kact[s]] = M.act_coef()[2 * kact[s]] * qd[1 + s];
+    if (kact[s] >= 0) S.act_vel[(size_t)env * nu + kact[s]] = (PB ? r_kacoef[s] : M.act_coef()[2 * kact[s]]) * qd[1 + s];
   }
   if (isa) S.act_vel[(size_t)env * nu + lane] = avel;
   if (lane < RPK_NCOUT) {
