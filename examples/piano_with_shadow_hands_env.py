@@ -22,8 +22,9 @@ import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from robopianist_amd import suite  # noqa: E402
-from robopianist_amd.wrappers import (AudioObservationWrapper, CanonicalSpecWrapper, MidiEvaluationWrapper,  # noqa: E402
-                                      PianoSoundVideoWrapper, PianoSoundWrapper, PixelWrapper)
+from robopianist_amd.suite.fingertip_pianist import FingeringPianist  # noqa: E402
+from robopianist_amd.wrappers import (AudioObservationWrapper, CanonicalSpecWrapper, FingertipActionWrapper,  # noqa: E402
+                                      MidiEvaluationWrapper, PianoSoundVideoWrapper, PianoSoundWrapper, PixelWrapper)
 
 
 def main() -> None:
@@ -49,6 +50,13 @@ def main() -> None:
     ap.add_argument("--hear", action="store_true",
                     help="wrap the env in AudioObservationWrapper (88 magnitudes of the last 2048 samples at 16 kHz) and print "
                          "the observation's shape and the loudest bin's key of env 0 every step")
+    ap.add_argument("--fingertip-pianist", dest="fingertip_pianist", action="store_true",
+                    help="command the hands in fingertip space (FingertipActionWrapper, absolute targets) and let "
+                         "FingeringPianist play: every finger the MIDI's fingering assigns to a key aims at it; prints the "
+                         "episode's F1")
+    ap.add_argument("--press_depth", type=float, default=0.01,
+                    help="with --fingertip-pianist: metres below a key's surface target the assigned finger aims at")
+    ap.add_argument("--ik_iterations", type=int, default=1, help="with --fingertip-pianist: IK steps per control step")
     ap.add_argument("--record", action="store_true",
                     help="record env 0 with PianoSoundWrapper and write its episode as a WAV file")
     ap.add_argument("--video", action="store_true",
@@ -57,6 +65,8 @@ def main() -> None:
     args = ap.parse_args()
     if args.video and not args.record:
         ap.error("--video needs --record")
+    if args.fingertip_pianist and (args.canonicalize or args.action_sequence):
+        ap.error("--fingertip-pianist commands fingertips: it takes neither --canonicalize nor --action_sequence")
 
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")
@@ -72,6 +82,10 @@ def main() -> None:
                 disable_forearm_reward=args.disable_forearm_reward,
                 disable_colorization=args.disable_colorization,
                 disable_hand_collisions=args.disable_hand_collisions, attachment_yaw=args.attachment_yaw))
+    pianist = fingertips = None
+    if args.fingertip_pianist:
+        env = fingertips = FingertipActionWrapper(env, mode="absolute", iterations=args.ik_iterations)
+        pianist = FingeringPianist(env, press_depth=args.press_depth)
     if args.canonicalize:
         env = CanonicalSpecWrapper(env)
     env = MidiEvaluationWrapper(env)
@@ -107,8 +121,13 @@ def main() -> None:
     n_steps, ret = 0, torch.zeros(E, device=dev, dtype=env.physics.dtype)
     t0 = time.perf_counter()
     while True:
-        a = actions[n_steps] if actions is not None and n_steps < len(actions) else zeros
-        timestep = env.step(torch.as_tensor(a, device=dev, dtype=env.physics.dtype).expand(E, -1))
+        if pianist is not None:
+            a, weights = pianist.action()
+            fingertips.set_weights(weights, validate=False)
+            timestep = env.step(a)
+        else:
+            a = actions[n_steps] if actions is not None and n_steps < len(actions) else zeros
+            timestep = env.step(torch.as_tensor(a, device=dev, dtype=env.physics.dtype).expand(E, -1))
         ret += timestep.reward
         n_steps += 1
         if args.hear:   # (a demonstration: the read-back is this print's, not the wrapper's)
@@ -121,8 +140,11 @@ def main() -> None:
     dt = time.perf_counter() - t0
     print(f"episode: {n_steps} control steps x {E} envs in {dt:.2f} s = {E * n_steps / dt:,.0f} env-steps/s")
     print(f"mean return {float(ret.mean()):.3f}")
-    for k, v in env.get_musical_metrics().items():
+    metrics = env.get_musical_metrics()
+    for k, v in metrics.items():
         print(f"\t{k}: {v:.4f}")
+    if pianist is not None:
+        print(f"fingertip pianist: F1 {metrics['f1']:.4f} (press depth {args.press_depth} m, {args.ik_iterations} IK step(s) per control step)")
     print(f"warn flags: {int(env.physics.warn.max())}")
     if args.record:
         print("recorded: " + (", ".join(str(p) for p in env.written) or "nothing (the episode has no note)"))

@@ -1,0 +1,232 @@
+"""ctypes binding of the fingertip inverse kinematics' C ABI (include/control/rp_ik.h, librp_ik.so).
+
+`FingertipIK` turns fingertip targets of a batch of environments into actuator-space position targets with damped
+least-squares steps on the hands' kinematic trees, from the engine's qpos array, on the caller's HIP stream, into torch
+tensors it caches.  Tips are numbered in fingering order (right 0-4, left 5-9; 0-4 in a one-hand scene); the output
+columns are the task's action order (the right hand's actuators, then the left's).  Like the engine, it has no CPU
+fallback: a missing library is an error.
+"""
+
+from __future__ import annotations
+
+import ctypes
+import os
+
+import numpy as np
+
+from robopianist_amd.model import ik_tables
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+LIB_PATH = os.environ.get("RP_IK_LIB") or os.path.join(_HERE, "csrc", "librp_ik.so")
+
+EXPORTED_SYMBOLS = ("rp_ik_create", "rp_ik_destroy", "rp_ik_solve", "rp_ik_dim", "rp_ik_last_error")
+
+DEFAULT_DAMPING = 0.03
+DEFAULT_MAX_STEP = 0.02
+
+_lib = None
+
+
+class IKError(RuntimeError):
+    pass
+
+
+class IKArgs(ctypes.Structure):
+    """rp_ik_args (include/control/rp_ik.h)."""
+    _fields_ = [
+        ("struct_size", ctypes.c_size_t),
+        ("qpos", ctypes.c_void_p),
+        ("tree_offset", ctypes.c_void_p),
+        ("target", ctypes.c_void_p),
+        ("weight", ctypes.c_void_p),
+        ("dof_weight", ctypes.c_void_p),
+        ("delta", ctypes.c_int), ("iterations", ctypes.c_int),
+        ("damping", ctypes.c_double),
+        ("max_step", ctypes.c_double),
+        ("out", ctypes.c_void_p),
+        ("out_stride", ctypes.c_longlong),
+        ("q_target", ctypes.c_void_p),
+        ("residual", ctypes.c_void_p),
+        ("tips", ctypes.c_void_p),
+        ("env_first", ctypes.c_int), ("env_count", ctypes.c_int),
+        ("hip_stream", ctypes.c_void_p),
+    ]
+
+
+def make_args(env_first, env_count, qpos=None, tree_offset=None, target=None, weight=None, dof_weight=None, delta=False,
+              damping=DEFAULT_DAMPING, max_step=DEFAULT_MAX_STEP, iterations=1, out=None, out_stride=0, q_target=None,
+              residual=None, tips=None, hip_stream=None) -> IKArgs:
+    """Fills an rp_ik_args; the array arguments are raw addresses (or None)."""
+    a = IKArgs()
+    a.struct_size = ctypes.sizeof(IKArgs)
+    a.qpos, a.tree_offset, a.target, a.weight, a.dof_weight = qpos, tree_offset, target, weight, dof_weight
+    a.delta, a.iterations = int(bool(delta)), int(iterations)
+    a.damping, a.max_step = float(damping), float(max_step)
+    a.out, a.out_stride = out, int(out_stride)
+    a.q_target, a.residual, a.tips = q_target, residual, tips
+    a.env_first, a.env_count = int(env_first), int(env_count)
+    a.hip_stream = hip_stream
+    return a
+
+
+def declare(L, prefix: str = "rp_ik_"):
+    """Declares the ABI's prototypes on a loaded library whose symbols start with `prefix`."""
+    f = lambda name: getattr(L, prefix + name)
+    f("last_error").restype = ctypes.c_char_p
+    f("create").argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                            ctypes.POINTER(ctypes.c_void_p)]
+    f("destroy").argtypes = [ctypes.c_void_p]
+    f("destroy").restype = None
+    f("solve").argtypes = [ctypes.c_void_p, ctypes.POINTER(IKArgs)]
+    f("dim").argtypes = [ctypes.c_void_p, ctypes.c_char_p]
+    return L
+
+
+def load_library(path: str = LIB_PATH):
+    """Loads librp_ik.so; raises IKError if it has not been built."""
+    global _lib
+    if _lib is not None:
+        return _lib
+    if not os.path.exists(path):
+        raise IKError(
+            f"HIP inverse-kinematics library not found at {path}. Build it with "
+            "`python -c 'import __graft_entry__ as g; g.build()'` (hipcc, gfx950). "
+            "There is no CPU fallback.")
+    try:   # torch's HIP runtime first, as in engine.load_library
+        import torch  # noqa: F401
+    except ImportError:
+        pass
+    _lib = declare(ctypes.CDLL(path))
+    return _lib
+
+
+class FingertipIK:
+    """Batched fingertip IK of one compiled scene (`scene_info`: model/scene.py SceneInfo)."""
+
+    def __init__(self, scene_info, n_envs: int, device_id: int = 0, precision: int = 64):
+        self._L = load_library()
+        self.model = scene_info.model
+        self.n_envs, self.device_id, self.precision = int(n_envs), int(device_id), int(precision)
+        self.tables = ik_tables.build_ik_tables(scene_info)
+        self.blob = ik_tables.make_ik_blob(scene_info, tables=self.tables)
+        self._h = ctypes.c_void_p()
+        rc = self._L.rp_ik_create(self.blob, len(self.blob), self.n_envs, self.device_id, self.precision,
+                                  ctypes.byref(self._h))
+        if rc != 0:
+            raise IKError(self._L.rp_ik_last_error().decode())
+        dim = lambda name: self._L.rp_ik_dim(self._h, name)
+        self.n_hands, self.n_tips, self.n_act, self.n_dof = dim(b"n_hands"), dim(b"n_tips"), dim(b"n_act"), dim(b"n_dof")
+        self.ntree = dim(b"ntree")
+        self._out = {}
+        self._keep = None
+
+    def __del__(self):
+        try:
+            if self._h:
+                self._L.rp_ik_destroy(self._h)
+                self._h = ctypes.c_void_p()
+        except Exception:
+            pass
+
+    # -- cached tensors ----------------------------------------------------------------------------------------------
+    def _cached(self, name, shape, dtype):
+        import torch
+        if name not in self._out:
+            self._out[name] = torch.zeros(shape, dtype=dtype, device=torch.device("cuda", self.device_id))
+        return self._out[name]
+
+    @property
+    def dtype(self):
+        import torch
+        return torch.float32 if self.precision == 32 else torch.float64
+
+    def outputs(self):
+        """The cached output tensors: (ctrl [E, n_act] of the solver's precision, q_target [E, n_dof], residual [E, T],
+        tips [E, T, 3], the last three float64), allocated at the first call."""
+        import torch
+        E = self.n_envs
+        return (self._cached("ctrl", (E, self.n_act), self.dtype), self._cached("q", (E, self.n_dof), torch.float64),
+                self._cached("residual", (E, self.n_tips), torch.float64),
+                self._cached("tips", (E, self.n_tips, 3), torch.float64))
+
+    def solve_raw(self, args: IKArgs) -> int:
+        """rp_ik_solve with a caller-made argument block; returns the C return code (see last_error())."""
+        return self._L.rp_ik_solve(self._h, ctypes.byref(args))
+
+    def last_error(self) -> str:
+        return self._L.rp_ik_last_error().decode()
+
+    def _device_f64(self, x, shape, what, nonnegative=False):
+        """`x` as a contiguous float64 device tensor of `shape`.  Host data (numpy, lists, CPU tensors) is checked and
+        uploaded; a device tensor is taken as it is, without a read-back."""
+        import torch
+        dev = torch.device("cuda", self.device_id)
+        if not (isinstance(x, torch.Tensor) and x.is_cuda):
+            host = np.ascontiguousarray(np.asarray(x.detach().numpy() if isinstance(x, torch.Tensor) else x, np.float64))
+            if nonnegative and not (host >= 0).all():
+                raise IKError(f"solve: {what} must be >= 0")
+            x = torch.as_tensor(host, device=dev)
+        if tuple(x.shape) != tuple(shape):
+            raise IKError(f"solve: {what} must have shape {tuple(shape)}, got {tuple(x.shape)}")
+        if x.dtype != torch.float64 or not x.is_contiguous():
+            x = x.to(torch.float64).contiguous()
+        return x
+
+    def solve(self, qpos, targets, weights=None, delta=False, tree_offset=None, damping=DEFAULT_DAMPING,
+              max_step=DEFAULT_MAX_STEP, iterations=1, out=None, want_q=False, want_residual=False, want_tips=False,
+              dof_weight=None, env_first: int = 0, env_count=None, hip_stream=None):
+        """qpos / tree_offset: contiguous device tensors ([E, nv] and [E, ntree, 3] of the solver's precision, e.g. the
+        engine's zero-copy views).  targets [E, T, 3] and weights [E, T] (None = 1): float64; device tensors are used in
+        place, host data is uploaded (and negative weights are refused; weights on the device must be >= 0).
+        dof_weight: host [n_dof] >= 0 or None.  out: a device tensor [E, >= n_act] of the solver's precision whose rows
+        are contiguous (default: the cached one); columns past n_act are not touched.
+        Returns `out`, or (out, q_target, residual, tips) restricted to what was asked for, in that order.  Enqueues one
+        kernel on `hip_stream` (default: torch's current stream); nothing is read back."""
+        import torch
+        if hip_stream is None:
+            hip_stream = torch.cuda.current_stream(torch.device("cuda", self.device_id)).cuda_stream
+        E, T = self.n_envs, self.n_tips
+        for t, shape in ((qpos, (E, int(self.model.nv))), (tree_offset, (E, self.ntree, 3))):
+            if t is None:
+                continue
+            if tuple(t.shape) != shape or not t.is_contiguous() or not t.is_cuda:
+                raise IKError(f"solve: expected a contiguous device tensor of shape {shape}, got {tuple(t.shape)}")
+            if t.dtype != self.dtype:
+                raise IKError(f"solve: qpos / tree_offset must be {self.dtype}")
+        if qpos is None:
+            raise IKError("solve: qpos is None")
+        targets = self._device_f64(targets, (E, T, 3), "targets")
+        if weights is not None:
+            weights = self._device_f64(weights, (E, T), "weights", nonnegative=True)
+        dw = None
+        if dof_weight is not None:
+            dw = np.ascontiguousarray(np.asarray(dof_weight, np.float64))
+            if dw.shape != (self.n_dof,):
+                raise IKError(f"solve: dof_weight must have shape ({self.n_dof},)")
+        o_ctrl, o_q, o_res, o_tips = self.outputs()
+        if out is None:
+            out = o_ctrl
+        elif (not out.is_cuda or out.dtype != self.dtype or out.dim() != 2 or out.shape[0] != E or out.shape[1] < self.n_act
+              or out.stride(1) != 1 or out.stride(0) < out.shape[1]):
+            raise IKError(f"solve: out must be a device tensor [{E}, >= {self.n_act}] of {self.dtype} with contiguous rows")
+        a = make_args(env_first, E - env_first if env_count is None else env_count, qpos=qpos.data_ptr(),
+                      tree_offset=tree_offset.data_ptr() if tree_offset is not None else None,
+                      target=targets.data_ptr(), weight=weights.data_ptr() if weights is not None else None,
+                      dof_weight=dw.ctypes.data if dw is not None else None, delta=delta, damping=damping,
+                      max_step=max_step, iterations=iterations, out=out.data_ptr(), out_stride=out.stride(0),
+                      q_target=o_q.data_ptr() if want_q else None, residual=o_res.data_ptr() if want_residual else None,
+                      tips=o_tips.data_ptr() if want_tips else None, hip_stream=hip_stream)
+        if self._L.rp_ik_solve(self._h, ctypes.byref(a)) != 0:
+            raise IKError(self.last_error())
+        self._keep = (targets, weights)   # alive until the kernel has run
+        extra = [t for t, want in ((o_q, want_q), (o_res, want_residual), (o_tips, want_tips)) if want]
+        return (out, *extra) if extra else out
+
+    def tip_positions(self, qpos, tree_offset=None):
+        """World positions of the fingertips at `qpos`, [E, T, 3] float64 (the cached tensor): a solve with zero weights
+        and a zero delta, which moves nothing.  The test seam against `physics.site_xpos`."""
+        import torch
+        zeros = self._cached("zero_targets", (self.n_envs, self.n_tips, 3), torch.float64)
+        zw = self._cached("zero_weights", (self.n_envs, self.n_tips), torch.float64)
+        scratch = self._cached("tips_ctrl", (self.n_envs, self.n_act), self.dtype)
+        return self.solve(qpos, zeros, weights=zw, delta=True, tree_offset=tree_offset, out=scratch, want_tips=True)[1]
