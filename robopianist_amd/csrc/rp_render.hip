@@ -158,7 +158,7 @@ int rp_render(rp_renderer* r, const rp_render_args* a) {
     const size_t lds = sizeof(float) * RPR_FRAME * (size_t)(r->M.ngeom ? r->M.ngeom : 1);
     // the env is the grid's y index, which the device limits to 65535: larger batches go out in slices
     for (int first = 0; first < a->env_count; first += RPR_MAX_GRID_Y) {
-      const int count = rpr_slice_count(a->env_count, first);   // (tests: the arithmetic on the host; no GPU test has > 65535 envs)
+      const int count = rpr_slice_count(a->env_count, first);   // (tests: the arithmetic on the host; 65540 envs in two launches on the GPU)
       const dim3 grid((unsigned)((npix + 255) / 256), (unsigned)count), block(256);
       hipLaunchKernelGGL(rp_render_kernel, grid, block, lds, st, r->M, cam, (const float*)r->d_frames, a->key_rgb, a->rgb,
                          a->depth, a->segmentation, a->env_first + first);

@@ -15,6 +15,11 @@ other eleven images: 0.7e-05 .. 4.4e-05).  DEPTH_TOL = 4 x that = 2.1988e-04: th
 0.2273 % of an image (3 pixels of 1320: scene "cylinder", camera topdown; back: 0.0758 %, closeup and free: none), under
 a quarter of the 1 % cap on every camera, so the 30 x 44 images and the cameras back / closeup / free / topdown are used
 as they are (no yawed camera and no other size were needed).
+
+The wide cases (`wide_cases`, `mixed_batch`) are judged by the SAME two figures.  The same evaluation over them gives a
+depth rounding of at most 4.2014e-05 (scene "capsule", topdown, 32 x 40) and a segmentation disagreement of at most
+0.1515 % (two pixels of 1320, mixed batch); tests/test_render_host.py asserts both per case, so a case that would need a
+wider bound cannot be added: it has to move to another size or pose (two did, see _WIDE_SPEC and LOOK_AT_CAMERAS).
 """
 import ctypes
 import os
@@ -204,14 +209,18 @@ def geom_colours(si, colorize_fingertips=False):
     return col
 
 
-def reference_render(si, xpos, xmat, cam, height=H, width=W, dtype=np.float64, key_rgb=None, colorize_fingertips=False):
-    """Returns (rgb uint8 [H,W,3], depth float32-valued [H,W] of `dtype`, segmentation int32 [H,W])."""
+def reference_render(si, xpos, xmat, cam, height=H, width=W, dtype=np.float64, key_rgb=None, colorize_fingertips=False,
+                     stats=None):
+    """Returns (rgb uint8 [H,W,3], depth float32-valued [H,W] of `dtype`, segmentation int32 [H,W]).  stats: an optional
+    dict that receives "exit_pixels", the number of pixels whose visible hit is a shape's EXIT (the camera, or the ray's
+    origin, lies inside that shape)."""
     from robopianist_amd.model import spec, render_tables as rt
     f = dtype
     m = si.model
     o, d = pixel_rays(cam, height, width, f)
     P = o.shape[0]
     best_t = np.full(P, np.inf, f); best_id = np.full(P, -1, np.int32); best_n = np.zeros((P, 3), f)
+    best_exit = np.zeros(P, bool)
     col = geom_colours(si, colorize_fingertips)
     if key_rgb is not None:
         col[np.asarray(si.key_geom_ids)] = np.asarray(key_rgb, float) / 255.0
@@ -235,18 +244,22 @@ def reference_render(si, xpos, xmat, cam, height=H, width=W, dtype=np.float64, k
         nw = np.stack([R[i, 0] * n[:, 0] + R[i, 1] * n[:, 1] + R[i, 2] * n[:, 2] for i in range(3)], 1)
         best_t = np.where(better, t, best_t); best_id = np.where(better, g, best_id)
         best_n = np.where(better[:, None], nw, best_n)
+        best_exit = np.where(better, ~entry, best_exit)
     with np.errstate(divide="ignore", invalid="ignore"):
         tf = -o[:, 2] / d[:, 2]
         x = o[:, 0] + tf * d[:, 0]; y = o[:, 1] + tf * d[:, 1]
         fl = (d[:, 2] != 0) & (tf > 0) & (tf < best_t) & (np.abs(x) <= rt.FLOOR_HALF_SIZE) & (np.abs(y) <= rt.FLOOR_HALF_SIZE)
     best_t = np.where(fl, tf, best_t); best_id = np.where(fl, m.ngeom, best_id)
     best_n = np.where(fl[:, None], np.array([0, 0, 1], f)[None, :], best_n)
+    if stats is not None:
+        stats["exit_pixels"] = int((best_exit & ~fl).sum())
     colour = np.concatenate([col, [rt.FLOOR_COLOR], [rt.BACKGROUND_COLOR]], 0).astype(f)[best_id]   # (-1 = the last row)
     hitp = o + np.where(np.isfinite(best_t), best_t, 0)[:, None] * d
     shade = np.full(P, 0.4, f)
     for L in rt.LIGHT_POSITIONS:
         l = np.asarray(L, float).astype(f)[None, :] - hitp
-        l = l / np.sqrt(_dot(l, l))[:, None]
+        with np.errstate(invalid="ignore"):      # (a background pixel of a camera AT a light: its shade is replaced below)
+            l = l / np.sqrt(_dot(l, l))[:, None]
         shade = shade + f(0.3) * np.maximum(0, _dot(best_n, l))
     shade = np.where(best_id < 0, 1.0, shade).astype(f)
     rgb = np.floor(255 * np.clip(colour * shade[:, None], 0, 1) + 0.5).astype(np.uint8)
@@ -302,16 +315,165 @@ def image_cases():
 _ref_cache = {}
 
 
-def reference_for(scene_name, qpos, cam, dtype=np.float64, **kw):
-    key = (scene_name, qpos.tobytes(), str(cam), np.dtype(dtype).name, tuple(sorted((k, str(v)) for k, v in kw.items())))
+def _key_part(v):
+    return v if v is None or isinstance(v, (str, int, bool)) else np.asarray(v).tobytes()
+
+
+def _camera_key(cam):
+    if isinstance(cam, (str, int, np.integer)):
+        return str(cam)
+    pos, rot, fovy = cam
+    return np.concatenate([np.ravel(pos), np.ravel(rot), [fovy]]).astype(np.float64).tobytes()
+
+
+def root_offsets(si, offsets):
+    """{hand root body: xyz} of per-root offsets [ntree][3] (RP_TREE_OFFSET's order: right hand first), as
+    oracle_geom_poses takes them."""
+    from robopianist_amd.model import render_tables
+    if offsets is None:
+        return None
+    roots = render_tables.hand_root_bodies(si.model, si.key_joint_ids)
+    return {int(b): np.asarray(offsets, float)[i] for i, b in enumerate(roots)}
+
+
+def _reference_entry(scene_name, qpos, cam, dtype, offsets, height, width, kw):
+    key = (scene_name, qpos.tobytes(), _camera_key(cam), np.dtype(dtype).name, _key_part(offsets), int(height), int(width),
+           tuple(sorted((k, _key_part(v)) for k, v in kw.items())))
     if key not in _ref_cache:
         si = build_scene_variant(scene_name)
-        pk = (scene_name, qpos.tobytes())
+        pk = (scene_name, qpos.tobytes(), _key_part(offsets))
         if pk not in _ref_cache:
-            _ref_cache[pk] = oracle_geom_poses(si, qpos)
+            _ref_cache[pk] = oracle_geom_poses(si, qpos, root_offsets(si, offsets))
         xpos, xmat = _ref_cache[pk]
-        _ref_cache[key] = reference_render(si, xpos, xmat, cam, dtype=dtype, **kw)
+        stats = {}
+        images = reference_render(si, xpos, xmat, cam, height=height, width=width, dtype=dtype, stats=stats, **kw)
+        _ref_cache[key] = (images, stats)
     return _ref_cache[key]
+
+
+def reference_for(scene_name, qpos, cam, dtype=np.float64, offsets=None, height=H, width=W, **kw):
+    """The reference's (rgb, depth, segmentation) of one image, computed once per process.  offsets: per-root tree
+    offsets [ntree][3] or None; kw: key_rgb, colorize_fingertips."""
+    return _reference_entry(scene_name, qpos, cam, dtype, offsets, height, width, kw)[0]
+
+
+def reference_stats_for(scene_name, qpos, cam, dtype=np.float64, offsets=None, height=H, width=W, **kw):
+    """The `stats` dict reference_render filled for the same image."""
+    return _reference_entry(scene_name, qpos, cam, dtype, offsets, height, width, kw)[1]
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# the wide cases: sizes on and next to a workgroup boundary, exact zeros, hand-placed cameras, tree offsets
+# ---------------------------------------------------------------------------------------------------------------
+def look_at(pos, target, up=(0.0, 0.0, 1.0), fovy=45.0):
+    """A (pos, rot, fovy) camera at `pos` that looks at `target`, its y axis as close to `up` as that allows."""
+    pos = np.asarray(pos, np.float64)
+    fwd = np.asarray(target, np.float64) - pos
+    fwd = fwd / np.linalg.norm(fwd)
+    x = np.cross(fwd, np.asarray(up, np.float64))
+    x = x / np.linalg.norm(x)
+    return (tuple(pos.tolist()), np.stack([x, np.cross(x, fwd), -fwd], axis=1), float(fovy))
+
+
+# straight down from above the keyboard; the matrix holds exact zeros and ones, so at an odd size the centre row and
+# the centre column of the image have a ray component that is exactly 0
+DOWN_CAMERA = ((0.1, 0, 1.0), [[0, 1, 0], [-1, 0, 0], [0, 0, 1]], 50.0)
+
+LOOK_AT_CAMERAS = {
+    "far_corner": look_at((2, 2, 1.5), (0, 0, 0), fovy=60),               # the floor's edge and background, depth to 4 m
+    "below": look_at((0.3, 0.1, -0.5), (0, 0, 0.2)),                      # the floor and the shapes from underneath
+    "away": look_at((0, 0, 1), (0, 0, 5), up=(0, 1, 0)),                  # nothing but background
+    # low over the keyboard, in the gap between the two middle keys and 77 mm in front of the piano's base: inside no
+    # shape, every hit an entry
+    "beside_base": look_at((0, 0, 0.02), (0.3, 0, 0.1)),
+    # INSIDE the piano's base box (x -0.177 .. -0.077, z 0 .. 0.04), looking forwards and 25 degrees up: every pixel is
+    # an exit hit of the base, through its front face below and its top face above.  No shape reaches into the base, so
+    # the base is all that a camera inside it can show; no ray leaves through the bottom face, which lies in the floor.
+    "inside_base": look_at((-0.127, 0.1, 0.01), (-0.127 + np.cos(np.radians(25)), 0.1, 0.01 + np.sin(np.radians(25))), fovy=40),
+    "narrow": look_at((-0.5, 0, 0.6), (0, 0, 0.05), fovy=3),
+    "wide": look_at((-0.3, 0, 0.4), (0.2, 0, 0.05), fovy=150),
+}
+ODD_H, ODD_W = 29, 43
+
+
+WIDE_OFFSETS = ((0.0, 0.02, -0.05), (0.03, -0.04, 0.02))                  # right hand root, left hand root
+MAGENTA = (255, 0, 255)
+
+# (id, scene, pose, offsets?, camera, H, W, key colours and fingertip colours?)
+_WIDE_SPEC = (
+    [(f"size-{cam}-{h}x{w}", "capsule", "random", False, cam, h, w, False)
+     for cam in ("back", "topdown") for h, w in ((16, 16), (32, 40), (3, 171), (1, 1))]
+    + [(f"down-{name}-{h}x{w}", name, "zero", False, "down", h, w, False) for name in SCENES for h, w in ((ODD_H, ODD_W), (15, 17))]
+    # (far_corner: scene "capsule" at ITS random pose has one grazing pixel of a finger capsule 3 m away whose depth the
+    #  reference rounds by 9.03e-05 at 29 x 43, over the figure on record; at scene "hull"'s pose, seed 12, it is 0.85e-05)
+    + [(f"{cam}-{name}", name, "seed12" if cam == "far_corner" else "random", False, cam, ODD_H, ODD_W, False)
+       for cam in LOOK_AT_CAMERAS for name in ("capsule", "hull")]
+    + [(f"offset-{name}-{cam}", name, "offset", True, cam, H, W, name == "capsule" and cam == "back")
+       for name in ("capsule", "hull") for cam in ("back", "topdown")])
+
+
+def wide_case_ids():
+    return [c[0] for c in _WIDE_SPEC]
+
+
+def base_key_rgb(n_envs=None):
+    """The keys' own colours as uint8 [88][3] (or [n_envs][88][3]): what key_rgb holds while no key is coloured."""
+    from robopianist_amd.model import piano
+    k = np.where(np.array([piano.is_key_black(i) for i in range(88)])[:, None], 26, 230).astype(np.uint8).repeat(3, 1)
+    return k if n_envs is None else np.ascontiguousarray(np.broadcast_to(k, (n_envs, 88, 3)))
+
+
+def most_visible_key(si, seg):
+    return int(np.argmax([(seg == g).sum() for g in si.key_geom_ids]))
+
+
+_wide_cache = []
+
+
+def wide_cases():
+    """[(scene, qpos, per-root offsets [2][3] or None, camera, H, W, key_rgb [88][3] or None, colorize_fingertips)],
+    in the order of wide_case_ids()."""
+    if not _wide_cache:
+        for _, name, pose, with_off, cam, h, w, coloured in _WIDE_SPEC:
+            si = build_scene_variant(name)
+            m = si.model
+            q = {"random": lambda: image_cases()[SCENES.index(name)][2], "zero": lambda: np.zeros(m.nv),
+                 "seed12": lambda: random_pose(m, 12),
+                 "offset": lambda: random_pose(m, 3)}[pose]()
+            off = np.asarray(WIDE_OFFSETS, np.float64) if with_off else None
+            camera = DOWN_CAMERA if cam == "down" else LOOK_AT_CAMERAS.get(cam, cam)
+            krgb = None
+            if coloured:
+                krgb = base_key_rgb()
+                krgb[most_visible_key(si, reference_for(name, q, camera, offsets=off, height=h, width=w)[2])] = MAGENTA
+            _wide_cache.append((name, q, off, camera, h, w, krgb, coloured))
+    return list(_wide_cache)
+
+
+MIXED_ENVS = 5
+
+
+def mixed_batch():
+    """(qpos [5][nv], offsets [5][2][3], key_rgb [5][88][3]) of scene "capsule": every env its own pose, tree offsets
+    and key colours (rendered from camera "back" with the fingertip colours on)."""
+    m = build_scene_variant("capsule").model
+    rng = np.random.default_rng(77)
+    q = np.stack([random_pose(m, 40 + e) for e in range(MIXED_ENVS)])
+    off = rng.uniform(-0.04, 0.04, (MIXED_ENVS, 2, 3))
+    off[0] = 0.0
+    return q, off, rng.integers(0, 256, (MIXED_ENVS, 88, 3)).astype(np.uint8)
+
+
+def rounded_to_float32(x):
+    """x as the fp32 engine holds it, back in float64: what the reference gets when it is compared with precision 32."""
+    return None if x is None else np.asarray(x, np.float64).astype(np.float32).astype(np.float64)
+
+
+def reference_rounding(r64, r32):
+    """(largest depth difference where the ids agree, fraction of the image whose ids differ) of two evaluations."""
+    same = (r64[2] == r32[2]) & np.isfinite(r64[1])
+    dd = float(np.abs(r64[1][same] - r32[1][same].astype(np.float64)).max()) if same.any() else 0.0
+    return dd, float((r64[2] != r32[2]).mean())
 
 
 def measure_reference_rounding(verbose=True):

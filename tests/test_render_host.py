@@ -412,7 +412,7 @@ def test_closed_forms_grazing_the_bounding_sphere():
 
 def test_launch_slices_cover_a_large_batch_once():
     """rp_render cuts a call of more than 65535 envs (the grid's y limit) into slices: every env in exactly one slice,
-    no slice larger than the limit.  (The GPU suite renders at most 5 envs: this arithmetic is checked here.)"""
+    no slice larger than the limit.  (tests/test_gpu_render.py renders 65540 envs in one call; the arithmetic is checked here.)"""
     L = rr.host_library()
     for n in (1, 5, 65535, 65536, 131070, 131071, 200000):
         buf = np.zeros((8, 2), np.int32)
@@ -420,3 +420,128 @@ def test_launch_slices_cover_a_large_batch_once():
         firsts, counts = buf[:k, 0], buf[:k, 1]
         assert k == -(-n // 65535) and (counts > 0).all() and counts.max() <= 65535
         assert firsts[0] == 0 and np.array_equal(firsts[1:], np.cumsum(counts)[:-1]) and counts.sum() == n
+
+
+# ---- the wide cases (tests/render_reference.py: wide_cases) --------------------------------------------------------
+def test_wide_cases_stay_inside_the_recorded_rounding():
+    """The reference in float32 against itself in float64 on every wide case and on the mixed batch: the depth rounding
+    stays under the figure the tolerance was derived from and the segmentation disagreement under a quarter of the cap,
+    so the cases are judged by the bounds on record.  Every case shows what it is there for."""
+    ids, cases = rr.wide_case_ids(), rr.wide_cases()
+    assert len(ids) == len(cases) == 32 and len(set(ids)) == 32
+    worst_d = worst_s = 0.0
+    for cid, (name, q, off, cam, h, w, krgb, tips) in zip(ids, cases):
+        kw = dict(offsets=off, height=h, width=w)
+        r64 = rr.reference_for(name, q, cam, np.float64, **kw); r32 = rr.reference_for(name, q, cam, np.float32, **kw)
+        dd, frac = rr.reference_rounding(r64, r32)
+        shown = len(np.unique(r64[2]))
+        print(f"reference f32 vs f64: {cid:28s} depth {dd:.4e} seg {100 * frac:.4f} % ids shown {shown}")
+        worst_d, worst_s = max(worst_d, dd), max(worst_s, frac)
+        assert dd <= rr.MEASURED_DEPTH_ROUNDING, f"{cid}: depth rounding {dd:.4e}: choose another size or pose"
+        assert frac < rr.SEG_CAP / 4, f"{cid}: the reference's own disagreement {frac:.4f}: choose another size or pose"
+        if cid.startswith("away"):
+            assert (r64[2] == -1).all() and np.isposinf(r64[1]).all()
+            assert (r64[0] == r64[0][0, 0]).all()
+        elif (h, w) not in ((1, 1), (3, 171)) and not cid.startswith("inside_base"):   # (inside a shape: that shape alone)
+            assert shown > 5, f"{cid}: the case shows too little to test anything"
+        if cid.startswith("down"):
+            # the centre row and the centre column: a ray component that is exactly 0, in float32 as the kernel casts them
+            _, d = rr.pixel_rays(cam, h, w, np.float32)
+            zero = (d == 0).any(1).reshape(h, w)
+            assert zero[h // 2].all() and zero[:, w // 2].all() and zero.sum() == h + w - 1
+            # the keys' and the base's frames are axis-aligned at the zero pose, so those rays keep their exact zero in the
+            # geom frame: the ones through the base take the box's parallel-slab branch and hit, the same rays miss the
+            # keys to either side of them through it
+            si = rr.build_scene_variant(name)
+            xmat = rr.oracle_geom_poses(si, q)[1]
+            assert all(np.isin(xmat[g], (0.0, 1.0, -1.0)).all() for g in si.key_geom_ids)
+            aligned = [g for g in np.unique(r64[2][zero]) if 0 <= g < si.model.ngeom and np.isin(xmat[g], (0.0, 1.0, -1.0)).all()]
+            print(f"  {cid}: {int(zero.sum())} rays with an exactly zero component, axis-aligned geoms under them: {aligned}")
+            assert len(aligned) >= 1, f"{cid}: no axis-aligned geom under the zero-component rays"
+        if cid.startswith("inside_base"):
+            # every pixel is resolved through the exit branch, and shows the base from inside: two of its faces
+            n_exit = rr.reference_stats_for(name, q, cam, np.float64, **kw)["exit_pixels"]
+            print(f"  {cid}: {n_exit} pixels resolved through the exit branch, {len(np.unique(r64[0][..., 0]))} shades")
+            assert n_exit == h * w and (r64[2] == 0).all()
+            assert rr.build_scene_variant(name).model.names["geom"][0] == "piano/base_geom"
+            assert r64[1].max() < 0.11 and len(np.unique(r64[0][..., 0])) >= 2
+        if cid.startswith("far_corner"):
+            m = rr.build_scene_variant(name).model
+            assert (r64[2] == m.ngeom).any() and (r64[2] == -1).any() and r64[1][np.isfinite(r64[1])].max() > 3.5
+        if cid.startswith("below"):
+            assert (r64[2] == rr.build_scene_variant(name).model.ngeom).any()
+        if krgb is not None:
+            si = rr.build_scene_variant(name)
+            key = int(np.flatnonzero((krgb == rr.MAGENTA).all(1))[0])
+            ref = rr.reference_for(name, q, cam, np.float64, key_rgb=krgb, colorize_fingertips=tips, **kw)
+            on_key = ref[2] == si.key_geom_ids[key]
+            assert on_key.sum() > 0 and (ref[0][on_key][:, 1] == 0).all() and (ref[0][on_key][:, 0] > 90).all()
+    q, off, krgb = rr.mixed_batch()
+    for e in range(rr.MIXED_ENVS):
+        kw = dict(offsets=off[e], key_rgb=krgb[e], colorize_fingertips=True)
+        dd, frac = rr.reference_rounding(rr.reference_for("capsule", q[e], "back", np.float64, **kw),
+                                         rr.reference_for("capsule", q[e], "back", np.float32, **kw))
+        print(f"reference f32 vs f64: mixed batch env {e}            depth {dd:.4e} seg {100 * frac:.4f} %")
+        worst_d, worst_s = max(worst_d, dd), max(worst_s, frac)
+        assert dd <= rr.MEASURED_DEPTH_ROUNDING and frac < rr.SEG_CAP / 4
+    print(f"wide cases: worst depth rounding {worst_d:.4e} (on record {rr.MEASURED_DEPTH_ROUNDING:.4e}), "
+          f"worst segmentation disagreement {100 * worst_s:.4f} % (cap / 4 = {100 * rr.SEG_CAP / 4:.2f} %)")
+
+
+@pytest.fixture(scope="module")
+def wide_host_renderers():
+    return {(name, tips): rr.HostRenderer(rr.build_scene_variant(name), 1, colorize_fingertips=tips)
+            for name, tips in {(c[0], c[7]) for c in rr.wide_cases()}}
+
+
+@pytest.mark.parametrize("case", range(len(rr.wide_case_ids())), ids=rr.wide_case_ids())
+def test_host_wide_cases_match_the_reference(wide_host_renderers, case):
+    """csrc/rp_render.hpp on the CPU over the wide cases: a bug in the shared per-ray code shows here without a GPU."""
+    name, q, off, cam, h, w, krgb, tips = rr.wide_cases()[case]
+    got = wide_host_renderers[(name, tips)].render(q, cam, h, w, tree_offset=None if off is None else off[None],
+                                                   key_rgb=None if krgb is None else krgb[None])
+    ref = rr.reference_for(name, q, cam, offsets=off, height=h, width=w,
+                           **(dict(key_rgb=krgb, colorize_fingertips=tips) if krgb is not None else {}))
+    rr.compare_images((got[0][0], got[1][0], got[2][0]), ref, label=f"host {rr.wide_case_ids()[case]}")
+
+
+def test_host_mixed_batch_matches_the_reference():
+    """Five envs, each with its own pose, tree offsets and key colours, against the reference of each."""
+    q, off, krgb = rr.mixed_batch()
+    hr = rr.HostRenderer(rr.build_scene_variant("capsule"), rr.MIXED_ENVS, colorize_fingertips=True)
+    out = hr.render(q, "back", tree_offset=off, key_rgb=krgb)
+    for e in range(rr.MIXED_ENVS):
+        ref = rr.reference_for("capsule", q[e], "back", offsets=off[e], key_rgb=krgb[e], colorize_fingertips=True)
+        rr.compare_images((out[0][e], out[1][e], out[2][e]), ref, label=f"host mixed batch env {e}")
+    assert not np.array_equal(out[2][0], out[2][1])
+
+
+def test_closed_forms_capsule_seam():
+    """Rays aimed AT the seam circle of a capsule, where its cylinder meets a half sphere: both parts describe that point,
+    and rounding must not leave the root to neither (RPR_CAP_EPS; without it one such ray in nine falls through to the
+    far side or misses).  2000 rays from 0.3 .. 1 m at a finger-sized capsule, incidence cosine >= 0.5, against the
+    reference's exact span of the same float32 ray.  Tolerance 1e-4 in the ray parameter (t is about 1): the float32
+    cancellation in b^2 - a c moves a root by about eps L / (r cos) = 1.2e-7 x 1 / (0.009 x 0.5) = 2.6e-5; 4 x that."""
+    r, hh = 0.009, 0.02
+    rng = np.random.default_rng(5)
+    n_rays = 2000
+    phi = rng.uniform(0, 2 * np.pi, n_rays)
+    radial = np.stack([np.cos(phi), np.sin(phi), np.zeros(n_rays)], 1)
+    seam = r * radial + np.array([0, 0, hh])[None, :] * rng.choice([-1.0, 1.0], n_rays)[:, None]
+    side = rng.normal(size=(n_rays, 3))
+    side -= radial * (side * radial).sum(1)[:, None]
+    side /= np.linalg.norm(side, axis=1)[:, None]
+    cosi = rng.uniform(0.5, 1.0, n_rays)
+    back = cosi[:, None] * radial + np.sqrt(1 - cosi ** 2)[:, None] * side          # from the seam point to the origin
+    o = (seam + back * rng.uniform(0.3, 1.0, n_rays)[:, None]).astype(np.float32)
+    d = (seam - o.astype(np.float64)).astype(np.float32)
+    t0, _, n0, _, hit = rr.shape_span(spec.GEOM_CAPSULE, np.array([r, hh, 0.0]), None, o.astype(np.float64), d.astype(np.float64), np.float64)
+    assert hit.sum() > 0.9 * n_rays
+    worst_t = worst_n = 0.0
+    for i in np.flatnonzero(hit):
+        t, n, rid = rr.trace_one(CAPSULE, (r, hh), o[i], d[i])
+        assert rid == 0, f"ray {i} at the seam misses the capsule"
+        worst_t = max(worst_t, abs(t - t0[i])); worst_n = max(worst_n, np.abs(n - n0[i]).max())
+    print(f"capsule seam: max |t - exact| {worst_t:.3e}, max normal difference {worst_n:.3e}")
+    assert worst_t <= 1e-4
+    assert worst_n <= 1e-4 / r * 2      # (a point moved by 1e-4 x 1 m along the ray turns the normal by that over r)
