@@ -2,8 +2,10 @@
 
 Same flags (argparse instead of absl; no viewer: the interactive viewer is out of scope; --record writes the first
 env's sound as a WAV file, --record --video its picture and sound as an AVI file: wrappers/sound.py), plus --n_envs /
---precision, --record_dir, --pixels (camera images in the observation: wrappers/pixels.py) and --hear (what every env hears in the
-observation: wrappers/hearing.py).  Replays an action sequence (or holds zeros) for one
+--precision, --record_dir, --pixels (camera images in the observation: wrappers/pixels.py), --hear (what every env hears in the
+observation: wrappers/hearing.py) and --plan (predictive sampling: suite/predictive_pianist.py; plays the episode twice, once
+with the nominal alone -- zeros, or FingeringPianist with --fingertip-pianist -- and once with the planner refining it, and
+prints both returns and F1s).  Replays an action sequence (or holds zeros) for one
 episode in every env and prints the musical metrics and the throughput, e.g. BASELINE config #2:
 
     python examples/piano_with_shadow_hands_env.py \\
@@ -23,8 +25,24 @@ import torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from robopianist_amd import suite  # noqa: E402
 from robopianist_amd.suite.fingertip_pianist import FingeringPianist  # noqa: E402
+from robopianist_amd.suite.predictive_pianist import PredictivePianist  # noqa: E402
 from robopianist_amd.wrappers import (AudioObservationWrapper, CanonicalSpecWrapper, FingertipActionWrapper,  # noqa: E402
                                       MidiEvaluationWrapper, PianoSoundVideoWrapper, PianoSoundWrapper, PixelWrapper)
+
+
+def _load(args, n_envs):
+    return suite.load(
+        environment_name=args.env_name, midi_file=args.midi_file, stretch=args.stretch, shift=args.shift,
+        seed=args.seed, n_envs=n_envs, precision=args.precision, record_key_trace=args.record or args.hear,
+        task_kwargs=dict(
+            change_color_on_activation=True, trim_silence=args.trim_silence,
+            control_timestep=args.control_timestep, gravity_compensation=args.gravity_compensation,
+            primitive_fingertip_collisions=args.primitive_fingertip_collisions,
+            reduced_action_space=args.reduced_action_space, n_steps_lookahead=args.n_steps_lookahead,
+            disable_fingering_reward=args.disable_fingering_reward,
+            disable_forearm_reward=args.disable_forearm_reward,
+            disable_colorization=args.disable_colorization,
+            disable_hand_collisions=args.disable_hand_collisions, attachment_yaw=args.attachment_yaw))
 
 
 def main() -> None:
@@ -57,6 +75,16 @@ def main() -> None:
     ap.add_argument("--press_depth", type=float, default=0.01,
                     help="with --fingertip-pianist: metres below a key's surface target the assigned finger aims at")
     ap.add_argument("--ik_iterations", type=int, default=1, help="with --fingertip-pianist: IK steps per control step")
+    ap.add_argument("--plan", action="store_true",
+                    help="predictive sampling (PredictivePianist): every control step, --plan_candidates action splines per env "
+                         "are rolled out --plan_horizon steps in a second environment of n_envs x candidates envs and the best "
+                         "one's first action is taken; with --fingertip-pianist the plan is seeded from FingeringPianist")
+    ap.add_argument("--plan_candidates", type=int, default=16)
+    ap.add_argument("--plan_horizon", type=int, default=5)
+    ap.add_argument("--plan_knots", type=int, default=2)
+    ap.add_argument("--plan_spline", default="linear", choices=("linear", "zero"))
+    ap.add_argument("--plan_sigma", type=float, default=None,
+                    help="noise around the nominal, in the action's units (default: 0.005 m with --fingertip-pianist, else 0.1)")
     ap.add_argument("--record", action="store_true",
                     help="record env 0 with PianoSoundWrapper and write its episode as a WAV file")
     ap.add_argument("--video", action="store_true",
@@ -68,20 +96,16 @@ def main() -> None:
     if args.fingertip_pianist and (args.canonicalize or args.action_sequence):
         ap.error("--fingertip-pianist commands fingertips: it takes neither --canonicalize nor --action_sequence")
 
-    with warnings.catch_warnings():
-        warnings.simplefilter("ignore")
-        env = suite.load(
-            environment_name=args.env_name, midi_file=args.midi_file, stretch=args.stretch, shift=args.shift,
-            seed=args.seed, n_envs=args.n_envs, precision=args.precision, record_key_trace=args.record or args.hear,
-            task_kwargs=dict(
-                change_color_on_activation=True, trim_silence=args.trim_silence,
-                control_timestep=args.control_timestep, gravity_compensation=args.gravity_compensation,
-                primitive_fingertip_collisions=args.primitive_fingertip_collisions,
-                reduced_action_space=args.reduced_action_space, n_steps_lookahead=args.n_steps_lookahead,
-                disable_fingering_reward=args.disable_fingering_reward,
-                disable_forearm_reward=args.disable_forearm_reward,
-                disable_colorization=args.disable_colorization,
-                disable_hand_collisions=args.disable_hand_collisions, attachment_yaw=args.attachment_yaw))
+    if args.plan and (args.canonicalize or args.action_sequence or args.pixels or args.hear or args.record):
+        ap.error("--plan goes with --fingertip-pianist or alone: not with --canonicalize, --action_sequence, --pixels, --hear "
+                 "or --record")
+
+    def load(n_envs):
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            return _load(args, n_envs)
+
+    env = load(args.n_envs)
     pianist = fingertips = None
     if args.fingertip_pianist:
         env = fingertips = FingertipActionWrapper(env, mode="absolute", iterations=args.ik_iterations)
@@ -89,6 +113,17 @@ def main() -> None:
     if args.canonicalize:
         env = CanonicalSpecWrapper(env)
     env = MidiEvaluationWrapper(env)
+    planner = None
+    if args.plan:
+        def make_plan_env(n_envs):
+            e = load(n_envs)
+            return FingertipActionWrapper(e, mode="absolute", iterations=args.ik_iterations) if args.fingertip_pianist else e
+        sigma = args.plan_sigma if args.plan_sigma is not None else (0.005 if args.fingertip_pianist else 0.1)
+        planner = PredictivePianist(env, make_plan_env, n_candidates=args.plan_candidates, horizon=args.plan_horizon,
+                                    n_knots=args.plan_knots, spline=args.plan_spline, sigma=sigma, seed=args.seed,
+                                    seed_from=pianist)
+        print(f"Planner: {args.plan_candidates} candidates x {args.plan_horizon} steps, {args.plan_knots} knots "
+              f"({args.plan_spline}), sigma {sigma}; planning env: {planner.sampler.E} envs")
     if args.pixels:
         env = PixelWrapper(env, render_kwargs=dict(height=84, width=84, camera_id="piano/back"))
         spec = env.observation_spec()["pixels"]
@@ -118,33 +153,48 @@ def main() -> None:
     print(f"Control frequency: {1 / args.control_timestep} Hz")
 
     actions = np.load(args.action_sequence) if args.action_sequence else None
-    n_steps, ret = 0, torch.zeros(E, device=dev, dtype=env.physics.dtype)
-    t0 = time.perf_counter()
-    while True:
-        if pianist is not None:
-            a, weights = pianist.action()
-            fingertips.set_weights(weights, validate=False)
-            timestep = env.step(a)
-        else:
-            a = actions[n_steps] if actions is not None and n_steps < len(actions) else zeros
-            timestep = env.step(torch.as_tensor(a, device=dev, dtype=env.physics.dtype).expand(E, -1))
-        ret += timestep.reward
-        n_steps += 1
-        if args.hear:   # (a demonstration: the read-back is this print's, not the wrapper's)
-            audio = timestep.observation["audio"]
-            loud = int(audio[0].argmax())
-            print(f"step {n_steps}: audio {tuple(audio.shape)}, env 0 loudest bin: key {loud} at {float(audio[0, loud]):.4f}")
-        if bool(timestep.last().all()):   # all envs play the same song: they finish together
-            break
-    torch.cuda.synchronize()
-    dt = time.perf_counter() - t0
-    print(f"episode: {n_steps} control steps x {E} envs in {dt:.2f} s = {E * n_steps / dt:,.0f} env-steps/s")
-    print(f"mean return {float(ret.mean()):.3f}")
-    metrics = env.get_musical_metrics()
-    for k, v in metrics.items():
-        print(f"\t{k}: {v:.4f}")
+
+    def episode(use_planner):
+        nonlocal timestep
+        n_steps, ret = 0, torch.zeros(E, device=dev, dtype=env.physics.dtype)
+        t0 = time.perf_counter()
+        while True:
+            if use_planner:
+                timestep = planner.step()
+            elif pianist is not None:
+                a, weights = pianist.action()
+                fingertips.set_weights(weights, validate=False)
+                timestep = env.step(a)
+            else:
+                a = actions[n_steps] if actions is not None and n_steps < len(actions) else zeros
+                timestep = env.step(torch.as_tensor(a, device=dev, dtype=env.physics.dtype).expand(E, -1))
+            ret += timestep.reward
+            n_steps += 1
+            if args.hear:   # (a demonstration: the read-back is this print's, not the wrapper's)
+                audio = timestep.observation["audio"]
+                loud = int(audio[0].argmax())
+                print(f"step {n_steps}: audio {tuple(audio.shape)}, env 0 loudest bin: key {loud} at {float(audio[0, loud]):.4f}")
+            if bool(timestep.last().all()):   # all envs play the same song: they finish together
+                break
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        print(f"episode: {n_steps} control steps x {E} envs in {dt:.2f} s = {E * n_steps / dt:,.0f} env-steps/s")
+        print(f"mean return {float(ret.mean()):.3f}")
+        metrics = env.get_musical_metrics()
+        for k, v in metrics.items():
+            print(f"\t{k}: {v:.4f}")
+        return float(ret.mean()), metrics
+
+    nominal_return, metrics = episode(False)
     if pianist is not None:
         print(f"fingertip pianist: F1 {metrics['f1']:.4f} (press depth {args.press_depth} m, {args.ik_iterations} IK step(s) per control step)")
+    if planner is not None:
+        nominal_f1 = metrics["f1"]
+        timestep = env.reset()
+        plan_return, metrics = episode(True)
+        print(f"predictive sampling: return {plan_return:.3f}, F1 {metrics['f1']:.4f}; the nominal alone "
+              f"({'FingeringPianist' if pianist is not None else 'zeros'}): return {nominal_return:.3f}, F1 {nominal_f1:.4f}")
+        print(f"planning env warn flags: {int(planner.sampler.plan_env.physics.warn.max())}")
     print(f"warn flags: {int(env.physics.warn.max())}")
     if args.record:
         print("recorded: " + (", ".join(str(p) for p in env.written) or "nothing (the episode has no note)"))

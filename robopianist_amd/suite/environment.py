@@ -207,6 +207,20 @@ class Environment:
                 "needs_reset": self._needs_reset.detach().clone(),
                 "random_state": self._random_state.get_state()}
 
+    def state_views(self):
+        """The live per-env tensors behind `state_dict`, flat: `{"physics.qpos": ..., "task.piano._state": ...,
+        "needs_reset": ...}`, each with leading dimension n_envs; everything `state_dict` clones except the host
+        RandomState.  Raises ValueError for tasks whose episode state is not plain per-env tensors."""
+        v = {"physics." + k: t for k, t in self._physics.state_views().items()}
+        v.update({"task." + k: t for k, t in self._task.state_views().items()})
+        v["needs_reset"] = self._needs_reset
+        return v
+
+    @property
+    def needs_reset(self):
+        """bool [n_envs]: the envs whose next step() starts a new episode (live, device)."""
+        return self._needs_reset
+
     def load_state_dict(self, sd):
         self._task.load_state_dict(sd["task"])
         self._physics.load_state_dict(sd["physics"])

@@ -191,6 +191,12 @@ class TorchPhysics:
         recomputed by `load_state_dict` with physics.forward()."""
         return {k: v.detach().clone() for k, v in self._state_views().items()}
 
+    def state_views(self):
+        """The LIVE tensors `state_dict` would clone, `{name: tensor [n_envs, ...]}`: zero-copy views of engine memory.
+        Writing them is writing the engine's state; as after `load_state_dict`, follow it with `active <- 1` and
+        forward().  (The planner's fork reads the real env's views and writes the planning env's: planning.py.)"""
+        return dict(self._state_views())
+
     def load_state_dict(self, sd):
         views = self._state_views()
         for k, v in views.items():

@@ -91,6 +91,10 @@ class Piano:
     def state_dict(self):
         return {k: getattr(self, k).detach().clone() for k in self._STATE}
 
+    def state_views(self):
+        """The live tensors `state_dict` would clone (they are allocated once and updated in place)."""
+        return {k: getattr(self, k) for k in self._STATE}
+
     def load_state_dict(self, sd):
         for k in self._STATE:
             getattr(self, k).copy_(sd[k].to(getattr(self, k).device))

@@ -441,6 +441,21 @@ class PianoWithShadowHands(base.PianoTask):
             sd["_tree_offset"] = self._tree_offset.detach().clone()
         return sd
 
+    def state_views(self):
+        """The live per-env tensors `state_dict` would clone, flat: `{"_t_idx": ..., "piano._state": ...}`, each
+        [n_envs, ...].  Refused where the episode state is more than that: MIDI augmentations (a per-env goal bank that is
+        reallocated, host-side draws; prefetch adds host parity bits) and `randomize_hand_positions` (a tensor that is
+        replaced, not updated)."""
+        if self.needs_host_episode_setup or self._prefetch:
+            raise ValueError("state_views: MIDI augmentations (and their prefetch) keep episode state on the host and in a "
+                             "goal bank that is reallocated; use state_dict()")
+        if self._randomize_hand_positions:
+            raise ValueError("state_views: randomize_hand_positions replaces its offsets tensor at every episode start; "
+                             "use state_dict()")
+        v = {k: getattr(self, k) for k in self._STATE}
+        v.update({"piano." + k: t for k, t in self.piano.state_views().items()})
+        return v
+
     def load_state_dict(self, sd):
         dev = self._physics_device
         for k in self._STATE:

@@ -101,6 +101,17 @@ class SelfActuatedPiano(base.PianoOnlyTask):
         sd["piano"] = self.piano.state_dict()
         return sd
 
+    def state_views(self):
+        """The live per-env tensors `state_dict` would clone, flat, each [n_envs, ...].  Without augmentations the goal
+        bank and its length are one shared, constant slot (not per-env state): they are left out.  With augmentations
+        the bank is per env, grows and is drawn on the host: refused."""
+        if self.needs_host_episode_setup:
+            raise ValueError("state_views: MIDI augmentations keep episode state on the host and in a goal bank that is "
+                             "reallocated; use state_dict()")
+        v = {k: getattr(self, k) for k in self._STATE if k not in ("_goal_bank", "_len")}
+        v.update({"piano." + k: t for k, t in self.piano.state_views().items()})
+        return v
+
     def load_state_dict(self, sd):
         for k in self._STATE:
             cur, new = getattr(self, k), sd[k].to(self._physics_device)
