@@ -3,6 +3,7 @@
 // tables), uploads the fixed-topology tables, owns the env-major state arrays and
 // launches the stage kernels rp_stage_kernel<T, MODE> (rp_kernels.hpp) on the engine's HIP stream.
 #include "rp_kernels.hpp"
+#include "rp_schedule.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -110,6 +111,92 @@ int fail(const std::string& s) { g_err = s; return -1; }
     if (e_ != hipSuccess)                                                          \
       return fail(std::string(#x) + ": " + hipGetErrorString(e_));                 \
   } while (0)
+
+#define RP_TRY(x)                                                                  \
+  do {                                                                             \
+    if (int r_ = (x)) return r_;                                                   \
+  } while (0)
+
+// true when `p` is device memory (a host pointer the runtime has never seen leaves an error behind: cleared)
+bool is_device_ptr(const void* p) {
+  hipPointerAttribute_t attr;
+  const bool on_device = hipPointerGetAttributes(&attr, p) == hipSuccess && attr.type == hipMemoryTypeDevice;
+  (void)hipGetLastError();
+  return on_device;
+}
+
+// Which builds of the stage kernels an engine launches: fixed by the model (Engine<T>::build).  Every launch_* helper
+// below dispatches over exactly the instantiations its kernel has -- a new build is added in ONE of them.
+struct StageVariant {
+  int hull = 0;         // the MESH template argument: 0 = primitives only, 1 = convex hulls (MPR), 2 = hulls with a vertex graph / cylinders
+  bool deep = false;    // the RPK_MAXD_DEEP builds
+  bool trunk4 = false;  // the solver builds specialised for "every tree has a 4-link trunk"
+};
+
+// rp_stage_kernel<T, MODE>: MODE 0 = position / velocity stage and MODE 2 = sensor stage (tree depth x hull support),
+// MODE 1 = solver stage (deep, 4-link trunk or general)
+template <typename T, int MODE>
+inline void launch_stage(const StageVariant& v, int grid, hipStream_t st, const RpModel<T>& M, const RpState<T>& s, const RpStage<T>& B, int k, int nsub) {
+#define RP_STAGE(...) hipLaunchKernelGGL((rp_stage_kernel<T, MODE, __VA_ARGS__>), dim3(grid), dim3(64), 0, st, M, s, B, k, nsub)
+  if constexpr (MODE == 1) {
+    if (v.deep) RP_STAGE(0, RPK_MAXD_DEEP);
+    else if (v.trunk4) RP_STAGE(4);
+    else RP_STAGE(0);
+  } else {
+    switch ((v.deep ? 3 : 0) + v.hull) {
+      case 5: RP_STAGE(0, RPK_MAXD_DEEP, 2); break;
+      case 4: RP_STAGE(0, RPK_MAXD_DEEP, 1); break;
+      case 3: RP_STAGE(0, RPK_MAXD_DEEP); break;
+      case 2: RP_STAGE(0, RPK_MAXD, 2); break;
+      case 1: RP_STAGE(0, RPK_MAXD, 1); break;
+      default: RP_STAGE(0); break;
+    }
+  }
+#undef RP_STAGE
+}
+// the position / velocity stage as front part, pooled narrow phase (`ng` workgroups), back part: the fp64 default-depth builds
+template <typename T, int MESH>
+inline void launch_pos_split_as(int grid, int ng, hipStream_t st, const RpModel<T>& M, const RpState<T>& s, const RpStage<T>& Bs, int k, int nsub) {
+  hipLaunchKernelGGL((rp_pos_front_kernel<T, MESH>), dim3(grid), dim3(64), 0, st, M, s, Bs, k, nsub);
+  hipLaunchKernelGGL((rp_narrow_kernel<T, MESH>), dim3(ng), dim3(64), 0, st, M, s, Bs);
+  hipLaunchKernelGGL((rp_pos_back_kernel<T, MESH>), dim3(grid), dim3(64), 0, st, M, s, Bs, k, nsub);
+}
+template <typename T>
+inline void launch_pos_split(const StageVariant& v, int grid, int ng, hipStream_t st, const RpModel<T>& M, const RpState<T>& s, const RpStage<T>& Bs, int k, int nsub) {
+  if constexpr (sizeof(T) == 8) {
+    if (v.hull == 2) launch_pos_split_as<T, 2>(grid, ng, st, M, s, Bs, k, nsub);
+    else if (v.hull == 1) launch_pos_split_as<T, 1>(grid, ng, st, M, s, Bs, k, nsub);
+    else launch_pos_split_as<T, 0>(grid, ng, st, M, s, Bs, k, nsub);
+  }
+}
+// the position / velocity stage of the envs on the list (of those outside the light class), in list order
+template <typename T>
+inline void launch_pos_listed(const StageVariant& v, int grid, hipStream_t st, const RpModel<T>& M, const RpState<T>& s, const RpStage<T>& B, int k, int nsub) {
+  if constexpr (sizeof(T) == 8) {   // (the light class exists in the fp64 default builds only)
+    if (v.hull) hipLaunchKernelGGL((rp_pos_list_kernel<T, 1>), dim3(grid), dim3(64), 0, st, M, s, B, k, nsub);
+    else hipLaunchKernelGGL((rp_pos_list_kernel<T, 0>), dim3(grid), dim3(64), 0, st, M, s, B, k, nsub);
+  }
+}
+// fused substeps: the light envs' launch (SPLIT: with the split stage's bodies, else the one-kernel body), then the clean-up
+// launch over the list (fp64, default depth, no graph hulls)
+template <typename T, int MESH, bool SPLIT>
+inline void launch_fused_as(bool trunk4, int grid, int cgrid, hipStream_t st, const RpModel<T>& M, const RpState<T>& sf, const RpStage<T>& Bfused,
+                            const RpStage<T>& B, int nsub) {
+  if constexpr (SPLIT) hipLaunchKernelGGL((rp_fused_split_kernel<T, MESH>), dim3(grid), dim3(64), 0, st, M, sf, Bfused, nsub);
+  else hipLaunchKernelGGL((rp_fused_steps_kernel<T, MESH>), dim3(grid), dim3(64), 0, st, M, sf, Bfused, nsub);
+  if (trunk4) hipLaunchKernelGGL((rp_cleanup_steps_kernel<T, MESH, 4>), dim3(cgrid), dim3(64), 0, st, M, sf, B, nsub);
+  else hipLaunchKernelGGL((rp_cleanup_steps_kernel<T, MESH, 0>), dim3(cgrid), dim3(64), 0, st, M, sf, B, nsub);
+}
+template <typename T>
+inline void launch_fused(const StageVariant& v, bool fsplit, int grid, int cgrid, hipStream_t st, const RpModel<T>& M, const RpState<T>& sf,
+                         const RpStage<T>& Bfused, const RpStage<T>& B, int nsub) {
+  if constexpr (sizeof(T) == 8) {
+    if (fsplit && v.hull) launch_fused_as<T, 1, true>(v.trunk4, grid, cgrid, st, M, sf, Bfused, B, nsub);
+    else if (fsplit) launch_fused_as<T, 0, true>(v.trunk4, grid, cgrid, st, M, sf, Bfused, B, nsub);
+    else if (v.hull) launch_fused_as<T, 1, false>(v.trunk4, grid, cgrid, st, M, sf, Bfused, B, nsub);
+    else launch_fused_as<T, 0, false>(v.trunk4, grid, cgrid, st, M, sf, Bfused, B, nsub);
+  }
+}
 
 struct BlobEntry { char name[40]; int32_t dtype, ndim; int64_t count, offset; };
 
@@ -235,7 +322,7 @@ struct EngineBase {
   bool legacy_step = true;   // rp_set_legacy_step: false = dm_control's legacy_step=False output semantics
   bool cost_order = false;   // rp_set_cost_ordered_launch
   int n_slices = 1;          // rp_set_stream_slices (0 = automatic)
-  static const int kMaxSlices = 4;
+  static const int kMaxSlices = kRpMaxSlices;
   hipStream_t xstream[kMaxSlices] = {};   // [0] unused: slice 0 runs on the caller's stream
   hipEvent_t ev_fork = nullptr, ev_join[kMaxSlices] = {};
   // capacity classes: the full-capacity solver stage (few envs, one wave per SIMD, long waves) runs beside the
@@ -268,6 +355,7 @@ struct Engine : EngineBase {
   bool mesh = false;    // the model has convex-hull geoms: position / sensor stages with MPR
   bool graph = false;   // ... some of them with a vertex graph (more than 32 vertices): the MESH = 2 builds
   bool deep = false;    // a trunk of 5..8 links (more than two forearm dofs): the RPK_MAXD_DEEP builds
+  StageVariant variant; // ... the four as the launch helpers read them
   int dense_joint = 0;  // RPK_LEAN_JOINT when RP_DENSE_HANDS=0 (goes to the kernels in S.lean)
   bool lean = false;    // light envs are stepped by rp_lean_solver_kernel (rp_solver2.hpp), the others by the full build
   // the position stage of the substeps as three launches: front part, pooled narrow phase (rp_collide.hpp), back part
@@ -282,10 +370,8 @@ struct Engine : EngineBase {
     split_mode = on < 0 ? 2 : (on > 2 ? 2 : on);
     return 0;
   }
-  // (0 = off, 1 = in use, 2 = the rule may pick it: batches of >= 3072 envs that have never overflowed its lists)
-  int split_position_on() const override {
-    return split_mode == 1 ? 1 : (split_mode == 2 && n_slices == 0 && nenv >= 3072 && !split_dropped ? (auto_mode == 4 ? 1 : 2) : 0);
-  }
+  // (0 = off, 1 = in use, 2 = the rule may pick it: rp_split_report)
+  int split_position_on() const override { return rp_split_report(plan_input(0, false), auto_mode); }
   int lean_solver(int on) override {
     if (on && (deep || sizeof(T) != 8)) return fail("rp_set_lean_solver: the lean solver stage exists for the fp64 default builds only");
     lean = on != 0; S.lean = on > 0 ? ((on & RPK_LEAN_CAP) | dense_joint) : 0;   // (on > 1: the light class capped at that many Jacobian entries)
@@ -337,6 +423,17 @@ struct Engine : EngineBase {
 
   void build(const Blob& b, int n_envs) {
     nenv = n_envs;
+    read_options(b);
+    upload_tables(b);
+    alloc_state();
+    read_switches();
+    // The fills and uploads above went through the null stream, which is NOT ordered with the
+    // engine's non-blocking stream: everything must have landed before the first kernel.
+    if (hipDeviceSynchronize() != hipSuccess) throw std::string("hipDeviceSynchronize failed after model upload");
+    variant.hull = mesh ? (graph ? 2 : 1) : 0; variant.deep = deep; variant.trunk4 = trunk4;
+  }
+  // sizes, limits and solver options
+  void read_options(const Blob& b) {
     M.nlink = nlink = b.i1("eng_nlink"); M.ntree = ntree = b.i1("eng_ntree");
     M.maxdepth = maxdepth = b.i1("eng_maxdepth"); M.nkey = nkey = b.i1("eng_nkey");
     M.ngeom = b.i1("eng_ngeom");
@@ -368,7 +465,9 @@ struct Engine : EngineBase {
       M.mu_scale = (T)std::sqrt(1.0 / (ir > 1e-15 ? ir : 1e-15));
     }
     M.mpr_tol = (T)1e-6; M.mpr_tol_poly = (T)1e-6;   // MuJoCo's uniform rule (rp_set_mpr_tolerance)
-    // ---- pack every model table into the two device arrays (RpLayout offsets)
+  }
+  // every model table packed into the two device arrays (RpLayout offsets); the kernel builds the model needs
+  void upload_tables(const Blob& b) {
     std::vector<double> ft((size_t)RpLayout::F_TOTAL, 0.0);
     std::vector<int> it((size_t)RpLayout::I_TOTAL, 0);
     auto putF = [&](int off, int cap, const std::vector<double>& v, const char* name) {
@@ -477,6 +576,9 @@ struct Engine : EngineBase {
       qpos0.assign(q0.begin(), q0.end());
       d_qpos0 = const_cast<T*>(upF(q0));
     }
+  }
+  // the env-major state, hand-over and bookkeeping arrays
+  void alloc_state() {
     size_t E = (size_t)nenv;
     S.nenv = nenv;
     S.qpos = dalloc<T>(E * nv); S.qvel = dalloc<T>(E * nv); S.warm = dalloc<T>(E * nv);
@@ -498,14 +600,6 @@ struct Engine : EngineBase {
     B.keyslot = dalloc<int>(E * (RPK_NKEYS / 4));
     B.covf = dalloc<T>(E * (RPK_NC - RPK_NCL) * 12);
     B.covi = dalloc<int>(E * (RPK_NC - RPK_NCL) * 4);
-    // split position stage (front part -> pooled narrow phase -> back part): the fp64 default-depth builds
-    {
-      const char* sp = getenv("RP_SPLIT_POS");
-      split_capable = sizeof(T) == 8 && !deep;
-      split_mode = !split_capable ? 0 : (sp ? (sp[0] == '0' ? 0 : (sp[0] == '1' ? 1 : 2)) : 2);
-      // (the buffers -- 78 KB per env: 320 MB at 4096 envs -- are allocated by the first rp_step that runs the split stage:
-      // ensure_split_buffers; an engine that never does, small batches and RP_SPLIT_POS=0 among them, never pays for them)
-    }
     // hand-over buffers start as NaN / -1 patterns: a read of anything the position kernel
     // did not write this substep shows up as a bad state instead of silently reusing old data
     hipMemset(B.RM, 0xFF, sizeof(T) * E * RPK_NLX(md()) * (md() + 1));
@@ -538,6 +632,17 @@ struct Engine : EngineBase {
     S.qpos_prev = nullptr; S.qvel_prev = nullptr;
     d_valid = dalloc<unsigned char>(E);  // (zero-filled: nothing is valid yet)
     S.max_newton = M.iterations; S.max_ls = M.ls_iterations;
+  }
+  // RP_SPLIT_POS, RP_LEAN, RP_DENSE_HANDS (RP_FORCE_DEEP: upload_tables; RP_FUSED, RP_FUSED_SPLIT, RP_HEAVY_GRID: their members)
+  void read_switches() {
+    // split position stage (front part -> pooled narrow phase -> back part): the fp64 default-depth builds
+    {
+      const char* sp = getenv("RP_SPLIT_POS");
+      split_capable = sizeof(T) == 8 && !deep;
+      split_mode = !split_capable ? 0 : (sp ? (sp[0] == '0' ? 0 : (sp[0] == '1' ? 1 : 2)) : 2);
+      // (the buffers -- 78 KB per env: 320 MB at 4096 envs -- are allocated by the first rp_step that runs the split stage:
+      // ensure_split_buffers; an engine that never does, small batches and RP_SPLIT_POS=0 among them, never pays for them)
+    }
     {
       const char* le = getenv("RP_LEAN");
       lean = sizeof(T) == 8 && !deep && !(le && le[0] == '0');
@@ -548,9 +653,6 @@ struct Engine : EngineBase {
       S.lean = lean ? (1 | dense_joint) : 0;
       if (lean && le && atoi(le) > 1) S.lean = (atoi(le) & RPK_LEAN_CAP) | dense_joint;   // (RP_LEAN=n > 1: the light class capped at n Jacobian entries, as rp_set_lean_solver(e, n))
     }
-    // The fills and uploads above went through the null stream, which is NOT ordered with the
-    // engine's non-blocking stream: everything must have landed before the first kernel.
-    if (hipDeviceSynchronize() != hipSuccess) throw std::string("hipDeviceSynchronize failed after model upload");
   }
 
   // The split position stage's buffers, on first use.  False (and the split stage off for good) when the device has no
@@ -600,26 +702,27 @@ struct Engine : EngineBase {
   int *d_heavy_peak = nullptr, *h_heavy_peak = nullptr;
   double heavy_est[kMaxSlices] = {8, 8, 8, 8};
   int heavy_grid_for(int sl, int cnt) {
-    int g = kHeavyGrid;
-    if (!heavy_grid_fixed && h_heavy_peak) {
-      const int seen = *(volatile int*)&h_heavy_peak[sl];
-      if (seen >= 0) { heavy_est[sl] = seen > heavy_est[sl] ? seen : 0.9 * heavy_est[sl] + 0.1 * seen; *(volatile int*)&h_heavy_peak[sl] = -1; }
-      // (config 3, 4096 envs: fixed grids of 24 / 48 / 128: 409 / 436 / 445 k env-steps/s.  Round 6: the floor is 2
-      // workgroups, not 8 -- each needs a whole idle SIMD, and on the replay, whose lists are empty most of the time, a
-      // grid of one measured +0.7 %: 636.6 against 632.2 k, two runs each inside one call)
-      g = (int)(2.0 * heavy_est[sl]) + 2;
-      g = g < 2 ? 2 : (g > kHeavyGrid ? kHeavyGrid : g);
-    }
-    return cnt < g ? cnt : g;
+    if (heavy_grid_fixed || !h_heavy_peak) return cnt < kHeavyGrid ? cnt : kHeavyGrid;
+    const int seen = *(volatile int*)&h_heavy_peak[sl];
+    if (seen >= 0) { heavy_est[sl] = rp_heavy_est_update(heavy_est[sl], seen); *(volatile int*)&h_heavy_peak[sl] = -1; }
+    return rp_heavy_grid(heavy_est[sl], cnt, kHeavyGrid);
   }
   // fused substeps (rp_fused_steps_kernel): one launch takes every light env through all substeps of an rp_step
   // 0 = off, 1 = on, 2 = automatic (a candidate of the schedule choice when the slice count is automatic too)
   int fused = getenv("RP_FUSED") ? atoi(getenv("RP_FUSED")) : 2;
   const bool fused_split = !(getenv("RP_FUSED_SPLIT") && getenv("RP_FUSED_SPLIT")[0] == '0');
   int fused_substeps(int on) override { fused = on < 0 ? 2 : (on > 2 ? 2 : on); return 0; }
-  int fused_substeps_on() const override {
-    const bool capable = lean && !deep && !graph && sizeof(T) == 8;
-    return !capable ? 0 : (fused == 1 ? 1 : (fused == 2 && n_slices == 0 ? (auto_mode == 3 ? 1 : 2) : 0));
+  int fused_substeps_on() const override { return rp_fused_report(plan_input(0, false), auto_mode); }
+  // what the schedule rule (rp_schedule.hpp) reads, as the engine stands
+  RpStepInput plan_input(int mode, bool capturing) const {
+    RpStepInput in;
+    in.nenv = nenv; in.mode = mode; in.n_slices = n_slices;
+    in.fused = fused; in.fused_capable = rp_fused_capable(lean, deep, graph, sizeof(T) == 8);
+    in.split_mode = split_mode; in.split_capable = split_capable; in.split_dropped = split_dropped;
+    in.capturing = capturing; in.lean = lean; in.deep = deep; in.graph = graph;
+    for (int i = 0; i < kMaxSlices; i++) in.heavy_est[i] = heavy_est[i];
+    in.last_nsl = last_nsl; in.many_heavy = many_heavy;
+    return in;
   }
   // MEASUREMENT-ONLY switches (they skip or repeat work: wrong physics / wasted time).  Compiled in only with
   // -DRP_EXPERIMENTS, and loud when set: a stray environment variable must not silently change a production step.
@@ -638,15 +741,6 @@ struct Engine : EngineBase {
   // (Measured and not kept, rounds 4-5: the lean launch in FRONT of the full-capacity one where there is no companion stream
   // (660 against 668 k env-steps/s); a high-priority companion stream (no effect on the dispatch order); the full-capacity
   // launch on the slice's own stream with two slices (-2.5 %).)
-  // Threads per residue class of rp_order_kernel: two envs per thread.  (A 512-thread workgroup needs a whole
-  // idle CU -- with both stage kernels at two waves per SIMD it waited ~60 us for one on every substep of a
-  // 2048-env slice -- while a single wave takes too long over 512 envs.  Measured: 2048-env slices 64 / 128 /
-  // 256 threads: 681 / 678 / 647 k env-steps/s; 4096-env slices 64 / 128 / 256 / 512: 540 / 547 / 561 / 562 k.)
-  int order_threads_for(int cnt) const {
-    // (the kernel's scan needs a full first wave and its launch bound is 512: multiples of 64 in 64 .. 512)
-    const int t = ((cnt / 16 + 63) / 64) * 64;
-    return t < 64 ? 64 : (t > 512 ? 512 : t);
-  }
   // (each of these workgroups needs a whole idle SIMD, also just to find the list empty: 512 of them delayed the slice's join;
   // measured 64 ... 128 best on configs 2-4, 16 starves config 3)
   const int kHeavyGrid = getenv("RP_HEAVY_GRID") ? (atoi(getenv("RP_HEAVY_GRID")) > 0 ? atoi(getenv("RP_HEAVY_GRID")) : 1) : 128;   // (one wave of that stage owns a SIMD: half the chip at most)
@@ -702,15 +796,38 @@ struct Engine : EngineBase {
     if (ls > 0) S.max_ls = ls;
   }
 
+  // One builder each for the states the launches below get instead of S:
+  // ... rp_reset_kernel: with the sensor outputs to clear
+  RpState<T> reset_state() const {
+    RpState<T> sr = S;
+    sr.sens_torque = sensors_on ? d_sens_torque : nullptr; sr.sens_touch = sensors_on ? d_sens_touch : nullptr;
+    return sr;
+  }
+  // ... the stages that walk or fill slice sl's list of envs outside the light class
+  RpState<T> heavy_state(const RpState<T>& ss, int sl, bool capturing) const {
+    RpState<T> sh = ss;
+    sh.heavy_list = d_heavy + ss.env_base; sh.heavy_cnt = d_heavy_cnt + 2 * sl; sh.heavy_done = d_heavy_cnt + 2 * sl + 1;
+    sh.heavy_peak = capturing ? nullptr : d_heavy_peak + sl;
+    return sh;
+  }
+  // ... the sensor stage: the state before the last substep in, the sensor arrays out
+  RpState<T> sensor_state(const RpState<T>& ss) const {
+    RpState<T> sq = ss;
+    sq.qpos = d_qpos_prev; sq.qvel = d_qvel_prev;
+    sq.sens_torque = d_sens_torque; sq.sens_touch = d_sens_touch;
+    sq.key_trace = nullptr; sq.prof = nullptr;
+    return sq;
+  }
+
+  // physics.reset() of the envs a device mask flags (null: all) -- rp_reset and rp_step_masked
+  void launch_reset(const unsigned char* dmask) {
+    hipLaunchKernelGGL(rp_reset_kernel<T>, dim3(nenv), dim3(64), 0, stream, reset_state(), d_qpos0, dmask, nv, nu, nsite, d_valid);
+  }
   int reset(const uint8_t* mask) override {
     HIP_OK(hipSetDevice(device));
     const unsigned char* dmask = nullptr;
     if (mask) {
-      hipPointerAttribute_t attr;
-      bool on_device = hipPointerGetAttributes(&attr, mask) == hipSuccess &&
-                       attr.type == hipMemoryTypeDevice;
-      (void)hipGetLastError();
-      if (on_device) dmask = mask;
+      if (is_device_ptr(mask)) dmask = mask;
       else {
         if (!d_mask) HIP_OK(hipMalloc((void**)&d_mask, (size_t)nenv));
         HIP_OK(hipMemcpyAsync(d_mask, mask, (size_t)nenv, hipMemcpyHostToDevice, stream));
@@ -718,9 +835,7 @@ struct Engine : EngineBase {
         dmask = d_mask;
       }
     }
-    RpState<T> sr = S;
-    sr.sens_torque = sensors_on ? d_sens_torque : nullptr; sr.sens_touch = sensors_on ? d_sens_touch : nullptr;
-    hipLaunchKernelGGL(rp_reset_kernel<T>, dim3(nenv), dim3(64), 0, stream, sr, d_qpos0, dmask, nv, nu, nsite, d_valid);
+    launch_reset(dmask);
     HIP_OK(hipGetLastError());
     return 0;
   }
@@ -769,10 +884,7 @@ struct Engine : EngineBase {
       // Host sources: drain the stream first.  Stream order alone should put this copy after
       // the kernels already enqueued, but under rocprofv3 --pmc (dispatch interception) a
       // pending kernel was observed to run after a later host-to-device copy.
-      hipPointerAttribute_t attr;
-      const bool src_on_device = hipPointerGetAttributes(&attr, src) == hipSuccess && attr.type == hipMemoryTypeDevice;
-      (void)hipGetLastError();
-      if (!src_on_device) HIP_OK(hipStreamSynchronize(stream));
+      if (!is_device_ptr(src)) HIP_OK(hipStreamSynchronize(stream));
       HIP_OK(hipMemcpyAsync(p, src, nb, hipMemcpyDefault, stream));
     }
     if (f == RP_ACTIVE) S.active = d_active;
@@ -786,320 +898,280 @@ struct Engine : EngineBase {
     if (!dst) return fail("rp_get: null destination");
     HIP_OK(hipSetDevice(device));
     if (nb) HIP_OK(hipMemcpyAsync(dst, p, nb, hipMemcpyDefault, stream));
-    hipPointerAttribute_t attr;
-    bool on_device = hipPointerGetAttributes(&attr, dst) == hipSuccess && attr.type == hipMemoryTypeDevice;
-    (void)hipGetLastError();
-    if (!on_device) HIP_OK(hipStreamSynchronize(stream));  // device destinations stay stream-ordered
+    if (!is_device_ptr(dst)) HIP_OK(hipStreamSynchronize(stream));  // device destinations stay stream-ordered
     return 0;
   }
-  int step(int nsub, uint32_t* trace, int mode, const uint8_t* reset_mask = nullptr) override {
-    HIP_OK(hipSetDevice(device));
-    if (mode == 0 && nsub <= 0) return fail("rp_step: n_substeps must be positive");
-    if (reset_mask) {
-      // rp_step_masked: physics.reset() of the flagged envs first (same launch as rp_reset with a device mask); their
-      // physics.forward() is the leading position / velocity stage below
-      hipPointerAttribute_t attr;
-      const bool on_device = hipPointerGetAttributes(&attr, reset_mask) == hipSuccess && attr.type == hipMemoryTypeDevice;
-      (void)hipGetLastError();
-      if (!on_device) return fail("rp_step_masked: the reset mask must be device memory");
-      RpState<T> sr = S;
-      sr.sens_torque = sensors_on ? d_sens_torque : nullptr; sr.sens_touch = sensors_on ? d_sens_touch : nullptr;
-      hipLaunchKernelGGL(rp_reset_kernel<T>, dim3(nenv), dim3(64), 0, stream, sr, d_qpos0, reset_mask, nv, nu, nsite, d_valid);
-    }
-    RpState<T> s = S;
-    size_t need = (size_t)nenv * (nsub > 0 ? nsub : 1) * 4;
-    if (trace && mode == 0) {
-      if (need > trace_cap) {
-        if (d_trace) hipFree(d_trace);
-        HIP_OK(hipMalloc((void**)&d_trace, need * sizeof(uint32_t)));
-        trace_cap = need;
-      }
-      s.key_trace = d_trace;
-    }
-    // inside a stream capture (the caller is recording a hipGraph of its whole step) no
-    // event may be synchronised and per-launch events are meaningless: skip the timers
+  // ---- rp_step / rp_forward / rp_step_masked: the host half, part by part (step() at the end puts them in order) ----
+
+  // What one call hands from part to part (on step()'s stack).
+  struct StepCtx {
+    int nsub = 0, mode = 0;
+    const uint8_t* reset_mask = nullptr;
+    bool capturing = false, timeit = false, lead_masked = false;
+    int slot = 0;          // of the timer rings
+    RpStepInput in;
+    RpStepPlan plan;
+    int nsl = 1;           // slices, after the runtime's vetoes
+    RpState<T> s;          // S with this call's key trace, order and output flags
+  };
+  // One slice of the batch: the envs [base, base + cnt) on stream st
+  struct Slice {
+    int sl = 0, base = 0, cnt = 0;
+    hipStream_t st = nullptr;
+    RpState<T> ss;         // StepCtx::s with env_base = base
+    int hgrid_step = 0;    // (the full-capacity stage's grid: one choice per step and slice)
+  };
+
+  // inside a stream capture (the caller is recording a hipGraph of its whole step) no
+  // event may be synchronised and per-launch events are meaningless: skip the timers
+  int begin_timers(StepCtx& c) {
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     (void)hipStreamIsCapturing(stream, &cap);
-    const bool capturing = cap != hipStreamCaptureStatusNone;
-    const int slot = ev_next;
-    if (!capturing) {
+    c.capturing = cap != hipStreamCaptureStatusNone;
+    c.slot = ev_next;
+    if (!c.capturing) {
       ev_next = (ev_next + 1) % kRing;
-      harvest(slot, true);
+      harvest(c.slot, true);
     }
-    const bool timeit = (mode == 0) && !capturing;
-    if (timeit) HIP_OK(hipEventRecord(ev0[slot], stream));
-    // mj_step1 for the current state, then n_sub x (mj_step2; mj_step1): dm_control's legacy
-    // order.  Two small kernels per substep instead of one fused launch: each half fits in
-    // registers, and the hand-over (RpStage) stays in L2 / Infinity Cache.
-    const int hb = (nenv + 255) / 256;
-    // Slices: the batch may be stepped as two halves on two streams.  Within a half the kernels are
-    // ordered (solver -> position -> solver ...), between the halves they are not, so the tail of one
-    // half's launch (a few heavy envs still running, most SIMDs idle) is filled by the other half's
-    // next kernel instead of waiting for a launch boundary.
-    int want = n_slices;
-    const bool fused_capable = lean && !deep && !graph && sizeof(T) == 8;   // (no fused builds for scenes with graph hulls)
-    bool fused_now = fused == 1 && fused_capable && mode == 0;
-    bool sched4 = false;
-    if (n_slices == 0 && mode == 0 && !fused_now) {
-      // The schedule of an rp_step, chosen by RULE (round 6; rounds 3-5 ran timing trials of up to four candidates on
-      // some steps of every 128 .. 1024: 1 % of a run, and a choice that differed from run to run).  All schedules give
-      // bit-identical results (tests/test_gpu_parity.py), so the rule only has to be good, not exact:
-      //   1 = one launch per stage        2 = the same as two slices on two streams, full-capacity launches on companion streams
-      //   3 = fused substeps (one launch takes a light env through all substeps; the rest in a clean-up launch)
-      //   4 = three slices, the position stage split (front part / pooled narrow phase / back part), no companion streams
-      // Measured on MI355X: batches under 3072 envs fill at most one round and a half of the chip's 2048 wave
-      // slots -- every launch boundary there is a tail, and the fused schedule (no boundaries) wins by 6-16 %; from 3072
-      // envs on, three slices with the split stage win on the replay (lists of envs outside the light class short or
-      // empty), two slices with companion streams when those lists are long (random policies: the full-capacity
-      // launches then need the chip to themselves beside the lean ones); 6144 envs and more are three rounds per launch
-      // and need no slices at all.  `many_heavy` follows the list lengths the device reports one step late (with
-      // hysteresis), never a timer.
-      double hl = 0;
-      for (int i = 0; i < last_nsl && i < kMaxSlices; i++) hl = heavy_est[i] > hl ? heavy_est[i] : hl;   // (the slices the last step used: the others' estimates are stale)
-      many_heavy = many_heavy ? hl >= 2.0 : hl >= 4.0;
-      const bool fused_ok = fused == 2 && fused_capable;
-      // (the split stage keeps at most 256 candidates / 384 result records per env where the one-kernel stage never
-      // overflows: once it has dropped any -- RP_WARN_SPLIT_FULL, counted on the device and read back with the list
-      // lengths -- the rule stops choosing it for this engine: identical inputs must not give different physics
-      // depending on the schedule.  ADVICE round 5.)
+    c.timeit = (c.mode == 0) && !c.capturing;
+    if (c.timeit) HIP_OK(hipEventRecord(ev0[c.slot], stream));
+    return 0;
+  }
+
+  // The schedule of this call: the rule (rp_schedule.hpp), then the vetoes that need the runtime, in this order: the
+  // split stage's buffers, the fork event, the slices' streams and join events.
+  void plan(StepCtx& c) {
+    c.in = plan_input(c.mode, c.capturing);
+    if (rp_engine_chooses(c.in)) {
+      // (the drop count of the split stage comes back with the list lengths: rp_plan_step's comment on split_ok)
       if (h_heavy_peak && *(volatile int*)&h_heavy_peak[kMaxSlices] > 0) split_dropped = true;
-      const bool split_ok = split_mode == 2 && split_capable && !capturing && !split_dropped;
-      int sched;
-      if (capturing) sched = fused_ok ? 3 : 1;
-      else if (nenv < 3072) sched = (fused_ok && !many_heavy) ? 3 : (nenv >= 1024 ? 2 : 1);   // (config 5, 2048 envs, long lists: fused 245 k, two slices 286 k)
-      else if (split_ok && !many_heavy) sched = 4;
-      else sched = nenv >= 6144 ? 1 : 2;
-      if (!capturing) auto_mode = sched;
-      fused_now = sched == 3;
-      want = sched == 2 ? 2 : (sched == 4 ? 3 : 1);
-      sched4 = sched == 4;
+      c.in.split_dropped = split_dropped;
     }
-    split_now = split_capable && mode == 0 && (split_mode == 1 || sched4);
-    int nsl = (mode == 0 && want > 1 && nenv >= 1024 && !capturing && !fused_now) ? (want >= 4 ? 4 : want) : 1;
-    // (slices 2 / 3 run ON the companion streams of slices 0 / 1 -- pooled_stream: four hardware queues -- so with more
-    // than two slices there are no companion streams, whoever asked for the slices: the full-capacity launch then goes in
-    // front of the lean one on the slice's own stream.  ADVICE round 5: only the engine's own three-slice schedule turned
-    // them off; a forced rp_set_stream_slices(e, 3 | 4) queued slice 2's whole chain behind slice 0's heavy solves.)
-    if (split_now && ((capturing && !B.frames) || !ensure_split_buffers())) split_now = false;   // (no allocation inside a stream capture)
-    if (mode == 0 && !capturing) last_nsl = nsl;
-    const bool companion_now = nsl <= 2;
+    c.plan = rp_plan_step(c.in);
+    many_heavy = c.plan.many_heavy;
+    if (c.plan.sched && !c.capturing) auto_mode = c.plan.sched;
+    split_now = c.plan.split_wanted;
+    if (split_now && ((c.capturing && !B.frames) || !ensure_split_buffers())) split_now = false;   // (no allocation inside a stream capture)
+    int nsl = c.plan.nsl;
+    if (c.mode == 0 && !c.capturing) last_nsl = nsl;
     if (nsl > 1 && !ev_fork && hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); ev_fork = nullptr; nsl = 1; }
     for (int i = 1; i < nsl; i++) {
       if (xstream[i]) continue;
       xstream[i] = pooled_stream(device, i, false);
       if (!xstream[i] || hipEventCreateWithFlags(&ev_join[i], hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); xstream[i] = nullptr; nsl = 1; break; }
     }
-    // slice sl covers the envs [bound(sl), bound(sl + 1)); bounds are multiples of 8 (XCD classes of the order)
-    auto bound = [&](int sl) { return sl >= nsl ? nenv : (int)(((long long)nenv * sl / nsl + 7) / 8 * 8); };
-    if (cost_order && mode == 0) s.order = d_order;   // (initialised to the identity; refreshed below)
-    // (legacy_step = False: the leading stage always runs -- it is what publishes the outputs of the incoming state,
-    // which the previous step's last position stage computed but kept to itself)
-    const bool lazy_now = lazy_position && legacy_step;
-    s.stale_outputs = (!legacy_step && mode == 0) ? 1 : 0;
-    const bool lead_masked = (lazy_now || reset_mask) && mode == 0;
-    if (lead_masked)
-      hipLaunchKernelGGL(rp_lead_mask_kernel, dim3(hb), dim3(256), 0, stream, d_lead, s.active, d_valid, lazy_now ? 1 : 0, reset_mask, nenv);
-    if (nsl > 1) {
+    c.nsl = nsl;
+  }
+
+  // Slices: the batch may be stepped as two halves on two streams.  Within a half the kernels are
+  // ordered (solver -> position -> solver ...), between the halves they are not, so the tail of one
+  // half's launch (a few heavy envs still running, most SIMDs idle) is filled by the other half's
+  // next kernel instead of waiting for a launch boundary.
+  int fork_slices(const StepCtx& c) {
+    if (c.nsl > 1) {
       HIP_OK(hipEventRecord(ev_fork, stream));
-      for (int i = 1; i < nsl; i++) HIP_OK(hipStreamWaitEvent(xstream[i], ev_fork, 0));
+      for (int i = 1; i < c.nsl; i++) HIP_OK(hipStreamWaitEvent(xstream[i], ev_fork, 0));
     }
-    for (int sl = 0; sl < nsl; sl++) {
-      hipStream_t st = sl == 0 ? stream : xstream[sl];
-      const int base = bound(sl), cnt = bound(sl + 1) - base;
-      RpState<T> ss = s;
-      ss.env_base = base;
-      auto launch_pos_listed = [&](const RpState<T>& q, int k, int grid, hipStream_t str) {
-        if constexpr (sizeof(T) == 8) {   // (the light class exists in the fp64 default builds only)
-          if (mesh) hipLaunchKernelGGL((rp_pos_list_kernel<T, 1>), dim3(grid), dim3(64), 0, str, M, q, B, k, nsub);
-          else hipLaunchKernelGGL((rp_pos_list_kernel<T, 0>), dim3(grid), dim3(64), 0, str, M, q, B, k, nsub);
-        }
-      };
-      // the position / velocity stage of substep k as front part, pooled narrow phase, back part (same results, bit for bit)
-      auto launch_pos_split = [&](const RpState<T>& q, int k) {
-        if constexpr (sizeof(T) == 8) {
-          RpStage<T> Bs = B;
-          Bs.tcount_off = sl * RPK_NSTRIPE * RPK_NTYPE_PAD;
-          Bs.split_dropped = capturing ? nullptr : d_heavy_peak + kMaxSlices;
-          int ng = cnt / 2;
-          ng = ng < 64 ? 64 : (ng > 2048 ? 2048 : ng);
-#define RP_SPLIT_LAUNCH(MESH_)                                                                                                     \
-          {                                                                                                                        \
-            hipLaunchKernelGGL((rp_pos_front_kernel<T, MESH_>), dim3(cnt), dim3(64), 0, st, M, q, Bs, k, nsub);                     \
-            hipLaunchKernelGGL((rp_narrow_kernel<T, MESH_>), dim3(ng), dim3(64), 0, st, M, q, Bs);                                  \
-            hipLaunchKernelGGL((rp_pos_back_kernel<T, MESH_>), dim3(cnt), dim3(64), 0, st, M, q, Bs, k, nsub);                      \
-          }
-          if (mesh && graph) RP_SPLIT_LAUNCH(2) else if (mesh) RP_SPLIT_LAUNCH(1) else RP_SPLIT_LAUNCH(0)
-#undef RP_SPLIT_LAUNCH
-        }
-      };
-      auto launch_pos_on = [&](const RpState<T>& q, int k) {
-        if (split_now && !deep && sizeof(T) == 8) { launch_pos_split(q, k); return; }
-        if (deep && mesh && graph) hipLaunchKernelGGL((rp_stage_kernel<T, 0, 0, RPK_MAXD_DEEP, 2>), dim3(cnt), dim3(64), 0, st, M, q, B, k, nsub);
-        else if (mesh && graph) hipLaunchKernelGGL((rp_stage_kernel<T, 0, 0, RPK_MAXD, 2>), dim3(cnt), dim3(64), 0, st, M, q, B, k, nsub);
-        else if (deep && mesh) hipLaunchKernelGGL((rp_stage_kernel<T, 0, 0, RPK_MAXD_DEEP, 1>), dim3(cnt), dim3(64), 0, st, M, q, B, k, nsub);
-        else if (deep) hipLaunchKernelGGL((rp_stage_kernel<T, 0, 0, RPK_MAXD_DEEP>), dim3(cnt), dim3(64), 0, st, M, q, B, k, nsub);
-        else if (mesh) hipLaunchKernelGGL((rp_stage_kernel<T, 0, 0, RPK_MAXD, 1>), dim3(cnt), dim3(64), 0, st, M, q, B, k, nsub);
-        else hipLaunchKernelGGL((rp_stage_kernel<T, 0>), dim3(cnt), dim3(64), 0, st, M, q, B, k, nsub);
-      };
-      // mj_step1 for the current state, in index order: d_order may date from a step with another slice
-      // count (a permutation of other ranges), and every slice must write the hand-over of exactly ITS envs
-      // before its solver stage reads it (the solver stage consumes the hand-over: it parks values in it)
-      RpState<T> lead = ss;
-      lead.order = nullptr;
-      if (lead_masked) lead.active = d_lead;   // skipped for envs whose hand-over is still the one of their state
-      launch_pos_on(lead, -1);
-      if (mode != 0) continue;
-      if constexpr (sizeof(T) == 8) {
-        if (fused_now) {
-          // heaviest envs first (4096 envs are two rounds of resident waves), from the hand-over just written
-          if (cost_order)
-            hipLaunchKernelGGL(rp_order_kernel, dim3(RP_ORDER_CLASSES), dim3(order_threads_for(cnt)), 0, st, d_order, B.hdr, s.active, base, cnt, (int*)nullptr, (int*)nullptr, (unsigned char*)nullptr);
-          RpState<T> sf = ss;
-          sf.heavy_list = d_heavy + base; sf.heavy_cnt = d_heavy_cnt + 2 * sl; sf.heavy_done = d_heavy_cnt + 2 * sl + 1;
-          sf.heavy_peak = capturing ? nullptr : d_heavy_peak + sl;
-          if (sensors_on) { sf.qpos_prev = d_qpos_prev; sf.qvel_prev = d_qvel_prev; }
-          const bool probe = timeit && sl == 0;
-          if (probe) { HIP_OK(hipEventRecord(sv0[slot], st)); sv_envs[slot] = cnt * nsub; sv_kind[slot] = 1; }
-          const int cgrid = capturing ? (cnt < kHeavyGrid ? cnt : kHeavyGrid) : heavy_grid_for(sl, cnt);
-          // (round 6: with the split stage's bodies where they exist -- the one-kernel position body spills 276 registers
-          // in the hull builds; RP_FUSED_SPLIT=0: the round-3 kernel)
-          const bool fsplit = fused_split && split_capable && !deep && (capturing ? B.frames != nullptr : ensure_split_buffers());
-          RpStage<T> Bf = B;
-          Bf.tlist = nullptr;   // (no pooled lists: every wave runs its own env's narrow phase)
-          if (fsplit && mesh) {
-            hipLaunchKernelGGL((rp_fused_split_kernel<T, 1>), dim3(cnt), dim3(64), 0, st, M, sf, Bf, nsub);
-            if (trunk4) hipLaunchKernelGGL((rp_cleanup_steps_kernel<T, 1, 4>), dim3(cgrid), dim3(64), 0, st, M, sf, B, nsub);
-            else hipLaunchKernelGGL((rp_cleanup_steps_kernel<T, 1, 0>), dim3(cgrid), dim3(64), 0, st, M, sf, B, nsub);
-          } else if (fsplit) {
-            hipLaunchKernelGGL((rp_fused_split_kernel<T, 0>), dim3(cnt), dim3(64), 0, st, M, sf, Bf, nsub);
-            if (trunk4) hipLaunchKernelGGL((rp_cleanup_steps_kernel<T, 0, 4>), dim3(cgrid), dim3(64), 0, st, M, sf, B, nsub);
-            else hipLaunchKernelGGL((rp_cleanup_steps_kernel<T, 0, 0>), dim3(cgrid), dim3(64), 0, st, M, sf, B, nsub);
-          } else if (mesh) {
-            hipLaunchKernelGGL((rp_fused_steps_kernel<T, 1>), dim3(cnt), dim3(64), 0, st, M, sf, B, nsub);
-            if (trunk4) hipLaunchKernelGGL((rp_cleanup_steps_kernel<T, 1, 4>), dim3(cgrid), dim3(64), 0, st, M, sf, B, nsub);
-            else hipLaunchKernelGGL((rp_cleanup_steps_kernel<T, 1, 0>), dim3(cgrid), dim3(64), 0, st, M, sf, B, nsub);
-          } else {
-            hipLaunchKernelGGL((rp_fused_steps_kernel<T, 0>), dim3(cnt), dim3(64), 0, st, M, sf, B, nsub);
-            if (trunk4) hipLaunchKernelGGL((rp_cleanup_steps_kernel<T, 0, 4>), dim3(cgrid), dim3(64), 0, st, M, sf, B, nsub);
-            else hipLaunchKernelGGL((rp_cleanup_steps_kernel<T, 0, 0>), dim3(cgrid), dim3(64), 0, st, M, sf, B, nsub);
-          }
-          if (probe) HIP_OK(hipEventRecord(sv1[slot], st));
-          if (sensors_on) {
-            // sensor stage: position / velocity stage of the state before the last substep + mj_rnePostConstraint
-            // with the constrained qacc (S.warm) and the contact row forces of that substep's solver stage
-            RpState<T> sq = ss;
-            sq.qpos = d_qpos_prev; sq.qvel = d_qvel_prev;
-            sq.sens_torque = d_sens_torque; sq.sens_touch = d_sens_touch;
-            sq.key_trace = nullptr; sq.prof = nullptr;
-            if (mesh) hipLaunchKernelGGL((rp_stage_kernel<T, 2, 0, RPK_MAXD, 1>), dim3(cnt), dim3(64), 0, st, M, sq, B, -1, nsub);
-            else hipLaunchKernelGGL((rp_stage_kernel<T, 2>), dim3(cnt), dim3(64), 0, st, M, sq, B, -1, nsub);
-          }
-          continue;
-        }
-      }
-      // ... then n_sub x (mj_step2; mj_step1): dm_control's legacy order.  Two kernels per substep instead
-      // of one fused launch: each half fits in registers, the hand-over (RpStage) stays in L2 / Infinity Cache.
-      int hgrid_step = 0;   // (the full-capacity stage's grid: one choice per step and slice)
-      bool split_step = false;
-      for (int k = 0; k < nsub; k++) {
-        const bool probe = timeit && sl == 0 && k == (int)(step_calls % (unsigned)nsub);
-        const bool sense = sensors_on && k == nsub - 1;
-        // cost-ordered launch: heaviest envs first, from the hand-over the position stage just wrote
-        // (the same pass compacts the envs outside the light class for the full-capacity solver stage)
-        const bool listed = lean && d_heavy != nullptr;
-        if (cost_order || listed)
-          hipLaunchKernelGGL(rp_order_kernel, dim3(RP_ORDER_CLASSES), dim3(order_threads_for(cnt)), 0, st, cost_order ? d_order : nullptr, B.hdr, s.active, base, cnt,
-                             listed ? d_heavy : nullptr, listed ? d_heavy_cnt + 2 * sl : nullptr, listed ? d_listed : nullptr);
-        // (RP_X_ORDER_TWICE=1: MEASUREMENT ONLY -- the order pass a second time (no list): what the pass costs the step)
-        if (x_order_twice && cost_order)
-          hipLaunchKernelGGL(rp_order_kernel, dim3(RP_ORDER_CLASSES), dim3(order_threads_for(cnt)), 0, st, d_order, B.hdr, s.active, base, cnt, (int*)nullptr, (int*)nullptr, (unsigned char*)nullptr);
-        if (sense) {  // the state this substep's forces belong to (the solver stage integrates in place)
-          HIP_OK(hipMemcpyAsync(d_qpos_prev + (size_t)base * nv, S.qpos + (size_t)base * nv, sizeof(T) * (size_t)cnt * nv, hipMemcpyDeviceToDevice, st));
-          HIP_OK(hipMemcpyAsync(d_qvel_prev + (size_t)base * nv, S.qvel + (size_t)base * nv, sizeof(T) * (size_t)cnt * nv, hipMemcpyDeviceToDevice, st));
-        }
-        if (probe) { HIP_OK(hipEventRecord(sv0[slot], st)); sv_envs[slot] = cnt; sv_kind[slot] = 0; }
-        // solver stage; the build specialised for "every tree has a 4-link trunk" when it applies
-        // light envs on the lean build (two waves per SIMD), the others on the full-capacity build (it skips
-        // the light ones) -- side by side: the full-capacity launch goes to the slice's companion stream
-        hipStream_t hs = st;
-        if (lean && !capturing && companion_now) {
-          if (!hstream[sl]) hstream[sl] = pooled_stream(device, 4 + sl, false);
-          if (hstream[sl] && !ev_hfork[sl] && (hipEventCreateWithFlags(&ev_hfork[sl], hipEventDisableTiming) != hipSuccess ||
-                                               hipEventCreateWithFlags(&ev_hjoin[sl], hipEventDisableTiming) != hipSuccess)) {
-            (void)hipGetLastError(); hstream[sl] = nullptr;
-          }
-          if (hstream[sl]) {
-            hs = hstream[sl];
-            HIP_OK(hipEventRecord(ev_hfork[sl], st));
-            HIP_OK(hipStreamWaitEvent(hs, ev_hfork[sl], 0));
-          }
-        }
-        RpState<T> sh = ss;
-        int hgrid = cnt;
-        if (listed) {
-          sh.heavy_list = d_heavy + base; sh.heavy_cnt = d_heavy_cnt + 2 * sl; sh.heavy_done = d_heavy_cnt + 2 * sl + 1;
-          sh.heavy_peak = capturing ? nullptr : d_heavy_peak + sl;
-          // (the split pays when the list is long: config 3 446 -> 455 k; on a batch whose lists are empty the extra
-          // launch and the later join cost 1-4 %: config 2 657 -> 632 ... 651 k -- so it follows the same lagged estimate)
-          hgrid = capturing ? (cnt < kHeavyGrid ? cnt : kHeavyGrid) : (k == 0 ? (hgrid_step = heavy_grid_for(sl, cnt)) : hgrid_step);
-          split_step = hs != st && !deep && !graph && sizeof(T) == 8 && heavy_est[sl] >= 4.0;
-          sh.heavy_keep = (split_step && !sense) ? 1 : 0;
-        }
-        // (RP_X_NO_HEAVY=1: MEASUREMENT ONLY -- the full-capacity launch is suppressed, envs outside the light class are
-        // not stepped at all: what the launch costs a batch whose lists are empty)
-        if (x_no_heavy && listed) { /* nothing */ }
-        else if (deep) hipLaunchKernelGGL((rp_stage_kernel<T, 1, 0, RPK_MAXD_DEEP>), dim3(hgrid), dim3(64), 0, hs, M, sh, B, k, nsub);
-        else if (trunk4) hipLaunchKernelGGL((rp_stage_kernel<T, 1, 4>), dim3(hgrid), dim3(64), 0, hs, M, sh, B, k, nsub);
-        else hipLaunchKernelGGL((rp_stage_kernel<T, 1>), dim3(hgrid), dim3(64), 0, hs, M, sh, B, k, nsub);
-        // ... and, except at a substep the sensor stage follows, the heavy envs' position / velocity stage goes with
-        // them: the slice's own position launch then skips them and no longer waits for the slowest heavy solve
-        // (config 3: 0.27 ms of every 0.81 ms substep); the streams join after it, in front of the next order pass
-        const bool split_pos = split_step && listed && !sense;
-        if (hs != st && !split_pos) HIP_OK(hipEventRecord(ev_hjoin[sl], hs));
-        if (lean) hipLaunchKernelGGL((rp_lean_solver_kernel<T>), dim3(cnt), dim3(64), 0, st, M, ss, B);
-        if (hs != st && !split_pos) HIP_OK(hipStreamWaitEvent(st, ev_hjoin[sl], 0));
-        if (probe) HIP_OK(hipEventRecord(sv1[slot], st));
-        if (sense) {
-          // sensor stage: position / velocity stage of the saved state + mj_rnePostConstraint with the
-          // constrained qacc (S.warm) and the contact row forces the solver stage just stored
-          RpState<T> sq = ss;
-          sq.qpos = d_qpos_prev; sq.qvel = d_qvel_prev;
-          sq.sens_torque = d_sens_torque; sq.sens_touch = d_sens_touch;
-          sq.key_trace = nullptr; sq.prof = nullptr;
-          if (deep && mesh && graph) hipLaunchKernelGGL((rp_stage_kernel<T, 2, 0, RPK_MAXD_DEEP, 2>), dim3(cnt), dim3(64), 0, st, M, sq, B, -1, nsub);
-          else if (mesh && graph) hipLaunchKernelGGL((rp_stage_kernel<T, 2, 0, RPK_MAXD, 2>), dim3(cnt), dim3(64), 0, st, M, sq, B, -1, nsub);
-          else if (deep && mesh) hipLaunchKernelGGL((rp_stage_kernel<T, 2, 0, RPK_MAXD_DEEP, 1>), dim3(cnt), dim3(64), 0, st, M, sq, B, -1, nsub);
-          else if (deep) hipLaunchKernelGGL((rp_stage_kernel<T, 2, 0, RPK_MAXD_DEEP>), dim3(cnt), dim3(64), 0, st, M, sq, B, -1, nsub);
-          else if (mesh) hipLaunchKernelGGL((rp_stage_kernel<T, 2, 0, RPK_MAXD, 1>), dim3(cnt), dim3(64), 0, st, M, sq, B, -1, nsub);
-          else hipLaunchKernelGGL((rp_stage_kernel<T, 2>), dim3(cnt), dim3(64), 0, st, M, sq, B, -1, nsub);
-        }
-        if (split_pos) {
-          RpState<T> sp = sh;              // (the list; walked in list order)
-          sp.order = nullptr; sp.heavy_keep = 0;
-          launch_pos_listed(sp, k, hgrid, hs);
-          HIP_OK(hipEventRecord(ev_hjoin[sl], hs));
-          RpState<T> sm_ = ss;
-          sm_.skip_heavy = 1;
-          launch_pos_on(sm_, k);
-          HIP_OK(hipStreamWaitEvent(st, ev_hjoin[sl], 0));
-        } else {
-          launch_pos_on(ss, k);
-        }
-      }
-    }
-    for (int i = 1; i < nsl; i++) { HIP_OK(hipEventRecord(ev_join[i], xstream[i])); HIP_OK(hipStreamWaitEvent(stream, ev_join[i], 0)); }
-    hipLaunchKernelGGL(rp_mark_valid_kernel, dim3(hb), dim3(256), 0, stream, d_valid, s.active, reset_mask, nenv);
-    if (mode == 0 && lean && !capturing && h_heavy_peak && !heavy_grid_fixed) {
+    return 0;
+  }
+  Slice slice_of(const StepCtx& c, int sl) const {
+    Slice x;
+    x.sl = sl; x.st = sl == 0 ? stream : xstream[sl];
+    x.base = rp_slice_bound(nenv, c.nsl, sl); x.cnt = rp_slice_bound(nenv, c.nsl, sl + 1) - x.base;
+    x.ss = c.s;
+    x.ss.env_base = x.base;
+    return x;
+  }
+
+  // ... the slices join the caller's stream; the hand-overs are marked valid; the list peaks start their way back
+  int join_slices(const StepCtx& c) {
+    for (int i = 1; i < c.nsl; i++) { HIP_OK(hipEventRecord(ev_join[i], xstream[i])); HIP_OK(hipStreamWaitEvent(stream, ev_join[i], 0)); }
+    hipLaunchKernelGGL(rp_mark_valid_kernel, dim3((nenv + 255) / 256), dim3(256), 0, stream, d_valid, c.s.active, c.reset_mask, nenv);
+    if (c.mode == 0 && lean && !c.capturing && h_heavy_peak && !heavy_grid_fixed) {
       // the longest lists of this step, for the grids of a later one (the host never waits for the copy)
       HIP_OK(hipMemcpyAsync(h_heavy_peak, d_heavy_peak, sizeof(int) * (kMaxSlices + 1), hipMemcpyDeviceToHost, stream));
       HIP_OK(hipMemsetAsync(d_heavy_peak, 0, sizeof(int) * (kMaxSlices + 1), stream));
     }
-    HIP_OK(hipGetLastError());
-    if (mode == 0) step_calls++;
-    if (timeit) { HIP_OK(hipEventRecord(ev1[slot], stream)); ev_pending[slot] = true; }
-    if (trace && mode == 0)
-      HIP_OK(hipMemcpyAsync(trace, d_trace, need * sizeof(uint32_t), hipMemcpyDefault, stream));
     return 0;
+  }
+
+  // the position / velocity stage of substep k (-1: of the incoming state) for the envs of slice x
+  void emit_pos(const StepCtx& c, const Slice& x, const RpState<T>& q, int k) {
+    if (!(split_now && !deep && sizeof(T) == 8)) { launch_stage<T, 0>(variant, x.cnt, x.st, M, q, B, k, c.nsub); return; }
+    // ... as front part, pooled narrow phase, back part (same results, bit for bit)
+    RpStage<T> Bs = B;
+    Bs.tcount_off = x.sl * RPK_NSTRIPE * RPK_NTYPE_PAD;
+    Bs.split_dropped = c.capturing ? nullptr : d_heavy_peak + kMaxSlices;
+    int ng = x.cnt / 2;
+    ng = ng < 64 ? 64 : (ng > 2048 ? 2048 : ng);
+    launch_pos_split<T>(variant, x.cnt, ng, x.st, M, q, Bs, k, c.nsub);
+  }
+
+  // order pass over slice x, from the hand-over the position stage just wrote: the cost order and / or the list of envs
+  // outside the light class
+  void emit_order(const StepCtx& c, const Slice& x, bool order, bool list) {
+    hipLaunchKernelGGL(rp_order_kernel, dim3(RP_ORDER_CLASSES), dim3(rp_order_threads_for(x.cnt)), 0, x.st, order ? d_order : nullptr, B.hdr, c.s.active,
+                       x.base, x.cnt, list ? d_heavy : nullptr, list ? d_heavy_cnt + 2 * x.sl : nullptr, list ? d_listed : nullptr);
+  }
+
+  // sensor stage: position / velocity stage of the state before the last substep + mj_rnePostConstraint
+  // with the constrained qacc (S.warm) and the contact row forces of that substep's solver stage
+  void emit_sensor_stage(const StepCtx& c, const Slice& x) {
+    launch_stage<T, 2>(variant, x.cnt, x.st, M, sensor_state(x.ss), B, -1, c.nsub);
+  }
+
+  // Fused substeps: one launch takes every light env of the slice through all substeps, a clean-up launch the others.
+  int emit_fused_slice(const StepCtx& c, const Slice& x) {
+    if constexpr (sizeof(T) == 8) {
+      // heaviest envs first (4096 envs are two rounds of resident waves), from the hand-over just written
+      if (cost_order) emit_order(c, x, true, false);
+      RpState<T> sf = heavy_state(x.ss, x.sl, c.capturing);
+      if (sensors_on) { sf.qpos_prev = d_qpos_prev; sf.qvel_prev = d_qvel_prev; }
+      const bool probe = c.timeit && x.sl == 0;
+      if (probe) { HIP_OK(hipEventRecord(sv0[c.slot], x.st)); sv_envs[c.slot] = x.cnt * c.nsub; sv_kind[c.slot] = 1; }
+      const int cgrid = c.capturing ? (x.cnt < kHeavyGrid ? x.cnt : kHeavyGrid) : heavy_grid_for(x.sl, x.cnt);
+      // (round 6: with the split stage's bodies where they exist -- the one-kernel position body spills 276 registers
+      // in the hull builds; RP_FUSED_SPLIT=0: the round-3 kernel)
+      const bool fsplit = fused_split && split_capable && !deep && (c.capturing ? B.frames != nullptr : ensure_split_buffers());
+      RpStage<T> Bf = B;
+      Bf.tlist = nullptr;   // (no pooled lists: every wave runs its own env's narrow phase)
+      launch_fused<T>(variant, fsplit, x.cnt, cgrid, x.st, M, sf, fsplit ? Bf : B, B, c.nsub);
+      if (probe) HIP_OK(hipEventRecord(sv1[c.slot], x.st));
+      if (sensors_on) emit_sensor_stage(c, x);
+    }
+    return 0;
+  }
+
+  // Substep k of slice x: mj_step2 (the solver stage), then mj_step1 (the position / velocity stage) of the new state --
+  // dm_control's legacy order.  Two kernels per substep instead of one fused launch: each half fits in registers,
+  // the hand-over (RpStage) stays in L2 / Infinity Cache.
+  int emit_substep(const StepCtx& c, Slice& x, int k) {
+    hipStream_t st = x.st;
+    const int sl = x.sl, base = x.base, cnt = x.cnt, slot = c.slot;
+    const bool probe = c.timeit && sl == 0 && k == (int)(step_calls % (unsigned)c.nsub);
+    const bool sense = sensors_on && k == c.nsub - 1;
+    // cost-ordered launch: heaviest envs first, from the hand-over the position stage just wrote
+    // (the same pass compacts the envs outside the light class for the full-capacity solver stage)
+    const bool listed = lean && d_heavy != nullptr;
+    if (cost_order || listed) emit_order(c, x, cost_order, listed);
+    // (RP_X_ORDER_TWICE=1: MEASUREMENT ONLY -- the order pass a second time (no list): what the pass costs the step)
+    if (x_order_twice && cost_order) emit_order(c, x, true, false);
+    if (sense) {  // the state this substep's forces belong to (the solver stage integrates in place)
+      HIP_OK(hipMemcpyAsync(d_qpos_prev + (size_t)base * nv, S.qpos + (size_t)base * nv, sizeof(T) * (size_t)cnt * nv, hipMemcpyDeviceToDevice, st));
+      HIP_OK(hipMemcpyAsync(d_qvel_prev + (size_t)base * nv, S.qvel + (size_t)base * nv, sizeof(T) * (size_t)cnt * nv, hipMemcpyDeviceToDevice, st));
+    }
+    if (probe) { HIP_OK(hipEventRecord(sv0[slot], st)); sv_envs[slot] = cnt; sv_kind[slot] = 0; }
+    // solver stage; the build specialised for "every tree has a 4-link trunk" when it applies
+    // light envs on the lean build (two waves per SIMD), the others on the full-capacity build (it skips
+    // the light ones) -- side by side: the full-capacity launch goes to the slice's companion stream
+    hipStream_t hs = st;
+    if (lean && !c.capturing && c.plan.companion_now) {
+      if (!hstream[sl]) hstream[sl] = pooled_stream(device, 4 + sl, false);
+      if (hstream[sl] && !ev_hfork[sl] && (hipEventCreateWithFlags(&ev_hfork[sl], hipEventDisableTiming) != hipSuccess ||
+                                           hipEventCreateWithFlags(&ev_hjoin[sl], hipEventDisableTiming) != hipSuccess)) {
+        (void)hipGetLastError(); hstream[sl] = nullptr;
+      }
+      if (hstream[sl]) {
+        hs = hstream[sl];
+        HIP_OK(hipEventRecord(ev_hfork[sl], st));
+        HIP_OK(hipStreamWaitEvent(hs, ev_hfork[sl], 0));
+      }
+    }
+    RpState<T> sh = x.ss;
+    int hgrid = cnt;
+    bool split_step = false;
+    if (listed) {
+      sh = heavy_state(x.ss, sl, c.capturing);
+      hgrid = c.capturing ? (cnt < kHeavyGrid ? cnt : kHeavyGrid) : (k == 0 ? (x.hgrid_step = heavy_grid_for(sl, cnt)) : x.hgrid_step);
+      split_step = rp_heavy_pos_alongside(c.in, hs != st, sizeof(T) == 8, heavy_est[sl]);
+      sh.heavy_keep = (split_step && !sense) ? 1 : 0;
+    }
+    // (RP_X_NO_HEAVY=1: MEASUREMENT ONLY -- the full-capacity launch is suppressed, envs outside the light class are
+    // not stepped at all: what the launch costs a batch whose lists are empty)
+    if (x_no_heavy && listed) { /* nothing */ }
+    else launch_stage<T, 1>(variant, hgrid, hs, M, sh, B, k, c.nsub);
+    // ... and, except at a substep the sensor stage follows, the heavy envs' position / velocity stage goes with
+    // them: the slice's own position launch then skips them and no longer waits for the slowest heavy solve
+    // (config 3: 0.27 ms of every 0.81 ms substep); the streams join after it, in front of the next order pass
+    const bool split_pos = split_step && listed && !sense;
+    if (hs != st && !split_pos) HIP_OK(hipEventRecord(ev_hjoin[sl], hs));
+    if (lean) hipLaunchKernelGGL((rp_lean_solver_kernel<T>), dim3(cnt), dim3(64), 0, st, M, x.ss, B);
+    if (hs != st && !split_pos) HIP_OK(hipStreamWaitEvent(st, ev_hjoin[sl], 0));
+    if (probe) HIP_OK(hipEventRecord(sv1[slot], st));
+    if (sense) emit_sensor_stage(c, x);   // (of the saved state, with the contact row forces the solver stage just stored)
+    if (split_pos) {
+      RpState<T> sp = sh;              // (the list; walked in list order)
+      sp.order = nullptr; sp.heavy_keep = 0;
+      launch_pos_listed<T>(variant, hgrid, hs, M, sp, B, k, c.nsub);
+      HIP_OK(hipEventRecord(ev_hjoin[sl], hs));
+      RpState<T> sm_ = x.ss;
+      sm_.skip_heavy = 1;
+      emit_pos(c, x, sm_, k);
+      HIP_OK(hipStreamWaitEvent(st, ev_hjoin[sl], 0));
+    } else {
+      emit_pos(c, x, x.ss, k);
+    }
+    return 0;
+  }
+
+  // timers and trace copy-out
+  int finish(const StepCtx& c, uint32_t* trace, size_t trace_words) {
+    HIP_OK(hipGetLastError());
+    if (c.mode == 0) step_calls++;
+    if (c.timeit) { HIP_OK(hipEventRecord(ev1[c.slot], stream)); ev_pending[c.slot] = true; }
+    if (trace && c.mode == 0)
+      HIP_OK(hipMemcpyAsync(trace, d_trace, trace_words * sizeof(uint32_t), hipMemcpyDefault, stream));
+    return 0;
+  }
+
+  int step(int nsub, uint32_t* trace, int mode, const uint8_t* reset_mask = nullptr) override {
+    HIP_OK(hipSetDevice(device));
+    if (mode == 0 && nsub <= 0) return fail("rp_step: n_substeps must be positive");
+    if (reset_mask) {
+      // rp_step_masked: physics.reset() of the flagged envs first (same launch as rp_reset with a device mask); their
+      // physics.forward() is the leading position / velocity stage below
+      if (!is_device_ptr(reset_mask)) return fail("rp_step_masked: the reset mask must be device memory");
+      launch_reset(reset_mask);
+    }
+    StepCtx c;
+    c.nsub = nsub; c.mode = mode; c.reset_mask = reset_mask;
+    c.s = S;
+    const size_t need = (size_t)nenv * (nsub > 0 ? nsub : 1) * 4;
+    if (trace && mode == 0) {
+      if (need > trace_cap) {
+        if (d_trace) hipFree(d_trace);
+        HIP_OK(hipMalloc((void**)&d_trace, need * sizeof(uint32_t)));
+        trace_cap = need;
+      }
+      c.s.key_trace = d_trace;
+    }
+    RP_TRY(begin_timers(c));
+    plan(c);
+    if (cost_order && mode == 0) c.s.order = d_order;   // (initialised to the identity; refreshed by the order passes)
+    // (legacy_step = False: the leading stage always runs -- it is what publishes the outputs of the incoming state,
+    // which the previous step's last position stage computed but kept to itself)
+    const bool lazy_now = lazy_position && legacy_step;
+    c.s.stale_outputs = (!legacy_step && mode == 0) ? 1 : 0;
+    c.lead_masked = (lazy_now || reset_mask) && mode == 0;
+    if (c.lead_masked)
+      hipLaunchKernelGGL(rp_lead_mask_kernel, dim3((nenv + 255) / 256), dim3(256), 0, stream, d_lead, c.s.active, d_valid, lazy_now ? 1 : 0, reset_mask, nenv);
+    RP_TRY(fork_slices(c));
+    for (int sl = 0; sl < c.nsl; sl++) {
+      Slice x = slice_of(c, sl);
+      // mj_step1 for the current state, in index order: d_order may date from a step with another slice
+      // count (a permutation of other ranges), and every slice must write the hand-over of exactly ITS envs
+      // before its solver stage reads it (the solver stage consumes the hand-over: it parks values in it)
+      RpState<T> lead = x.ss;
+      lead.order = nullptr;
+      if (c.lead_masked) lead.active = d_lead;   // skipped for envs whose hand-over is still the one of their state
+      emit_pos(c, x, lead, -1);
+      if (mode != 0) continue;
+      // ... then n_sub x (mj_step2; mj_step1), in one launch per slice or stage by stage
+      if (c.plan.fused_now && sizeof(T) == 8) { RP_TRY(emit_fused_slice(c, x)); continue; }
+      for (int k = 0; k < nsub; k++) RP_TRY(emit_substep(c, x, k));
+    }
+    RP_TRY(join_slices(c));
+    return finish(c, trace, need);
   }
 };
 

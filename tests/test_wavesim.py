@@ -131,3 +131,32 @@ def test_impratio_and_cylinder_colliders_on_the_wave_emulator(wavesim_lib):
     assert maxcon >= 6 and worst < 1e-9, (worst, maxcon)
     worst, compared, cyl = [float(x) for x in re.search(r"CYLINDER (.*)", out.stdout).group(1).split()]
     assert compared >= 10 and cyl >= 8 and worst < 1e-9, (worst, compared, cyl)
+
+
+LAUNCH_TRACE_GROUPS = ("prim64", "hull64", "graph64", "deep64", "prim32", "short64", "sizes", "executed")
+
+
+@pytest.mark.parametrize("group", LAUNCH_TRACE_GROUPS)
+def test_launch_traces_equal_the_recorded_ones(wavesim_lib, group, tmp_path):
+    """What rp_step / rp_forward / rp_step_masked ENQUEUE -- every kernel launch with its instantiation, grid, block and
+    stream, every event record and wait, every asynchronous copy and fill, in order -- under every schedule, setting and
+    kernel build, against tests/golden/launch_trace (written by tests/wavesim/launch_trace.py before the host code of
+    rp_step was split into parts).  A file holds, per case, the count and SHA-1 of every call's lines, and the lines
+    themselves for representative cases; the script leaves the raw log beside its output for reading a difference.
+    Kernels are skipped except in "executed"; see the script for the cases."""
+    env = dict(os.environ, RP_ENGINE_LIB=wavesim_lib, WAVESIM_SITE="0", RP_SKIP_SELF_CHECK="1")
+    for k in [k for k in env if k.startswith("RP_") and k not in ("RP_ENGINE_LIB", "RP_SKIP_SELF_CHECK")]:
+        del env[k]   # (the engine's own switches are part of the cases)
+    out = subprocess.run([sys.executable, os.path.join(WS, "launch_trace.py"), str(tmp_path), group], env=env,
+                         capture_output=True, text=True, timeout=900)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
+    got = (tmp_path / (group + ".txt")).read_text().splitlines()
+    want = open(os.path.join(HERE, "golden", "launch_trace", group + ".txt")).read().splitlines()
+    first = next((i for i, (a, b) in enumerate(zip(got, want)) if a != b), min(len(got), len(want)))
+    head = max((i for i in range(first + 1) if i < len(want) and want[i].startswith("## ")), default=0)
+    assert got == want, "first difference at line %d (%s):\n  recorded: %s\n  now:      %s" % (
+        first + 1, want[head] if want else "", want[first] if first < len(want) else "<end>", got[first] if first < len(got) else "<end>")
+
+
+def test_every_recorded_launch_trace_is_compared():
+    assert sorted(os.listdir(os.path.join(HERE, "golden", "launch_trace"))) == sorted(g + ".txt" for g in LAUNCH_TRACE_GROUPS)

@@ -1,6 +1,7 @@
 // TEST INFRASTRUCTURE ONLY: stand-in for <hip/hip_runtime.h> when the engine's sources are compiled
 // for the CPU wave emulator (tests/wavesim).  Device memory is host memory, streams and events are
-// no-ops (everything is synchronous), kernels run through wavesim::launch.
+// no-ops (everything is synchronous), kernels run through wavesim::launch.  Every enqueue (launch, event
+// record / wait, asynchronous copy / fill) can be logged: the launch trace of wavesim.hpp.
 #pragma once
 #ifndef _GNU_SOURCE
 #define _GNU_SOURCE
@@ -12,6 +13,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <typeinfo>
 
 #include "../wavesim.hpp"
 
@@ -149,24 +151,38 @@ static inline hipError_t hipFree(void* p) { ::free(p); return hipSuccess; }
 static inline hipError_t hipHostMalloc(void** p, size_t n, unsigned = 0) { *p = ::malloc(n ? n : 1); return *p ? hipSuccess : hipErrorUnknown; }
 static inline hipError_t hipHostFree(void* p) { ::free(p); return hipSuccess; }
 static inline hipError_t hipMemset(void* p, int v, size_t n) { ::memset(p, v, n); return hipSuccess; }
-static inline hipError_t hipMemsetAsync(void* p, int v, size_t n, hipStream_t) { ::memset(p, v, n); return hipSuccess; }
+static inline hipError_t hipMemsetAsync(void* p, int v, size_t n, hipStream_t s) { wavesim::trace_copy("memset", n, s); ::memset(p, v, n); return hipSuccess; }
 static inline hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind) { ::memmove(d, s, n); return hipSuccess; }
-static inline hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind, hipStream_t) { ::memmove(d, s, n); return hipSuccess; }
+static inline hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind, hipStream_t st) { wavesim::trace_copy("memcpy", n, st); ::memmove(d, s, n); return hipSuccess; }
 static inline hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) { *s = (hipStream_t)::malloc(8); return hipSuccess; }
 static inline hipError_t hipStreamCreateWithPriority(hipStream_t* s, unsigned, int) { *s = (hipStream_t)::malloc(8); return hipSuccess; }
 static inline hipError_t hipDeviceGetStreamPriorityRange(int* least, int* greatest) { *least = 0; *greatest = 0; return hipSuccess; }
 static inline hipError_t hipStreamDestroy(hipStream_t s) { ::free(s); return hipSuccess; }
 static inline hipError_t hipStreamSynchronize(hipStream_t) { return hipSuccess; }
-static inline hipError_t hipStreamWaitEvent(hipStream_t, hipEvent_t, unsigned) { return hipSuccess; }
-static inline hipError_t hipStreamIsCapturing(hipStream_t, hipStreamCaptureStatus* c) { *c = hipStreamCaptureStatusNone; return hipSuccess; }
+static inline hipError_t hipStreamWaitEvent(hipStream_t s, hipEvent_t e, unsigned) { wavesim::trace_event("wait", e, s); return hipSuccess; }
+static inline hipError_t hipStreamIsCapturing(hipStream_t, hipStreamCaptureStatus* c) {
+  *c = wavesim::switch_on("WAVESIM_CAPTURING") ? hipStreamCaptureStatusActive : hipStreamCaptureStatusNone;
+  return hipSuccess;
+}
 static inline hipError_t hipEventCreate(hipEvent_t* e) { *e = (hipEvent_t)::malloc(8); return hipSuccess; }
 static inline hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { *e = (hipEvent_t)::malloc(8); return hipSuccess; }
 static inline hipError_t hipEventDestroy(hipEvent_t e) { ::free(e); return hipSuccess; }
-static inline hipError_t hipEventRecord(hipEvent_t, hipStream_t) { return hipSuccess; }
+static inline hipError_t hipEventRecord(hipEvent_t e, hipStream_t s) { wavesim::trace_event("record", e, s); return hipSuccess; }
 static inline hipError_t hipEventSynchronize(hipEvent_t) { return hipSuccess; }
 static inline hipError_t hipEventQuery(hipEvent_t) { return hipSuccess; }
 static inline hipError_t hipEventElapsedTime(float* ms, hipEvent_t, hipEvent_t) { *ms = 0.f; return hipSuccess; }
-static inline hipError_t hipPointerGetAttributes(hipPointerAttribute_t* a, const void*) { a->type = hipMemoryTypeHost; return hipSuccess; }
+static inline hipError_t hipPointerGetAttributes(hipPointerAttribute_t* a, const void*) {
+  a->type = wavesim::switch_on("WAVESIM_DEVICE_PTRS") ? hipMemoryTypeDevice : hipMemoryTypeHost;
+  return hipSuccess;
+}
 
-#define hipLaunchKernelGGL(kernel, grid, block, shmem, stream, ...) \
-  wavesim::launch((grid), (block), [&]() { kernel(__VA_ARGS__); })
+// The launch trace (wavesim.hpp) names a kernel by its instantiation, whatever the call site spells: the mangled name
+// of a type that has the kernel as its template argument spells every template argument out, defaults included.
+template <auto K> struct ws_kernel_tag {};
+template <auto K> static const char* ws_kernel_name() { return typeid(ws_kernel_tag<K>).name(); }
+#define hipLaunchKernelGGL(kernel, grid, block, shmem, stream, ...)                                        \
+  do {                                                                                                     \
+    const wavesim::Dim3 ws_grid_ = (grid), ws_block_ = (block);                                            \
+    if (wavesim::trace_on()) wavesim::trace_launch(ws_kernel_name<kernel>(), ws_grid_, ws_block_, (stream)); \
+    if (!wavesim::switch_on("WAVESIM_SKIP_KERNELS")) wavesim::launch(ws_grid_, ws_block_, [&]() { kernel(__VA_ARGS__); }); \
+  } while (0)

@@ -1,6 +1,7 @@
 // wavesim.cpp -- TEST INFRASTRUCTURE ONLY (see wavesim.hpp).
 #include "wavesim.hpp"
 
+#include <cxxabi.h>
 #include <dlfcn.h>
 #include <sys/mman.h>
 
@@ -8,6 +9,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <string>
 #include <thread>
 #include <vector>
 
@@ -290,4 +292,80 @@ void launch(Dim3 grid, Dim3 block, const std::function<void()>& fn) {
   for (auto& t : pool) t.join();
 }
 
+// ---- launch trace (wavesim.hpp)
+namespace {
+struct Trace {
+  std::string path;
+  FILE* f = nullptr;
+  std::vector<const void*> streams, events;
+  // (re)opens the file WAVESIM_TRACE names now: a script may point one process at several files in turn
+  FILE* file() {
+    const char* p = getenv("WAVESIM_TRACE");
+    if (!p || !*p) { if (f) { fclose(f); f = nullptr; path.clear(); } return nullptr; }
+    if (!f || path != p) {
+      if (f) fclose(f);
+      path = p;
+      f = fopen(p, "w");
+      if (!f) die("cannot open the WAVESIM_TRACE file");
+      setvbuf(f, nullptr, _IOLBF, 0);   // (the driving script reads a step's lines back)
+      streams.clear(); events.clear();
+    }
+    return f;
+  }
+  static int id_of(std::vector<const void*>& seen, const void* p) {
+    for (size_t i = 0; i < seen.size(); i++) if (seen[i] == p) return (int)i;
+    seen.push_back(p);
+    return (int)seen.size() - 1;
+  }
+} g_trace;
+}  // namespace
+
+bool switch_on(const char* name) {
+  const char* v = getenv(name);
+  return v && *v && *v != '0';
+}
+bool trace_on() { return g_trace.file() != nullptr; }
+void trace_launch(const char* mangled_tag, Dim3 grid, Dim3 block, const void* stream) {
+  FILE* f = g_trace.file();
+  if (!f) return;
+  // "ws_kernel_tag<&(void rp_stage_kernel<double, 0, 0, 9, 0>(RpModel<double>, ...))>": keep the kernel and its arguments
+  int status = 0;
+  char* dm = abi::__cxa_demangle(mangled_tag, nullptr, nullptr, &status);
+  std::string name = status == 0 && dm ? dm : mangled_tag;
+  free(dm);
+  const size_t amp = name.find('&');
+  if (amp != std::string::npos) {
+    name = name.substr(amp + 1);
+    if (name[0] == '(' && name.compare(0, 11, "(anonymous ") != 0) name = name.substr(1);
+    if (name.compare(0, 5, "void ") == 0) name = name.substr(5);
+    int depth = 0;
+    for (size_t i = 0; i < name.size(); i++) {
+      if (name[i] == '<') depth++;
+      else if (name[i] == '>') { if (--depth < 0) { name.resize(i); break; } }   // (a kernel that is no template: no argument list)
+      else if (name[i] == '(' && depth == 0 && name.compare(i, 11, "(anonymous ") != 0) { name.resize(i); break; }
+    }
+  }
+  fprintf(f, "launch %s grid=%u block=%u s%d\n", name.c_str(), grid.x * grid.y * grid.z, block.x * block.y * block.z,
+          Trace::id_of(g_trace.streams, stream));
+}
+void trace_event(const char* what, const void* event, const void* stream) {
+  FILE* f = g_trace.file();
+  if (!f) return;
+  const int s = Trace::id_of(g_trace.streams, stream);
+  fprintf(f, "%s e%d s%d\n", what, Trace::id_of(g_trace.events, event), s);
+}
+void trace_copy(const char* what, size_t bytes, const void* stream) {
+  FILE* f = g_trace.file();
+  if (f) fprintf(f, "%s %zu s%d\n", what, bytes, Trace::id_of(g_trace.streams, stream));
+}
+
 }  // namespace wavesim
+
+extern "C" void wavesim_trace_begin(const char* label) {
+  FILE* f = wavesim::g_trace.file();
+  if (!f) return;
+  wavesim::g_trace.streams.clear();
+  wavesim::g_trace.events.clear();
+  fprintf(f, "## %s\n", label);
+  fflush(f);
+}

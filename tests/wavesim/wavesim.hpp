@@ -46,4 +46,19 @@ uint64_t collective(Kind kind, const void* site, uint32_t val, uint32_t arg, uin
 // Runs kernel body `fn` for grid x block work-items (blocks are spread over a few OS threads).
 void launch(Dim3 grid, Dim3 block, const std::function<void()>& fn);
 
+// ---- launch trace: what the host code enqueues, one text line per enqueue (hip/hip_runtime.h calls these).
+// On only while the environment variable WAVESIM_TRACE names an output file.  Streams and events are numbered
+// by first appearance since the last wavesim_trace_begin(), which the driving script calls in front of every
+// rp_step / rp_forward (tests/wavesim/launch_trace.py).
+//   WAVESIM_SKIP_KERNELS=1  kernels are traced but not executed (a 4096-env engine costs only its allocation)
+//   WAVESIM_CAPTURING=1     hipStreamIsCapturing reports an active capture
+//   WAVESIM_DEVICE_PTRS=1   hipPointerGetAttributes reports device memory (rp_step_masked wants a device mask)
+bool trace_on();
+bool switch_on(const char* name);   // the environment variable `name` is set and does not start with '0'
+void trace_launch(const char* mangled_tag, Dim3 grid, Dim3 block, const void* stream);   // (ws_kernel_name<kernel>())
+void trace_event(const char* what, const void* event, const void* stream);   // what: "record" / "wait"
+void trace_copy(const char* what, size_t bytes, const void* stream);         // what: "memcpy" / "memset"
+
 }  // namespace wavesim
+
+extern "C" void wavesim_trace_begin(const char* label);   // writes "## label", restarts the numbering
