@@ -90,6 +90,10 @@ def main() -> None:
     ap.add_argument("--video", action="store_true",
                     help="with --record: film env 0 as well (PianoSoundVideoWrapper) and write an AVI file with picture and sound")
     ap.add_argument("--record_dir", default="recordings")
+    ap.add_argument("--train-ppo", type=int, default=0, metavar="UPDATES",
+                    help="train a policy with learning.PPO for that many updates instead of stepping a fixed one; prints the "
+                         "mean episode return per update and the F1 of the trained policy at the end")
+    ap.add_argument("--time-limit", type=float, default=None, help="--train-ppo: stop after that many seconds")
     args = ap.parse_args()
     if args.video and not args.record:
         ap.error("--video needs --record")
@@ -104,6 +108,14 @@ def main() -> None:
         with warnings.catch_warnings():
             warnings.simplefilter("ignore")
             return _load(args, n_envs)
+
+    if args.train_ppo > 0:
+        if (args.fingertip_pianist or args.plan or args.action_sequence or args.pixels or args.hear or args.record
+                or args.canonicalize):
+            ap.error("--train-ppo trains on the plain environment: it goes with the task flags only")
+        from robopianist_amd import learning
+        learning.train_and_evaluate(load(args.n_envs), args.train_ppo, time_limit=args.time_limit, seed=args.seed)
+        return
 
     env = load(args.n_envs)
     pianist = fingertips = None

@@ -22,7 +22,20 @@ def main() -> None:
     ap.add_argument("--control_timestep", type=float, default=0.05)
     ap.add_argument("--n_envs", type=int, default=16)
     ap.add_argument("--precision", type=int, default=64, choices=(32, 64))
+    ap.add_argument("--train-ppo", type=int, default=0, metavar="UPDATES",
+                    help="train a policy with learning.PPO for that many updates instead of playing the oracle policy; "
+                         "prints the mean episode return per update and the F1 of the trained policy at the end")
+    ap.add_argument("--time-limit", type=float, default=None, help="--train-ppo: stop after that many seconds")
     args = ap.parse_args()
+    if args.train_ppo > 0:
+        from robopianist_amd import learning
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            task = SelfActuatedPiano(midi=music.load(args.midi), n_steps_lookahead=1,
+                                     control_timestep=args.control_timestep)
+            env = environment.Environment(task, n_envs=args.n_envs, precision=args.precision)
+        learning.train_and_evaluate(env, args.train_ppo, time_limit=args.time_limit)
+        return
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")
         task = SelfActuatedPiano(midi=music.load(args.midi), n_steps_lookahead=1,
