@@ -25,16 +25,25 @@ def main() -> None:
     ap.add_argument("--train-ppo", type=int, default=0, metavar="UPDATES",
                     help="train a policy with learning.PPO for that many updates instead of playing the oracle policy; "
                          "prints the mean episode return per update and the F1 of the trained policy at the end")
-    ap.add_argument("--time-limit", type=float, default=None, help="--train-ppo: stop after that many seconds")
+    ap.add_argument("--train-sac", type=int, default=0, metavar="ROUNDS",
+                    help="train a policy with offpolicy.SAC for that many rounds (16 control steps and 4 gradient steps "
+                         "each) instead; prints the same lines and the F1 of the trained policy at the end")
+    ap.add_argument("--time-limit", type=float, default=None, help="--train-ppo, --train-sac: stop after that many seconds")
     args = ap.parse_args()
-    if args.train_ppo > 0:
-        from robopianist_amd import learning
+    if args.train_ppo > 0 and args.train_sac > 0:
+        ap.error("--train-ppo and --train-sac are two learners: choose one")
+    if args.train_ppo > 0 or args.train_sac > 0:
+        from robopianist_amd import learning, offpolicy
         with warnings.catch_warnings():
             warnings.simplefilter("ignore")
             task = SelfActuatedPiano(midi=music.load(args.midi), n_steps_lookahead=1,
                                      control_timestep=args.control_timestep)
             env = environment.Environment(task, n_envs=args.n_envs, precision=args.precision)
-        learning.train_and_evaluate(env, args.train_ppo, time_limit=args.time_limit)
+        if args.train_sac > 0:
+            offpolicy.train_and_evaluate(env, args.train_sac, time_limit=args.time_limit,
+                                         batch_size=min(4096, 16 * args.n_envs))
+        else:
+            learning.train_and_evaluate(env, args.train_ppo, time_limit=args.time_limit)
         return
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")

@@ -1,0 +1,322 @@
+// rp_sac.hip -- librp_sac.so: the kernels of the on-device off-policy learner (include/learn/rp_sac.h).
+//
+// One launch per call:
+//   rp_sac_sample_kernel   grid (row), one wave: the wave draws up to RP_SAC_SAMPLE_TRIES transitions (every lane the
+//                          same Philox words and the same two step types: wave-uniform), then copies the winner's two obs
+//                          rows and its action row out of the ring in the widest unit both rows allow, as
+//                          rp_learn_pack_kernel does; a row without a valid attempt is zeroed.
+//   rp_sac_act_kernel      grid (row tile), four waves: the tile of rp_mlp_tile.hpp on the actor D -> H1 -> H2 -> 2 A, then
+//                          the squashed Gaussian's epilogue with the planner's noise.
+//   rp_sac_target_kernel   grid (row tile), four waves: the same tile on each target critic in turn, the first layer
+//                          reading cat([normalised next obs, action]); the running minimum of the tile's 16 rows stays
+//                          in LDS, so the ensemble needs neither atomics nor a second launch.
+// Resources (gfx950, -O3 -ffp-contract=on, the compiler's kernel-resource-usage remark): sample 14 VGPRs, no LDS; act
+// 178 VGPRs + 16 AGPRs, 0 scratch, 53,632 bytes of LDS (rp_learn_act_kernel's figures: two workgroups per CU); target 256
+// VGPRs + 72 AGPRs, 0 scratch, 53,696 bytes (the learner's three arrays and 64 bytes of minima): one workgroup per CU,
+// which is what the 256 tiles of a 4096-row batch occupy anyway.  Measured at 4096 rows, D = 1130, 256 x 256 hidden units,
+// 45 actions, two critics (profiles/sac_bench.json): sample 20.6 us, act + target 660 us.
+#include <hip/hip_runtime.h>
+
+#include <math.h>
+#include <string.h>
+
+#include <string>
+
+#include "rp_sac.hpp"
+#include "rp_mlp_tile.hpp"
+
+namespace {
+
+thread_local std::string g_err;
+int fail(const std::string& s) { g_err = s; return -1; }
+#define HIP_OK(x)                                                                  \
+  do {                                                                             \
+    hipError_t e_ = (x);                                                           \
+    if (e_ != hipSuccess)                                                          \
+      return fail(std::string(#x) + ": " + hipGetErrorString(e_));                 \
+  } while (0)
+
+// ---- sample ----------------------------------------------------------------------------------------------------------
+// Copies the `width` floats of row s into row d, one wave: where the two addresses agree modulo 16 (8) bytes, single
+// floats up to the first boundary, units of 16 (8) bytes from there, single floats for the rest.
+template <typename U>
+__device__ inline int rps_copy_units(const float* s, float* d, int from, int width) {
+  constexpr int per = (int)(sizeof(U) / sizeof(float));
+  const int n = (width - from) / per;
+  const U* su = reinterpret_cast<const U*>(s + from);
+  U* du = reinterpret_cast<U*>(d + from);
+  for (int i = threadIdx.x; i < n; i += RPL_WAVE) du[i] = su[i];
+  return from + n * per;
+}
+
+__device__ inline int rps_head(uintptr_t a, int unit, int width) {
+  const int h = (int)(((uintptr_t)unit - (a & (uintptr_t)(unit - 1))) & (uintptr_t)(unit - 1)) >> 2;
+  return h < width ? h : width;
+}
+
+__device__ inline void rps_copy_row(const float* s, float* d, int width) {
+  const uintptr_t sa = reinterpret_cast<uintptr_t>(s), da = reinterpret_cast<uintptr_t>(d);
+  const int lane = (int)threadIdx.x;
+  int head = 0, done = 0;
+  if (((sa ^ da) & 15) == 0) {
+    head = rps_head(sa, 16, width);
+    done = rps_copy_units<uint4>(s, d, head, width);
+  } else if (((sa ^ da) & 7) == 0) {
+    head = rps_head(sa, 8, width);
+    done = rps_copy_units<uint2>(s, d, head, width);
+  }
+  if (lane < head) d[lane] = s[lane];                                     // (head <= 3)
+  for (int i = done + lane; i < width; i += RPL_WAVE) d[i] = s[i];        // (the tail: < 4 floats, or all)
+}
+
+__device__ inline void rps_zero_row(float* d, int width) {
+  for (int i = (int)threadIdx.x; i < width; i += RPL_WAVE) d[i] = 0.f;
+}
+
+__global__ __launch_bounds__(RPL_WAVE) void rp_sac_sample_kernel(const rp_sac_sample_args a) {
+  const long long b = (long long)a.row_first + blockIdx.x;
+  const long long C = a.C, E = a.E;
+  const long long F = a.n_written < C ? a.n_written : C;
+  const uint64_t N = (uint64_t)((F - 1) * E);   // (< 2^32, checked)
+  long long slot = -1, next = -1, e = 0;
+  for (uint32_t j = 0; j < RP_SAC_SAMPLE_TRIES; ++j) {
+    const uint32_t w = rppl_philox(a.round, (uint32_t)b, 0u, 16u + j, a.seed_lo, a.seed_hi).w[0];
+    const uint64_t i = ((uint64_t)w * N) >> 32;   // (< N)
+    const long long t = (long long)(i / (uint64_t)E);
+    const long long ee = (long long)(i % (uint64_t)E);
+    const long long m = a.n_written - F + t;      // (<= n_written - 2)
+    const long long s0 = m % C, s1 = (m + 1) % C;
+    const int st0 = a.ring_step_type[s0 * E + ee], st1 = a.ring_step_type[s1 * E + ee];
+    if (st0 != RP_LEARN_STEP_LAST && st1 != RP_LEARN_STEP_FIRST) {   // (wave-uniform)
+      slot = s0; next = s1; e = ee;
+      break;
+    }
+  }
+  float* obs = a.obs + b * a.D;
+  float* nobs = a.next_obs + b * a.D;
+  float* act = a.action + b * a.A;
+  if (slot < 0) {
+    rps_zero_row(obs, a.D);
+    rps_zero_row(nobs, a.D);
+    rps_zero_row(act, a.A);
+    if (threadIdx.x == 0) {
+      a.reward[b] = 0.f;
+      a.discount[b] = 0.f;
+      a.mask[b] = 0.f;
+      if (a.index) a.index[b] = -1;
+    }
+    return;
+  }
+  const long long r0 = slot * E + e, r1 = next * E + e;
+  rps_copy_row(a.ring_obs + r0 * a.D, obs, a.D);
+  rps_copy_row(a.ring_obs + r1 * a.D, nobs, a.D);
+  rps_copy_row(a.ring_action + r0 * a.A, act, a.A);
+  if (threadIdx.x == 0) {
+    a.reward[b] = a.ring_reward[r1];
+    a.discount[b] = a.ring_discount[r1];
+    a.mask[b] = 1.f;
+    if (a.index) a.index[b] = (int32_t)r0;
+  }
+}
+
+// ---- act -------------------------------------------------------------------------------------------------------------
+struct RpsActor {
+  rp_learn_mlp net;
+  float logp_const;   // (float)(0.5 A ln 2 pi)
+  float ln2;          // (float)ln 2
+};
+
+__global__ __launch_bounds__(RPL_BLOCK) void rp_sac_act_kernel(const rp_sac_act_args a, const RpsActor actor) {
+  __shared__ float sa[RPL_TILE_R * RPL_S_PITCH];        // the staged input: [row][k]
+  __shared__ float sw[RP_LEARN_MAX_H * RPL_S_PITCH];    // the staged weights: [out][k]; the epilogue's log-probability terms
+  __shared__ float sh[RPL_TILE_R * RPL_H_PITCH];        // the tile's activations: [row][unit]
+  const int tid = (int)threadIdx.x;
+  const rp_learn_mlp net = actor.net;
+  const int A = a.A, N3 = 2 * a.A;
+  const long long e0 = (long long)a.row_first + (long long)blockIdx.x * RPL_TILE_R;
+  const long long e_end = (long long)a.row_first + a.row_count;
+  f32x4 acc[RPL_ACC];
+  const float clip = a.obs_clip, nclip = -a.obs_clip;
+  rpl_layer(
+      [&](int r, int k) {
+        const long long e = e0 + r;
+        if (e >= e_end) return 0.f;
+        const float x = a.obs[(size_t)e * a.D + k];
+        const float d = x - a.mean[k];
+        const float p = d * a.inv_std[k];
+        const float lo = fmaxf(p, nclip);
+        return fminf(lo, clip);
+      },
+      a.D, net.w1, a.H1, sa, sw, acc);
+  rpl_store_layer<true>(acc, net.b1, a.H1, sh);
+  rpl_layer([&](int r, int k) { return sh[r * RPL_H_PITCH + k]; }, a.H1, net.w2, a.H2, sa, sw, acc);
+  rpl_store_layer<true>(acc, net.b2, a.H2, sh);
+  rpl_layer([&](int r, int k) { return sh[r * RPL_H_PITCH + k]; }, a.H2, net.w3, N3, sa, sw, acc);
+  rpl_store_layer<false>(acc, net.b3, N3, sh);
+  float* sg = sw;   // [row][RP_LEARN_MAX_A]: the terms of the log-probability (the weight stage is dead)
+  for (int idx = tid; idx < RPL_TILE_R * A; idx += RPL_BLOCK) {
+    const int r = idx / A, u = idx - r * A;
+    const long long e = e0 + r;
+    if (e >= e_end) continue;
+    const float m = sh[r * RPL_H_PITCH + u];
+    float p = m;
+    if (!a.deterministic) {
+      const float l = sh[r * RPL_H_PITCH + A + u];
+      const float lc = fmaxf(l, a.log_std_min);
+      const float ls = fminf(lc, a.log_std_max);
+      const float zf = (float)rppl_z(a.seed_lo, a.seed_hi, a.round, (uint32_t)e, (uint32_t)u);
+      const float sd = expf(ls);
+      const float t = sd * zf;
+      p = m + t;
+      const float w = -2.f * p;
+      const float aw = fabsf(w);
+      const float ex = expf(-aw);
+      const float l1 = log1pf(ex);
+      const float wp = fmaxf(w, 0.f);
+      const float sp = wp + l1;
+      const float c1 = actor.ln2 - p;
+      const float c2 = c1 - sp;
+      const float lg = 2.f * c2;
+      const float q = zf * zf;
+      const float h = -0.5f * q;
+      const float g0 = h - ls;
+      sg[r * RP_LEARN_MAX_A + u] = g0 - lg;
+    }
+    const float act = tanhf(p);
+    const size_t o = (size_t)e * A + u;
+    a.action[o] = act;
+    if (a.pre) a.pre[o] = p;
+    if (a.env_action) {
+      if (a.precision == 32) static_cast<float*>(a.env_action)[o] = act;
+      else static_cast<double*>(a.env_action)[o] = (double)act;
+    }
+  }
+  if (a.deterministic) return;   // (block-uniform)
+  __syncthreads();
+  if (tid < RPL_TILE_R && e0 + tid < e_end) {
+    float s = 0.f;
+    for (int u = 0; u < A; u++) s = s + sg[tid * RP_LEARN_MAX_A + u];
+    a.logp[e0 + tid] = s - actor.logp_const;
+  }
+}
+
+// ---- target ----------------------------------------------------------------------------------------------------------
+struct RpsCritics {
+  rp_learn_mlp net[RP_SAC_MAX_CRITICS];
+};
+
+__global__ __launch_bounds__(RPL_BLOCK) void rp_sac_target_kernel(const rp_sac_target_args a, const RpsCritics critics) {
+  __shared__ float sa[RPL_TILE_R * RPL_S_PITCH];
+  __shared__ float sw[RP_LEARN_MAX_H * RPL_S_PITCH];
+  __shared__ float sh[RPL_TILE_R * RPL_H_PITCH];
+  __shared__ float sq[RPL_TILE_R];                      // the running minimum over the critics, per row
+  const int tid = (int)threadIdx.x;
+  const int D = a.D, A = a.A;
+  const long long e0 = (long long)a.row_first + (long long)blockIdx.x * RPL_TILE_R;
+  const long long e_end = (long long)a.row_first + a.row_count;
+  f32x4 acc[RPL_ACC];
+  const float clip = a.obs_clip, nclip = -a.obs_clip;
+#pragma unroll 1
+  for (int i = 0; i < a.n_critics; ++i) {   // (block-uniform)
+    const rp_learn_mlp net = critics.net[i];
+    rpl_layer(
+        [&](int r, int k) {
+          const long long e = e0 + r;
+          if (e >= e_end) return 0.f;
+          if (k >= D) return a.action[(size_t)e * A + (k - D)];
+          const float x = a.next_obs[(size_t)e * D + k];
+          const float d = x - a.mean[k];
+          const float p = d * a.inv_std[k];
+          const float lo = fmaxf(p, nclip);
+          return fminf(lo, clip);
+        },
+        D + A, net.w1, a.H1, sa, sw, acc);
+    rpl_store_layer<true>(acc, net.b1, a.H1, sh);
+    rpl_layer([&](int r, int k) { return sh[r * RPL_H_PITCH + k]; }, a.H1, net.w2, a.H2, sa, sw, acc);
+    rpl_store_layer<true>(acc, net.b2, a.H2, sh);
+    rpl_layer([&](int r, int k) { return sh[r * RPL_H_PITCH + k]; }, a.H2, net.w3, 1, sa, sw, acc);
+    rpl_store_layer<false>(acc, net.b3, 1, sh);
+    // (thread r alone reads and writes sq[r]; sh[r][0] is rewritten only behind the next layers' barriers)
+    if (tid < RPL_TILE_R) {
+      const float q = sh[tid * RPL_H_PITCH];
+      sq[tid] = i == 0 ? q : fminf(sq[tid], q);
+    }
+  }
+  if (tid < RPL_TILE_R && e0 + tid < e_end) {
+    const long long e = e0 + tid;
+    const float qm = sq[tid];
+    const float al = expf(*a.log_alpha);
+    const float s = al * a.logp[e];
+    const float v = qm - s;
+    const float nv = a.gamma * a.discount[e];
+    const float tv = nv * v;
+    a.y[e] = a.reward[e] + tv;
+    if (a.q_min) a.q_min[e] = qm;
+  }
+}
+
+unsigned blocks_for(long long total, int per) { return (unsigned)((total + per - 1) / per); }
+
+}  // namespace
+
+#define RPS_HEAD(fn, type)                                                                          \
+  if (!a) return fail(fn ": args is NULL");                                                         \
+  if (a->struct_size != sizeof(type)) return fail(fn ": struct_size does not match this library's " #type)
+#define RPS_CHECK(expr)                                   \
+  do {                                                    \
+    const std::string err_ = (expr);                      \
+    if (!err_.empty()) return fail(err_);                 \
+  } while (0)
+
+extern "C" {
+
+const char* rp_sac_last_error(void) { return g_err.c_str(); }
+
+int rp_sac_dim(const char* name) {
+  if (!name) return -1;
+  if (!strcmp(name, "max_critics")) return RP_SAC_MAX_CRITICS;
+  if (!strcmp(name, "sample_tries")) return RP_SAC_SAMPLE_TRIES;
+  if (!strcmp(name, "tile_rows")) return RPL_TILE_R;
+  if (!strcmp(name, "max_hidden")) return RP_LEARN_MAX_H;
+  if (!strcmp(name, "max_actions")) return RP_SAC_MAX_HEAD / 2;
+  return -1;
+}
+
+int rp_sac_sample(const rp_sac_sample_args* a) {
+  RPS_HEAD("rp_sac_sample", rp_sac_sample_args);
+  RPS_CHECK(rps_check_sample(a));
+  if (a->row_count == 0) return 0;
+  hipLaunchKernelGGL(rp_sac_sample_kernel, dim3((unsigned)a->row_count), dim3(RPL_WAVE), 0, (hipStream_t)a->hip_stream, *a);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
+int rp_sac_act(const rp_sac_act_args* a) {
+  RPS_HEAD("rp_sac_act", rp_sac_act_args);
+  RPS_CHECK(rps_check_act(a));
+  if (a->row_count == 0) return 0;
+  RpsActor actor;
+  memset(&actor, 0, sizeof(actor));
+  actor.net = *a->actor;
+  actor.logp_const = (float)(0.5 * (double)a->A * 1.8378770664093453);   // ln 2 pi
+  actor.ln2 = (float)0.6931471805599453;
+  hipLaunchKernelGGL(rp_sac_act_kernel, dim3(blocks_for(a->row_count, RPL_TILE_R)), dim3(RPL_BLOCK), 0,
+                     (hipStream_t)a->hip_stream, *a, actor);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
+int rp_sac_target(const rp_sac_target_args* a) {
+  RPS_HEAD("rp_sac_target", rp_sac_target_args);
+  RPS_CHECK(rps_check_target(a));
+  if (a->row_count == 0) return 0;
+  RpsCritics critics;
+  memset(&critics, 0, sizeof(critics));
+  for (int i = 0; i < a->n_critics; ++i) critics.net[i] = a->critics[i];
+  hipLaunchKernelGGL(rp_sac_target_kernel, dim3(blocks_for(a->row_count, RPL_TILE_R)), dim3(RPL_BLOCK), 0,
+                     (hipStream_t)a->hip_stream, *a, critics);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
+}  // extern "C"
