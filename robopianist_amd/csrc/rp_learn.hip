@@ -27,19 +27,11 @@
 
 #include <string>
 
+#include "rp_abi_host.hpp"
 #include "rp_learn.hpp"
 #include "rp_mlp_tile.hpp"
 
 namespace {
-
-thread_local std::string g_err;
-int fail(const std::string& s) { g_err = s; return -1; }
-#define HIP_OK(x)                                                                  \
-  do {                                                                             \
-    hipError_t e_ = (x);                                                           \
-    if (e_ != hipSuccess)                                                          \
-      return fail(std::string(#x) + ": " + hipGetErrorString(e_));                 \
-  } while (0)
 
 // ---- pack ------------------------------------------------------------------------------------------------------------
 struct RplField {
@@ -49,23 +41,6 @@ struct RplField {
 struct RplFieldTable {
   RplField f[RP_LEARN_MAX_FIELDS];
 };
-
-// Copies floats [from, width) of a row in units of U (whole units only); returns the first float it left.
-template <typename U>
-__device__ inline int rpl_copy_units(const float* s, float* d, int from, int width) {
-  constexpr int per = (int)(sizeof(U) / sizeof(float));
-  const int n = (width - from) / per;
-  const U* su = reinterpret_cast<const U*>(s + from);
-  U* du = reinterpret_cast<U*>(d + from);
-  for (int i = threadIdx.x; i < n; i += RPL_WAVE) du[i] = su[i];
-  return from + n * per;
-}
-
-// The floats in front of the first address that is a multiple of `unit` bytes (a is 4-aligned), at most `width`.
-__device__ inline int rpl_head(uintptr_t a, int unit, int width) {
-  const int h = (int)(((uintptr_t)unit - (a & (uintptr_t)(unit - 1))) & (uintptr_t)(unit - 1)) >> 2;
-  return h < width ? h : width;
-}
 
 template <typename T>
 __device__ inline void rpl_pack_meta(const rp_learn_pack_args& a, long long e) {
@@ -108,7 +83,8 @@ __global__ __launch_bounds__(RPL_WAVE) void rp_learn_pack_kernel(const RplFieldT
   const int lane = (int)threadIdx.x;
   if (f.dtype == RP_LEARN_F32) {
     // rows whose addresses agree modulo 16 (or 8) bytes: single floats up to the first 16- (8-) byte boundary, whole
-    // units from there, single floats for the rest
+    // units from there, single floats for the rest (rpl_copy_row of rp_mlp_tile.hpp, written out: through the call
+    // the kernel is two instructions longer)
     const float* s = static_cast<const float*>(f.src) + e * f.width;
     const uintptr_t sa = reinterpret_cast<uintptr_t>(s);
     int head = 0, done = 0;
@@ -314,18 +290,7 @@ __global__ __launch_bounds__(RPL_MOMENT_COLS * RPL_MOMENT_LANES) void rp_learn_m
   a.inv_std_f32[j] = (float)inv;
 }
 
-unsigned blocks_for(long long total, int per) { return (unsigned)((total + per - 1) / per); }
-
 }  // namespace
-
-#define RPL_HEAD(fn, type)                                                                          \
-  if (!a) return fail(fn ": args is NULL");                                                         \
-  if (a->struct_size != sizeof(type)) return fail(fn ": struct_size does not match this library's " #type)
-#define RPL_CHECK(expr)                                   \
-  do {                                                    \
-    const std::string err_ = (expr);                      \
-    if (!err_.empty()) return fail(err_);                 \
-  } while (0)
 
 extern "C" {
 
@@ -345,8 +310,8 @@ int rp_learn_dim(const char* name) {
 }
 
 int rp_learn_pack(const rp_learn_pack_args* a) {
-  RPL_HEAD("rp_learn_pack", rp_learn_pack_args);
-  RPL_CHECK(rpl_check_pack(a));
+  RP_ARGS_HEAD("rp_learn_pack", rp_learn_pack_args);
+  RP_ARGS_CHECK(rpl_check_pack(a));
   if (a->env_count == 0) return 0;
   RplFieldTable tab;
   memset(&tab, 0, sizeof(tab));
@@ -366,8 +331,8 @@ int rp_learn_pack(const rp_learn_pack_args* a) {
 }
 
 int rp_learn_act(const rp_learn_act_args* a) {
-  RPL_HEAD("rp_learn_act", rp_learn_act_args);
-  RPL_CHECK(rpl_check_act(a));
+  RP_ARGS_HEAD("rp_learn_act", rp_learn_act_args);
+  RP_ARGS_CHECK(rpl_check_act(a));
   if (a->row_count == 0) return 0;
   RplNets nets;
   memset(&nets, 0, sizeof(nets));
@@ -382,8 +347,8 @@ int rp_learn_act(const rp_learn_act_args* a) {
 }
 
 int rp_learn_gae(const rp_learn_gae_args* a) {
-  RPL_HEAD("rp_learn_gae", rp_learn_gae_args);
-  RPL_CHECK(rpl_check_gae(a));
+  RP_ARGS_HEAD("rp_learn_gae", rp_learn_gae_args);
+  RP_ARGS_CHECK(rpl_check_gae(a));
   if (a->env_count == 0) return 0;
   hipLaunchKernelGGL(rp_learn_gae_kernel, dim3(blocks_for(a->env_count, RPL_BLOCK)), dim3(RPL_BLOCK), 0,
                      (hipStream_t)a->hip_stream, *a);
@@ -392,8 +357,8 @@ int rp_learn_gae(const rp_learn_gae_args* a) {
 }
 
 int rp_learn_moments(const rp_learn_moments_args* a) {
-  RPL_HEAD("rp_learn_moments", rp_learn_moments_args);
-  RPL_CHECK(rpl_check_moments(a));
+  RP_ARGS_HEAD("rp_learn_moments", rp_learn_moments_args);
+  RP_ARGS_CHECK(rpl_check_moments(a));
   hipLaunchKernelGGL(rp_learn_moments_kernel, dim3(blocks_for(a->D, RPL_MOMENT_COLS)), dim3(RPL_MOMENT_COLS * RPL_MOMENT_LANES),
                      0, (hipStream_t)a->hip_stream, *a);
   HIP_OK(hipGetLastError());

@@ -1,5 +1,6 @@
 // rp_mlp_tile.hpp -- the 16-row MFMA multilayer-perceptron tile in LDS, shared by the kernels of librp_learn.so
-// (rp_learn.hip: the PPO policy) and of librp_sac.so (rp_sac.hip: the SAC policy and TD target).
+// (rp_learn.hip: the PPO policy) and of librp_sac.so (rp_sac.hip: the SAC policy and TD target), and the one-wave row
+// copy: rp_sac_sample_kernel's rows through rpl_copy_row, rp_learn_pack_kernel's float32 fields through its parts.
 //
 // A workgroup of RPL_BLOCK = 256 threads (four waves) owns RPL_TILE_R = 16 rows.  A layer runs on
 // v_mfma_f32_16x16x4_f32; both operands go through LDS RPL_TK = 32 k at a time (the caller's `sa` [16][RPL_S_PITCH] and
@@ -85,6 +86,41 @@ __device__ inline void rpl_store_layer(const f32x4 (&acc)[RPL_ACC], const float*
     }
   }
   __syncthreads();
+}
+
+// ---- the aligned row copy of one wave (RPL_WAVE lanes): the sampler's rows, and the parts of the pack kernel's copy ------
+// Copies floats [from, width) of a row in units of U (whole units only); returns the first float it left.
+template <typename U>
+__device__ inline int rpl_copy_units(const float* s, float* d, int from, int width) {
+  constexpr int per = (int)(sizeof(U) / sizeof(float));
+  const int n = (width - from) / per;
+  const U* su = reinterpret_cast<const U*>(s + from);
+  U* du = reinterpret_cast<U*>(d + from);
+  for (int i = threadIdx.x; i < n; i += RPL_WAVE) du[i] = su[i];
+  return from + n * per;
+}
+
+// The floats in front of the first address that is a multiple of `unit` bytes (a is 4-aligned), at most `width`.
+__device__ inline int rpl_head(uintptr_t a, int unit, int width) {
+  const int h = (int)(((uintptr_t)unit - (a & (uintptr_t)(unit - 1))) & (uintptr_t)(unit - 1)) >> 2;
+  return h < width ? h : width;
+}
+
+// Copies the `width` floats of row s into row d: where the two addresses agree modulo 16 (8) bytes, single floats up to
+// the first 16- (8-) byte boundary, whole units from there, single floats for the rest.
+__device__ inline void rpl_copy_row(const float* s, float* d, int width) {
+  const uintptr_t sa = reinterpret_cast<uintptr_t>(s), da = reinterpret_cast<uintptr_t>(d);
+  const int lane = (int)threadIdx.x;
+  int head = 0, done = 0;
+  if (((sa ^ da) & 15) == 0) {
+    head = rpl_head(sa, 16, width);
+    done = rpl_copy_units<uint4>(s, d, head, width);
+  } else if (((sa ^ da) & 7) == 0) {
+    head = rpl_head(sa, 8, width);
+    done = rpl_copy_units<uint2>(s, d, head, width);
+  }
+  if (lane < head) d[lane] = s[lane];                                     // (head <= 3)
+  for (int i = done + lane; i < width; i += RPL_WAVE) d[i] = s[i];        // (the tail: < 4 floats, or all)
 }
 
 }  // namespace

@@ -14,18 +14,10 @@
 
 #include <string>
 
+#include "rp_abi_host.hpp"
 #include "rp_plan.hpp"
 
 namespace {
-
-thread_local std::string g_err;
-int fail(const std::string& s) { g_err = s; return -1; }
-#define HIP_OK(x)                                                                  \
-  do {                                                                             \
-    hipError_t e_ = (x);                                                           \
-    if (e_ != hipSuccess)                                                          \
-      return fail(std::string(#x) + ": " + hipGetErrorString(e_));                 \
-  } while (0)
 
 #define RPPL_BLOCK 256
 
@@ -154,18 +146,7 @@ __global__ __launch_bounds__(RPPL_BLOCK) void rp_plan_shift_kernel(const rp_plan
   }
 }
 
-unsigned blocks_for(long long total) { return (unsigned)((total + RPPL_BLOCK - 1) / RPPL_BLOCK); }
-
 }  // namespace
-
-#define RPPL_HEAD(fn, type)                                                                          \
-  if (!a) return fail(fn ": args is NULL");                                                          \
-  if (a->struct_size != sizeof(type)) return fail(fn ": struct_size does not match this library's " #type)
-#define RPPL_CHECK(expr)                                  \
-  do {                                                    \
-    const std::string err_ = (expr);                      \
-    if (!err_.empty()) return fail(err_);                 \
-  } while (0)
 
 extern "C" {
 
@@ -179,12 +160,12 @@ int rp_plan_dim(const char* name) {
 }
 
 int rp_plan_fork(const rp_plan_fork_args* a) {
-  RPPL_HEAD("rp_plan_fork", rp_plan_fork_args);
+  RP_ARGS_HEAD("rp_plan_fork", rp_plan_fork_args);
   if (!a->fields) return fail("rp_plan_fork: fields is NULL");
   if (a->n_fields < 1 || a->n_fields > RP_PLAN_MAX_FIELDS)
     return fail("rp_plan_fork: n_fields must be 1 .. " + std::to_string(RP_PLAN_MAX_FIELDS) + ", got " + std::to_string(a->n_fields));
-  RPPL_CHECK(rppl_check_layout("rp_plan_fork", a->G, a->K, 1, 1));
-  RPPL_CHECK(rppl_check_range("rp_plan_fork", "the row range", (long long)a->G * a->K, a->env_first, a->env_count));
+  RP_ARGS_CHECK(rppl_check_layout("rp_plan_fork", a->G, a->K, 1, 1));
+  RP_ARGS_CHECK(rppl_check_range("rp_plan_fork", "the row range", (long long)a->G * a->K, a->env_first, a->env_count));
   RpplFieldTable tab;
   memset(&tab, 0, sizeof(tab));
   for (int i = 0; i < a->n_fields; ++i) {
@@ -201,57 +182,57 @@ int rp_plan_fork(const rp_plan_fork_args* a) {
 }
 
 int rp_plan_sample(const rp_plan_sample_args* a) {
-  RPPL_HEAD("rp_plan_sample", rp_plan_sample_args);
+  RP_ARGS_HEAD("rp_plan_sample", rp_plan_sample_args);
   if (!a->nominal || !a->sigma || !a->lo || !a->hi || !a->knots) return fail("rp_plan_sample: a pointer is NULL");
-  RPPL_CHECK(rppl_check_layout("rp_plan_sample", a->G, a->K, a->P, a->nu));
-  RPPL_CHECK(rppl_check_range("rp_plan_sample", "the row range", (long long)a->G * a->K, a->env_first, a->env_count));
+  RP_ARGS_CHECK(rppl_check_layout("rp_plan_sample", a->G, a->K, a->P, a->nu));
+  RP_ARGS_CHECK(rppl_check_range("rp_plan_sample", "the row range", (long long)a->G * a->K, a->env_first, a->env_count));
   const long long total = (long long)a->env_count * a->P * a->nu;
   if (total == 0) return 0;
   if ((total + RPPL_BLOCK - 1) / RPPL_BLOCK > 0x7fffffffLL) return fail("rp_plan_sample: too many entries for one launch");
-  hipLaunchKernelGGL(rp_plan_sample_kernel, dim3(blocks_for(total)), dim3(RPPL_BLOCK), 0, (hipStream_t)a->hip_stream, *a, total);
+  hipLaunchKernelGGL(rp_plan_sample_kernel, dim3(blocks_for(total, RPPL_BLOCK)), dim3(RPPL_BLOCK), 0, (hipStream_t)a->hip_stream, *a, total);
   HIP_OK(hipGetLastError());
   return 0;
 }
 
 int rp_plan_action(const rp_plan_action_args* a) {
-  RPPL_HEAD("rp_plan_action", rp_plan_action_args);
+  RP_ARGS_HEAD("rp_plan_action", rp_plan_action_args);
   if (!a->knots || !a->out) return fail("rp_plan_action: a pointer is NULL");
   if (a->precision != 32 && a->precision != 64) return fail("rp_plan_action: precision must be 32 or 64");
   if (a->nu < 1) return fail("rp_plan_action: nu must be >= 1");
-  RPPL_CHECK(rppl_check_spline("rp_plan_action", a->spline, a->H, a->P));
+  RP_ARGS_CHECK(rppl_check_spline("rp_plan_action", a->spline, a->H, a->P));
   if (a->h < 0 || a->h >= a->H) return fail("rp_plan_action: h must lie in [0, H)");
   if (a->n_rows < 1) return fail("rp_plan_action: n_rows must be >= 1");
-  RPPL_CHECK(rppl_check_range("rp_plan_action", "the row range", a->n_rows, a->row_first, a->row_count));
+  RP_ARGS_CHECK(rppl_check_range("rp_plan_action", "the row range", a->n_rows, a->row_first, a->row_count));
   const long long total = (long long)a->row_count * a->nu;
   if (total == 0) return 0;
   if (a->precision == 32)
-    hipLaunchKernelGGL(rp_plan_action_kernel<float>, dim3(blocks_for(total)), dim3(RPPL_BLOCK), 0, (hipStream_t)a->hip_stream, *a, total);
+    hipLaunchKernelGGL(rp_plan_action_kernel<float>, dim3(blocks_for(total, RPPL_BLOCK)), dim3(RPPL_BLOCK), 0, (hipStream_t)a->hip_stream, *a, total);
   else
-    hipLaunchKernelGGL(rp_plan_action_kernel<double>, dim3(blocks_for(total)), dim3(RPPL_BLOCK), 0, (hipStream_t)a->hip_stream, *a, total);
+    hipLaunchKernelGGL(rp_plan_action_kernel<double>, dim3(blocks_for(total, RPPL_BLOCK)), dim3(RPPL_BLOCK), 0, (hipStream_t)a->hip_stream, *a, total);
   HIP_OK(hipGetLastError());
   return 0;
 }
 
 int rp_plan_accumulate(const rp_plan_accumulate_args* a) {
-  RPPL_HEAD("rp_plan_accumulate", rp_plan_accumulate_args);
+  RP_ARGS_HEAD("rp_plan_accumulate", rp_plan_accumulate_args);
   if (!a->ret || !a->alive || !a->reward || !a->step_type) return fail("rp_plan_accumulate: a pointer is NULL");
   if (a->precision != 32 && a->precision != 64) return fail("rp_plan_accumulate: precision must be 32 or 64");
   if (a->E < 1) return fail("rp_plan_accumulate: E must be >= 1");
-  RPPL_CHECK(rppl_check_range("rp_plan_accumulate", "the row range", a->E, a->env_first, a->env_count));
+  RP_ARGS_CHECK(rppl_check_range("rp_plan_accumulate", "the row range", a->E, a->env_first, a->env_count));
   if (a->env_count == 0) return 0;
   if (a->precision == 32)
-    hipLaunchKernelGGL(rp_plan_accumulate_kernel<float>, dim3(blocks_for(a->env_count)), dim3(RPPL_BLOCK), 0, (hipStream_t)a->hip_stream, *a);
+    hipLaunchKernelGGL(rp_plan_accumulate_kernel<float>, dim3(blocks_for(a->env_count, RPPL_BLOCK)), dim3(RPPL_BLOCK), 0, (hipStream_t)a->hip_stream, *a);
   else
-    hipLaunchKernelGGL(rp_plan_accumulate_kernel<double>, dim3(blocks_for(a->env_count)), dim3(RPPL_BLOCK), 0, (hipStream_t)a->hip_stream, *a);
+    hipLaunchKernelGGL(rp_plan_accumulate_kernel<double>, dim3(blocks_for(a->env_count, RPPL_BLOCK)), dim3(RPPL_BLOCK), 0, (hipStream_t)a->hip_stream, *a);
   HIP_OK(hipGetLastError());
   return 0;
 }
 
 int rp_plan_select(const rp_plan_select_args* a) {
-  RPPL_HEAD("rp_plan_select", rp_plan_select_args);
+  RP_ARGS_HEAD("rp_plan_select", rp_plan_select_args);
   if (!a->ret || !a->knots || !a->nominal || !a->best_k || !a->best_return) return fail("rp_plan_select: a pointer is NULL");
-  RPPL_CHECK(rppl_check_layout("rp_plan_select", a->G, a->K, a->P, a->nu));
-  RPPL_CHECK(rppl_check_range("rp_plan_select", "the group range", a->G, a->group_first, a->group_count));
+  RP_ARGS_CHECK(rppl_check_layout("rp_plan_select", a->G, a->K, a->P, a->nu));
+  RP_ARGS_CHECK(rppl_check_range("rp_plan_select", "the group range", a->G, a->group_first, a->group_count));
   if (a->group_count == 0) return 0;
   hipLaunchKernelGGL(rp_plan_select_kernel, dim3((unsigned)a->group_count), dim3(RPPL_WAVE), 0, (hipStream_t)a->hip_stream, *a);
   HIP_OK(hipGetLastError());
@@ -259,14 +240,14 @@ int rp_plan_select(const rp_plan_select_args* a) {
 }
 
 int rp_plan_shift(const rp_plan_shift_args* a) {
-  RPPL_HEAD("rp_plan_shift", rp_plan_shift_args);
+  RP_ARGS_HEAD("rp_plan_shift", rp_plan_shift_args);
   if (!a->nominal) return fail("rp_plan_shift: nominal is NULL");
-  RPPL_CHECK(rppl_check_layout("rp_plan_shift", a->G, 1, a->P, a->nu));
-  RPPL_CHECK(rppl_check_spline("rp_plan_shift", a->spline, a->H, a->P));
-  RPPL_CHECK(rppl_check_range("rp_plan_shift", "the group range", a->G, a->group_first, a->group_count));
+  RP_ARGS_CHECK(rppl_check_layout("rp_plan_shift", a->G, 1, a->P, a->nu));
+  RP_ARGS_CHECK(rppl_check_spline("rp_plan_shift", a->spline, a->H, a->P));
+  RP_ARGS_CHECK(rppl_check_range("rp_plan_shift", "the group range", a->G, a->group_first, a->group_count));
   const long long total = (long long)a->group_count * a->nu;
   if (total == 0) return 0;
-  hipLaunchKernelGGL(rp_plan_shift_kernel, dim3(blocks_for(total)), dim3(RPPL_BLOCK), 0, (hipStream_t)a->hip_stream, *a, total);
+  hipLaunchKernelGGL(rp_plan_shift_kernel, dim3(blocks_for(total, RPPL_BLOCK)), dim3(RPPL_BLOCK), 0, (hipStream_t)a->hip_stream, *a, total);
   HIP_OK(hipGetLastError());
   return 0;
 }

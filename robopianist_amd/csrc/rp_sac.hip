@@ -3,8 +3,8 @@
 // One launch per call:
 //   rp_sac_sample_kernel   grid (row), one wave: the wave draws up to RP_SAC_SAMPLE_TRIES transitions (every lane the
 //                          same Philox words and the same two step types: wave-uniform), then copies the winner's two obs
-//                          rows and its action row out of the ring in the widest unit both rows allow, as
-//                          rp_learn_pack_kernel does; a row without a valid attempt is zeroed.
+//                          rows and its action row out of the ring in the widest unit both rows allow (rpl_copy_row of
+//                          rp_mlp_tile.hpp, rp_learn_pack_kernel's); a row without a valid attempt is zeroed.
 //   rp_sac_act_kernel      grid (row tile), four waves: the tile of rp_mlp_tile.hpp on the actor D -> H1 -> H2 -> 2 A, then
 //                          the squashed Gaussian's epilogue with the planner's noise.
 //   rp_sac_target_kernel   grid (row tile), four waves: the same tile on each target critic in turn, the first layer
@@ -22,53 +22,13 @@
 
 #include <string>
 
+#include "rp_abi_host.hpp"
 #include "rp_sac.hpp"
 #include "rp_mlp_tile.hpp"
 
 namespace {
 
-thread_local std::string g_err;
-int fail(const std::string& s) { g_err = s; return -1; }
-#define HIP_OK(x)                                                                  \
-  do {                                                                             \
-    hipError_t e_ = (x);                                                           \
-    if (e_ != hipSuccess)                                                          \
-      return fail(std::string(#x) + ": " + hipGetErrorString(e_));                 \
-  } while (0)
-
 // ---- sample ----------------------------------------------------------------------------------------------------------
-// Copies the `width` floats of row s into row d, one wave: where the two addresses agree modulo 16 (8) bytes, single
-// floats up to the first boundary, units of 16 (8) bytes from there, single floats for the rest.
-template <typename U>
-__device__ inline int rps_copy_units(const float* s, float* d, int from, int width) {
-  constexpr int per = (int)(sizeof(U) / sizeof(float));
-  const int n = (width - from) / per;
-  const U* su = reinterpret_cast<const U*>(s + from);
-  U* du = reinterpret_cast<U*>(d + from);
-  for (int i = threadIdx.x; i < n; i += RPL_WAVE) du[i] = su[i];
-  return from + n * per;
-}
-
-__device__ inline int rps_head(uintptr_t a, int unit, int width) {
-  const int h = (int)(((uintptr_t)unit - (a & (uintptr_t)(unit - 1))) & (uintptr_t)(unit - 1)) >> 2;
-  return h < width ? h : width;
-}
-
-__device__ inline void rps_copy_row(const float* s, float* d, int width) {
-  const uintptr_t sa = reinterpret_cast<uintptr_t>(s), da = reinterpret_cast<uintptr_t>(d);
-  const int lane = (int)threadIdx.x;
-  int head = 0, done = 0;
-  if (((sa ^ da) & 15) == 0) {
-    head = rps_head(sa, 16, width);
-    done = rps_copy_units<uint4>(s, d, head, width);
-  } else if (((sa ^ da) & 7) == 0) {
-    head = rps_head(sa, 8, width);
-    done = rps_copy_units<uint2>(s, d, head, width);
-  }
-  if (lane < head) d[lane] = s[lane];                                     // (head <= 3)
-  for (int i = done + lane; i < width; i += RPL_WAVE) d[i] = s[i];        // (the tail: < 4 floats, or all)
-}
-
 __device__ inline void rps_zero_row(float* d, int width) {
   for (int i = (int)threadIdx.x; i < width; i += RPL_WAVE) d[i] = 0.f;
 }
@@ -108,9 +68,9 @@ __global__ __launch_bounds__(RPL_WAVE) void rp_sac_sample_kernel(const rp_sac_sa
     return;
   }
   const long long r0 = slot * E + e, r1 = next * E + e;
-  rps_copy_row(a.ring_obs + r0 * a.D, obs, a.D);
-  rps_copy_row(a.ring_obs + r1 * a.D, nobs, a.D);
-  rps_copy_row(a.ring_action + r0 * a.A, act, a.A);
+  rpl_copy_row(a.ring_obs + r0 * a.D, obs, a.D);
+  rpl_copy_row(a.ring_obs + r1 * a.D, nobs, a.D);
+  rpl_copy_row(a.ring_action + r0 * a.A, act, a.A);
   if (threadIdx.x == 0) {
     a.reward[b] = a.ring_reward[r1];
     a.discount[b] = a.ring_discount[r1];
@@ -255,18 +215,7 @@ __global__ __launch_bounds__(RPL_BLOCK) void rp_sac_target_kernel(const rp_sac_t
   }
 }
 
-unsigned blocks_for(long long total, int per) { return (unsigned)((total + per - 1) / per); }
-
 }  // namespace
-
-#define RPS_HEAD(fn, type)                                                                          \
-  if (!a) return fail(fn ": args is NULL");                                                         \
-  if (a->struct_size != sizeof(type)) return fail(fn ": struct_size does not match this library's " #type)
-#define RPS_CHECK(expr)                                   \
-  do {                                                    \
-    const std::string err_ = (expr);                      \
-    if (!err_.empty()) return fail(err_);                 \
-  } while (0)
 
 extern "C" {
 
@@ -283,8 +232,8 @@ int rp_sac_dim(const char* name) {
 }
 
 int rp_sac_sample(const rp_sac_sample_args* a) {
-  RPS_HEAD("rp_sac_sample", rp_sac_sample_args);
-  RPS_CHECK(rps_check_sample(a));
+  RP_ARGS_HEAD("rp_sac_sample", rp_sac_sample_args);
+  RP_ARGS_CHECK(rps_check_sample(a));
   if (a->row_count == 0) return 0;
   hipLaunchKernelGGL(rp_sac_sample_kernel, dim3((unsigned)a->row_count), dim3(RPL_WAVE), 0, (hipStream_t)a->hip_stream, *a);
   HIP_OK(hipGetLastError());
@@ -292,8 +241,8 @@ int rp_sac_sample(const rp_sac_sample_args* a) {
 }
 
 int rp_sac_act(const rp_sac_act_args* a) {
-  RPS_HEAD("rp_sac_act", rp_sac_act_args);
-  RPS_CHECK(rps_check_act(a));
+  RP_ARGS_HEAD("rp_sac_act", rp_sac_act_args);
+  RP_ARGS_CHECK(rps_check_act(a));
   if (a->row_count == 0) return 0;
   RpsActor actor;
   memset(&actor, 0, sizeof(actor));
@@ -307,8 +256,8 @@ int rp_sac_act(const rp_sac_act_args* a) {
 }
 
 int rp_sac_target(const rp_sac_target_args* a) {
-  RPS_HEAD("rp_sac_target", rp_sac_target_args);
-  RPS_CHECK(rps_check_target(a));
+  RP_ARGS_HEAD("rp_sac_target", rp_sac_target_args);
+  RP_ARGS_CHECK(rps_check_target(a));
   if (a->row_count == 0) return 0;
   RpsCritics critics;
   memset(&critics, 0, sizeof(critics));

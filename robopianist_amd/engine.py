@@ -15,6 +15,7 @@ from typing import Optional
 
 import numpy as np
 
+from robopianist_amd import _abi
 from robopianist_amd.model import compile as mcompile
 from robopianist_amd.model import engine_tables
 
@@ -55,21 +56,7 @@ def load_library(path: str = LIB_PATH):
     global _lib
     if _lib is not None:
         return _lib
-    if not os.path.exists(path):
-        raise EngineError(
-            f"HIP engine library not found at {path}. Build it with "
-            "`python -c 'import __graft_entry__ as g; g.build()'` (hipcc, gfx950). "
-            "There is no CPU fallback."
-        )
-    # torch bundles its own libamdhip64; it has to be in the process BEFORE this library pulls in the
-    # system one (same soname: the loader then binds us to torch's copy and the two share one runtime,
-    # which is what makes rp_field_ptr views and stream sharing work).  The other order leaves torch
-    # with "No HIP GPUs are available" at its first CUDA call.
-    try:
-        import torch  # noqa: F401
-    except ImportError:  # plain ctypes use without torch is fine
-        pass
-    L = ctypes.CDLL(path)
+    L = _abi.open_library(path, "engine", EngineError)
     L.rp_last_error.restype = ctypes.c_char_p
     L.rp_create.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_int,
                             ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]

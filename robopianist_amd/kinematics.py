@@ -14,6 +14,7 @@ import os
 
 import numpy as np
 
+from robopianist_amd import _abi
 from robopianist_amd.model import ik_tables
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -85,18 +86,8 @@ def declare(L, prefix: str = "rp_ik_"):
 def load_library(path: str = LIB_PATH):
     """Loads librp_ik.so; raises IKError if it has not been built."""
     global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(path):
-        raise IKError(
-            f"HIP inverse-kinematics library not found at {path}. Build it with "
-            "`python -c 'import __graft_entry__ as g; g.build()'` (hipcc, gfx950). "
-            "There is no CPU fallback.")
-    try:   # torch's HIP runtime first, as in engine.load_library
-        import torch  # noqa: F401
-    except ImportError:
-        pass
-    _lib = declare(ctypes.CDLL(path))
+    if _lib is None:
+        _lib = declare(_abi.open_library(path, "inverse-kinematics", IKError))
     return _lib
 
 

@@ -17,6 +17,8 @@ import os
 
 import numpy as np
 
+from robopianist_amd import _abi
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("RP_LEARN_LIB") or os.path.join(_HERE, "csrc", "librp_learn.so")
 
@@ -80,63 +82,22 @@ class MomentsArgs(ctypes.Structure):
 _ARGS = {"pack": PackArgs, "act": ActArgs, "gae": GaeArgs, "moments": MomentsArgs}
 
 
-def declare(L, prefix: str = "rp_learn_"):
-    """Declares the ABI's prototypes on a loaded library whose symbols start with `prefix`."""
-    f = lambda name: getattr(L, prefix + name)
-    f("last_error").restype = ctypes.c_char_p
-    f("dim").argtypes = [ctypes.c_char_p]
-    for name, cls in _ARGS.items():
-        f(name).argtypes = [ctypes.POINTER(cls)]
-    return L
-
-
 def load_library(path: str = LIB_PATH):
     """Loads librp_learn.so; raises LearnError if it has not been built."""
     global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(path):
-        raise LearnError(
-            f"HIP learner library not found at {path}. Build it with "
-            "`python -c 'import __graft_entry__ as g; g.build()'` (hipcc, gfx950). "
-            "There is no CPU fallback.")
-    try:   # torch's HIP runtime first, as in engine.load_library
-        import torch  # noqa: F401
-    except ImportError:
-        pass
-    _lib = declare(ctypes.CDLL(path))
+    if _lib is None:
+        _lib = declare(_abi.open_library(path, "learner", LearnError))
     return _lib
 
 
-def make_args(entry: str, **values):
-    """A filled argument block of entry point `entry` ("pack", ...); fields that are not named stay zero / NULL."""
-    a = _ARGS[entry]()
-    a.struct_size = ctypes.sizeof(a)
-    names = dict((f[0], 0) for f in a._fields_)
-    for k, v in values.items():
-        if k not in names:
-            raise TypeError(f"rp_learn_{entry}_args has no field {k!r}")
-        setattr(a, k, v)
-    return a
+_entries = _abi.EntryTable("rp_learn_", _ARGS, LearnError, load_library)
+make_args, call_raw, last_error, dim, _call = (_entries.make_args, _entries.call_raw, _entries.last_error, _entries.dim,
+                                               _entries.call)
 
 
-def call_raw(entry: str, args) -> int:
-    """The C return code of rp_learn_<entry>(&args) (see last_error())."""
-    return getattr(load_library(), "rp_learn_" + entry)(ctypes.byref(args))
-
-
-def last_error() -> str:
-    return load_library().rp_learn_last_error().decode()
-
-
-def dim(name: str) -> int:
-    return load_library().rp_learn_dim(name.encode())
-
-
-def _call(entry: str, **values) -> None:
-    args = make_args(entry, **values)
-    if call_raw(entry, args) != 0:
-        raise LearnError(last_error())
+def declare(L, prefix: str = "rp_learn_"):
+    """Declares the ABI's prototypes on a loaded library whose symbols start with `prefix`."""
+    return _entries.declare(L, prefix)
 
 
 def field_table(fields):
@@ -176,9 +137,9 @@ def act(obs, mean, inv_std, obs_clip, actor, critic, D, H1, H2, A, n_rows, log_s
           actor=ctypes.pointer(actor) if actor is not None else None,
           critic=ctypes.pointer(critic) if critic is not None else None, log_std=log_std, action=action, logp=logp, mu=mu,
           env_action=env_action, value=value, precision=precision, deterministic=int(bool(deterministic)),
-          seed_lo=int(seed) & 0xFFFFFFFF, seed_hi=(int(seed) >> 32) & 0xFFFFFFFF, round=int(round_) & 0xFFFFFFFF,
           D=D, H1=H1, H2=H2, A=A, n_rows=n_rows, row_first=row_first,
-          row_count=n_rows - row_first if row_count is None else row_count, hip_stream=hip_stream)
+          row_count=n_rows - row_first if row_count is None else row_count, hip_stream=hip_stream,
+          **_abi.seed_args(seed, round_))
 
 
 def gae(reward, discount, step_type, value, adv, ret, valid, gamma, lam, T, E, env_first=0, env_count=None,
@@ -230,37 +191,33 @@ def _unwrap(env):
     return env
 
 
-class PPO:
-    """Proximal policy optimisation (Schulman et al. 2017) with a diagonal Gaussian policy, over every env of `env` at
-    once.  `env` is a batched `Environment` or a `CanonicalSpecWrapper` around one: the policy acts in [-1, 1]^A, the
-    raw action is what is stored and scored, its clamp to [-1, 1] is what `step_canonical` receives.
+class DeviceLearner:
+    """What the learners (`PPO`, offpolicy's `SAC`) share: the environment and its specs, the packing of a TimeStep into
+    a slot of the learner's storage, the running episode statistics, the observation normaliser and the evaluation slot.
+    A subclass allocates the storage the pack writes (`_obs`, `_reward`, `_discount`, `_step_type`, indexed by slot) and
+    builds its networks: two tanh layers of `hidden` units, which the kernels read in place.  A subclass's constructor
+    calls `__init__`, checks its own storage sizes, then calls `_init_specs`."""
 
-    The actor and the critic are `torch.nn.Sequential`s with two tanh layers of `hidden` units; the kernels read their
-    weights in place, so Adam's updates need no copy.  Observations are the spec's tensors in sorted key order,
-    normalised by running moments (clamped to +-`obs_clip`); the normaliser learns in `train()` after each update, so
-    `collect()` alone never changes it.
+    _reads = "the kernels read"   # (how `_mlp`'s error names the reader)
 
-    `collect()` launches, on torch's current stream and without reading anything back, T x (act, env step, pack), the
-    critic at slot T and gae.  The first call resets the env; later ones continue from the last TimeStep."""
-
-    def __init__(self, env, hidden=(256, 256), horizon: int = 16, epochs: int = 4, minibatches: int = 4,
-                 gamma: float = 0.99, lam: float = 0.95, clip: float = 0.2, lr: float = 3e-4, vf_coef: float = 0.5,
-                 ent_coef: float = 0.0, max_grad_norm: float = 0.5, obs_clip: float = 10.0, seed: int = 0,
-                 init_log_std: float = -0.5, norm_eps: float = 1e-8):
+    def __init__(self, env):
         import torch
-        from torch import nn
         self._env = base = _unwrap(env)
         phys = base.physics
         self._dev, self._dtype = torch.device(phys.device), phys.dtype
         self._precision = 32 if phys.dtype == torch.float32 else 64
-        self.E, self.T = int(base.n_envs), int(horizon)
-        if self.T < 1:
-            raise ValueError("horizon must be >= 1")
+        self.E = int(base.n_envs)
+
+    def _init_specs(self, hidden, obs_clip, seed, norm_eps):
+        """The spec validation, D, A, H1, H2 and the action bounds; the buffers every learner has."""
+        import torch
+        base = self._env
         ospec = base.observation_spec()
         self._keys = sorted(ospec)
         self._widths = [int(np.prod(ospec[k].shape, dtype=np.int64)) for k in self._keys]
         if not 1 <= len(self._keys) <= MAX_FIELDS or min(self._widths) < 1:
-            raise ValueError(f"PPO packs 1 .. {MAX_FIELDS} non-empty observation tensors, the spec has {len(self._keys)}")
+            raise ValueError(f"{type(self).__name__} packs 1 .. {MAX_FIELDS} non-empty observation tensors, the spec has "
+                             f"{len(self._keys)}")
         self.D = int(sum(self._widths))
         aspec = base.action_spec()
         self.A = int(aspec.shape[0])
@@ -274,34 +231,9 @@ class PPO:
         rng = np.asarray(aspec.maximum, np.float64) - lo
         self._bounds = (torch.as_tensor(lo, device=self._dev, dtype=self._dtype),
                         torch.as_tensor(rng, device=self._dev, dtype=self._dtype))
-        self.epochs, self.minibatches = int(epochs), int(minibatches)
-        self.gamma, self.lam, self.clip = float(gamma), float(lam), float(clip)
-        self.vf_coef, self.ent_coef, self.max_grad_norm = float(vf_coef), float(ent_coef), float(max_grad_norm)
         self.obs_clip, self.norm_eps = float(obs_clip), float(norm_eps)
         self.seed, self._round = int(seed), 0
-
-        def mlp(n_out, last_gain):
-            net = nn.Sequential(nn.Linear(self.D, self.H1), nn.Tanh(), nn.Linear(self.H1, self.H2), nn.Tanh(),
-                                nn.Linear(self.H2, n_out))
-            with torch.no_grad():
-                net[4].weight.mul_(last_gain)
-                net[4].bias.zero_()
-            return net
-
-        with torch.random.fork_rng(devices=[]):   # (the global generator is left as it was)
-            torch.manual_seed(self.seed)
-            self.actor, self.critic = mlp(self.A, 0.01), mlp(1, 1.0)
-        self.actor.to(self._dev); self.critic.to(self._dev)
-        self.log_std = nn.Parameter(torch.full((self.A,), float(init_log_std), device=self._dev))
-        self.optimizer = torch.optim.Adam(list(self.actor.parameters()) + list(self.critic.parameters()) + [self.log_std],
-                                          lr=float(lr), eps=1e-5)
-        T, E, D, A = self.T, self.E, self.D, self.A
-        z = lambda *shape, dtype=torch.float32: torch.zeros(shape, dtype=dtype, device=self._dev)
-        self._obs, self._reward, self._discount = z(T + 1, E, D), z(T + 1, E), z(T + 1, E)
-        self._step_type = z(T + 1, E, dtype=torch.int32)
-        self._action, self._logp, self._value = z(T, E, A), z(T, E), z(T + 1, E)
-        self._env_action = z(T, E, A, dtype=self._dtype)
-        self._adv, self._ret, self._valid = z(T, E), z(T, E), z(T, E, dtype=torch.uint8)
+        E, D, A, z = self.E, self.D, self.A, self._zeros
         self._ep_return, self._ep_len = z(E, dtype=torch.float64), z(E, dtype=torch.int32)
         self._done_return, self._done_len = z(E, dtype=torch.float64), z(E, dtype=torch.int64)
         self._done_count = z(E, dtype=torch.int32)
@@ -313,8 +245,17 @@ class PPO:
         self._count = 0.0
         self._mean, self._M2 = z(D, dtype=torch.float64), z(D, dtype=torch.float64)
         self._mean_f32, self._inv_std_f32 = z(D), torch.ones(D, dtype=torch.float32, device=self._dev)
-        self._started = False
         self._keep = None
+
+    def _zeros(self, *shape, dtype=None):
+        import torch
+        return torch.zeros(shape, dtype=torch.float32 if dtype is None else dtype, device=self._dev)
+
+    def _net(self, n_in, n_out):
+        """A network as the kernels take it (on the CPU; drawn from torch's global generator)."""
+        from torch import nn
+        return nn.Sequential(nn.Linear(n_in, self.H1), nn.Tanh(), nn.Linear(self.H1, self.H2), nn.Tanh(),
+                             nn.Linear(self.H2, n_out))
 
     # -- accessors ---------------------------------------------------------------------------------------------------
     @property
@@ -337,14 +278,12 @@ class PPO:
             raise LearnError("the learner's kernels need a HIP device; there is no CPU fallback")
         return torch.cuda.current_stream(self._dev).cuda_stream
 
-    def _nets(self):
-        """(actor, critic) as rp_learn_mlp: the addresses of the parameters as they are now."""
-        for net in (self.actor, self.critic):
-            for layer in (net[0], net[2], net[4]):
-                if not (layer.weight.is_contiguous() and layer.bias.is_contiguous()):
-                    raise LearnError("the policy kernel reads contiguous float32 parameters")
-        tens = lambda net: [t for i in (0, 2, 4) for t in (net[i].weight, net[i].bias)]
-        return mlp_table(tens(self.actor)), mlp_table(tens(self.critic))
+    def _mlp(self, net):
+        """`net` as rp_learn_mlp: the addresses of the parameters as they are now."""
+        for layer in (net[0], net[2], net[4]):
+            if not (layer.weight.is_contiguous() and layer.bias.is_contiguous()):
+                raise LearnError(f"{self._reads} contiguous float32 parameters")
+        return mlp_table([t for i in (0, 2, 4) for t in (net[i].weight, net[i].bias)])
 
     def _table(self, observation):
         import torch
@@ -373,6 +312,108 @@ class PPO:
              stats=(self._ep_return.data_ptr(), self._ep_len.data_ptr(), self._done_return.data_ptr(),
                     self._done_len.data_ptr(), self._done_count.data_ptr()), hip_stream=st)
 
+    def _pack_observation(self, observation, st):
+        """The first half of `act()`: an observation dict of E rows into the evaluation slot (`_e_obs`)."""
+        self._e_step_type.fill_(STEP_MID)
+        pack(self._table(observation), self._precision, self._e_step_type.data_ptr(), None, None,
+             self._e_obs.data_ptr(), self._e_reward.data_ptr(), self._e_discount.data_ptr(),
+             self._e_step_type.data_ptr(), self.E, self.D, hip_stream=st)
+        self._keep = observation   # alive until the pack has run (a rollout's TimeSteps have been consumed by then)
+
+    def _merge_moments(self, obs, n_rows, st):
+        """The `n_rows` rows from `obs` on into the running moments (one launch)."""
+        moments(obs.data_ptr(), self._mean.data_ptr(), self._M2.data_ptr(), self._mean_f32.data_ptr(),
+                self._inv_std_f32.data_ptr(), self._count, self.norm_eps, n_rows, self.D, hip_stream=st)
+        self._count += float(n_rows)
+
+    def normalize(self, obs):
+        """What the kernels feed the first layer (torch, float32)."""
+        import torch
+        return torch.clamp((obs - self._mean_f32) * self._inv_std_f32, -self.obs_clip, self.obs_clip)
+
+    def episode_stats(self):
+        """{"episodes", "mean_return", "mean_length"} of the episodes that ended since the last call (one read-back);
+        the counters start again from zero."""
+        n = int(self._done_count.sum())
+        out = {"episodes": n,
+               "mean_return": float(self._done_return.sum()) / n if n else float("nan"),
+               "mean_length": float(self._done_len.sum()) / n if n else float("nan")}
+        self._done_return.zero_(); self._done_len.zero_(); self._done_count.zero_()
+        return out
+
+    # -- the blocks of a checkpoint that every learner has ---------------------------------------------------------------
+    def _normalizer_state(self):
+        c = lambda t: t.detach().clone()
+        return {"count": self._count, "mean": c(self._mean), "M2": c(self._M2), "mean_f32": c(self._mean_f32),
+                "inv_std_f32": c(self._inv_std_f32)}
+
+    def _episodes_state(self):
+        return {k: getattr(self, "_" + k).detach().clone()
+                for k in ("ep_return", "ep_len", "done_return", "done_len", "done_count")}
+
+    def _load_shared_state(self, sd):
+        """The "normalizer" and "episodes" blocks of `sd`."""
+        nz = sd["normalizer"]
+        self._count = float(nz["count"])
+        for dst, key in ((self._mean, "mean"), (self._M2, "M2"), (self._mean_f32, "mean_f32"),
+                         (self._inv_std_f32, "inv_std_f32")):
+            dst.copy_(nz[key])
+        for key, v in sd["episodes"].items():
+            getattr(self, "_" + key).copy_(v)
+
+
+class PPO(DeviceLearner):
+    """Proximal policy optimisation (Schulman et al. 2017) with a diagonal Gaussian policy, over every env of `env` at
+    once.  `env` is a batched `Environment` or a `CanonicalSpecWrapper` around one: the policy acts in [-1, 1]^A, the
+    raw action is what is stored and scored, its clamp to [-1, 1] is what `step_canonical` receives.
+
+    The actor and the critic are `torch.nn.Sequential`s with two tanh layers of `hidden` units; the kernels read their
+    weights in place, so Adam's updates need no copy.  Observations are the spec's tensors in sorted key order,
+    normalised by running moments (clamped to +-`obs_clip`); the normaliser learns in `train()` after each update, so
+    `collect()` alone never changes it.
+
+    `collect()` launches, on torch's current stream and without reading anything back, T x (act, env step, pack), the
+    critic at slot T and gae.  The first call resets the env; later ones continue from the last TimeStep."""
+
+    _reads = "the policy kernel reads"
+
+    def __init__(self, env, hidden=(256, 256), horizon: int = 16, epochs: int = 4, minibatches: int = 4,
+                 gamma: float = 0.99, lam: float = 0.95, clip: float = 0.2, lr: float = 3e-4, vf_coef: float = 0.5,
+                 ent_coef: float = 0.0, max_grad_norm: float = 0.5, obs_clip: float = 10.0, seed: int = 0,
+                 init_log_std: float = -0.5, norm_eps: float = 1e-8):
+        import torch
+        from torch import nn
+        super().__init__(env)
+        self.T = int(horizon)
+        if self.T < 1:
+            raise ValueError("horizon must be >= 1")
+        self._init_specs(hidden, obs_clip, seed, norm_eps)
+        self.epochs, self.minibatches = int(epochs), int(minibatches)
+        self.gamma, self.lam, self.clip = float(gamma), float(lam), float(clip)
+        self.vf_coef, self.ent_coef, self.max_grad_norm = float(vf_coef), float(ent_coef), float(max_grad_norm)
+
+        def mlp(n_out, last_gain):
+            net = self._net(self.D, n_out)
+            with torch.no_grad():
+                net[4].weight.mul_(last_gain)
+                net[4].bias.zero_()
+            return net
+
+        with torch.random.fork_rng(devices=[]):   # (the global generator is left as it was)
+            torch.manual_seed(self.seed)
+            self.actor, self.critic = mlp(self.A, 0.01), mlp(1, 1.0)
+        self.actor.to(self._dev); self.critic.to(self._dev)
+        self.log_std = nn.Parameter(torch.full((self.A,), float(init_log_std), device=self._dev))
+        self.optimizer = torch.optim.Adam(list(self.actor.parameters()) + list(self.critic.parameters()) + [self.log_std],
+                                          lr=float(lr), eps=1e-5)
+        T, E, D, A, z = self.T, self.E, self.D, self.A, self._zeros
+        self._obs, self._reward, self._discount = z(T + 1, E, D), z(T + 1, E), z(T + 1, E)
+        self._step_type = z(T + 1, E, dtype=torch.int32)
+        self._action, self._logp, self._value = z(T, E, A), z(T, E), z(T + 1, E)
+        self._env_action = z(T, E, A, dtype=self._dtype)
+        self._adv, self._ret, self._valid = z(T, E), z(T, E), z(T, E, dtype=torch.uint8)
+        self._started = False
+
     # -- the rollout -------------------------------------------------------------------------------------------------
     def rollout(self):
         """The storage as a dict of views (live)."""
@@ -386,7 +427,7 @@ class PPO:
         T, E, D, A = self.T, self.E, self.D, self.A
         with torch.cuda.device(self._dev):
             st = self._stream()
-            actor, critic = self._nets()
+            actor, critic = self._mlp(self.actor), self._mlp(self.critic)
             kept = []
             if self._started:
                 for buf in (self._obs, self._reward, self._discount, self._step_type, self._value):
@@ -418,15 +459,7 @@ class PPO:
         """Merges the observations of slots 0 .. T - 1 of the storage into the running moments (one launch)."""
         import torch
         with torch.cuda.device(self._dev):
-            n = self.T * self.E
-            moments(self._obs.data_ptr(), self._mean.data_ptr(), self._M2.data_ptr(), self._mean_f32.data_ptr(),
-                    self._inv_std_f32.data_ptr(), self._count, self.norm_eps, n, self.D, hip_stream=self._stream())
-            self._count += float(n)
-
-    def normalize(self, obs):
-        """What the policy kernel feeds the first layer (torch, float32)."""
-        import torch
-        return torch.clamp((obs - self._mean_f32) * self._inv_std_f32, -self.obs_clip, self.obs_clip)
+            self._merge_moments(self._obs, self.T * self.E, self._stream())
 
     # -- the gradient step ---------------------------------------------------------------------------------------------
     def update(self, rollout=None):
@@ -485,29 +518,14 @@ class PPO:
         import torch
         with torch.cuda.device(self._dev):
             st = self._stream()
-            self._e_step_type.fill_(STEP_MID)
-            pack(self._table(observation), self._precision, self._e_step_type.data_ptr(), None, None,
-                 self._e_obs.data_ptr(), self._e_reward.data_ptr(), self._e_discount.data_ptr(),
-                 self._e_step_type.data_ptr(), self.E, self.D, hip_stream=st)
-            actor, _ = self._nets()
-            act(self._e_obs.data_ptr(), self._mean_f32.data_ptr(), self._inv_std_f32.data_ptr(), self.obs_clip, actor, None,
-                self.D, self.H1, self.H2, self.A, self.E, log_std=self.log_std.data_ptr(),
+            self._pack_observation(observation, st)
+            act(self._e_obs.data_ptr(), self._mean_f32.data_ptr(), self._inv_std_f32.data_ptr(), self.obs_clip,
+                self._mlp(self.actor), None, self.D, self.H1, self.H2, self.A, self.E, log_std=self.log_std.data_ptr(),
                 action=self._e_action.data_ptr(), logp=self._e_logp.data_ptr(), env_action=self._e_env_action.data_ptr(),
                 precision=self._precision, deterministic=deterministic, seed=self.seed, round_=self._round, hip_stream=st)
             if not deterministic:
                 self._round += 1
-            self._keep = observation   # alive until the pack has run (a rollout's TimeSteps have been consumed by then)
         return self._e_env_action
-
-    def episode_stats(self):
-        """{"episodes", "mean_return", "mean_length"} of the episodes that ended since the last call (one read-back);
-        the counters start again from zero."""
-        n = int(self._done_count.sum())
-        out = {"episodes": n,
-               "mean_return": float(self._done_return.sum()) / n if n else float("nan"),
-               "mean_length": float(self._done_len.sum()) / n if n else float("nan")}
-        self._done_return.zero_(); self._done_len.zero_(); self._done_count.zero_()
-        return out
 
     # -- checkpoint / resume -------------------------------------------------------------------------------------------
     def state_dict(self):
@@ -519,14 +537,11 @@ class PPO:
         return {"actor": {k: c(v) for k, v in self.actor.state_dict().items()},
                 "critic": {k: c(v) for k, v in self.critic.state_dict().items()},
                 "log_std": c(self.log_std), "optimizer": copy.deepcopy(self.optimizer.state_dict()),
-                "normalizer": {"count": self._count, "mean": c(self._mean), "M2": c(self._M2),
-                               "mean_f32": c(self._mean_f32), "inv_std_f32": c(self._inv_std_f32)},
+                "normalizer": self._normalizer_state(),
                 "seed": self.seed, "round": self._round, "started": self._started,
                 "last": {"obs": c(self._obs[T]), "reward": c(self._reward[T]), "discount": c(self._discount[T]),
                          "step_type": c(self._step_type[T]), "value": c(self._value[T])},
-                "episodes": {"ep_return": c(self._ep_return), "ep_len": c(self._ep_len),
-                             "done_return": c(self._done_return), "done_len": c(self._done_len),
-                             "done_count": c(self._done_count)}}
+                "episodes": self._episodes_state()}
 
     def load_state_dict(self, sd):
         import torch
@@ -534,56 +549,58 @@ class PPO:
         with torch.no_grad():
             self.log_std.copy_(sd["log_std"])
         self.optimizer.load_state_dict(sd["optimizer"])
-        nz = sd["normalizer"]
-        self._count = float(nz["count"])
-        for dst, key in ((self._mean, "mean"), (self._M2, "M2"), (self._mean_f32, "mean_f32"),
-                         (self._inv_std_f32, "inv_std_f32")):
-            dst.copy_(nz[key])
+        self._load_shared_state(sd)
         self.seed, self._round, self._started = int(sd["seed"]), int(sd["round"]), bool(sd["started"])
         T = self.T
         for buf, key in ((self._obs, "obs"), (self._reward, "reward"), (self._discount, "discount"),
                          (self._step_type, "step_type"), (self._value, "value")):
             buf[T].copy_(sd["last"][key])
-        for key, v in sd["episodes"].items():
-            getattr(self, "_" + key).copy_(v)
 
 
-def train_and_evaluate(env, updates: int, time_limit: float = None, log=print, **ppo_kwargs):
-    """What the examples' --train-ppo does: `updates` rounds of PPO on `env` (a batched Environment), one line per
-    round with the mean return of the episodes that ended in it, then one deterministic episode of every env through a
-    MidiEvaluationWrapper.  Stops early after `time_limit` seconds.  Returns (ppo, log of the rounds, metrics)."""
+def _train_and_evaluate(learner, rounds, train_one, shown, time_limit, log):
+    """What both `train_and_evaluate` do: `rounds` calls of `train_one(callback)` (one round of training each), one line
+    per round with the mean return of the episodes that ended in it and the statistic `shown` = (label, key), then one
+    deterministic episode of every env through a MidiEvaluationWrapper.  Returns (log of the rounds, metrics)."""
     import time
     import torch
     from robopianist_amd.wrappers import CanonicalSpecWrapper, MidiEvaluationWrapper
-    ppo = PPO(env, **ppo_kwargs)
     t0 = time.perf_counter()
-    rounds = []
-
+    rounds_log = []
     last_mean = [float("nan")]
 
     def report(i, s):
-        rounds.append(s)
+        rounds_log.append(s)
         if s["episodes"]:
             last_mean[0] = s["mean_return"]
         # (a round in which no episode ended shows the mean of the last round in which some did)
         log(f"update {i + 1:4d}  episodes {s['episodes']:6d}  mean return {last_mean[0]:10.4f}  "
-            f"mean reward {s['mean_reward']:8.4f}  kl {s.get('approx_kl', float('nan')):8.5f}  "
+            f"mean reward {s['mean_reward']:8.4f}  {shown[0]} {s.get(shown[1], float('nan')):8.5f}  "
             f"{time.perf_counter() - t0:7.1f} s")
 
-    for i in range(int(updates)):
-        ppo.train(1, callback=lambda _, s, i=i: report(i, s))
+    for i in range(int(rounds)):
+        train_one(lambda _, s, i=i: report(i, s))
         if time_limit is not None and time.perf_counter() - t0 > time_limit:
             log(f"stopped after {i + 1} updates: the time limit of {time_limit:.0f} s")
             break
-    evaluated = CanonicalSpecWrapper(MidiEvaluationWrapper(ppo.env))
+    evaluated = CanonicalSpecWrapper(MidiEvaluationWrapper(learner.env))
     ts = evaluated.reset()
-    done = torch.zeros(ppo.E, dtype=torch.bool, device=ts.step_type.device)
+    done = torch.zeros(learner.E, dtype=torch.bool, device=ts.step_type.device)
     for _ in range(100000):
-        ts = evaluated.step(ppo.act(ts.observation, deterministic=True))
+        ts = evaluated.step(learner.act(ts.observation, deterministic=True))
         done |= ts.last()
         if bool(done.all()):
             break
     metrics = evaluated.get_musical_metrics()
     for k, v in metrics.items():
         log(f"\t{k}: {v:.4f}")
+    return rounds_log, metrics
+
+
+def train_and_evaluate(env, updates: int, time_limit: float = None, log=print, **ppo_kwargs):
+    """What the examples' --train-ppo does: `updates` rounds of PPO on `env` (a batched Environment), one line per
+    round with the mean return of the episodes that ended in it, then one deterministic episode of every env through a
+    MidiEvaluationWrapper.  Stops early after `time_limit` seconds.  Returns (ppo, log of the rounds, metrics)."""
+    ppo = PPO(env, **ppo_kwargs)
+    rounds, metrics = _train_and_evaluate(ppo, updates, lambda cb: ppo.train(1, callback=cb), ("kl", "approx_kl"),
+                                          time_limit, log)
     return ppo, rounds, metrics

@@ -18,6 +18,7 @@ from typing import Optional, Tuple
 
 import numpy as np
 
+from robopianist_amd import _abi
 from robopianist_amd.music import constants as consts
 from robopianist_amd.music import synthesizer
 
@@ -138,17 +139,7 @@ def load_library(path: Optional[str] = None):
     global _lib
     if _lib is not None and path is None:
         return _lib
-    p = LIB_PATH if path is None else path
-    if not os.path.exists(p):
-        raise HearingError(
-            f"HIP hearing library not found at {p}. Build it with "
-            "`python -c 'import __graft_entry__ as g; g.build()'` (hipcc, gfx950). "
-            "There is no CPU fallback.")
-    try:   # torch's HIP runtime first, as in engine.load_library
-        import torch  # noqa: F401
-    except ImportError:
-        pass
-    L = ctypes.CDLL(p)
+    L = _abi.open_library(LIB_PATH if path is None else path, "hearing", HearingError)
     declare(L)
     if path is None:
         _lib = L

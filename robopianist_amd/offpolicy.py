@@ -16,10 +16,10 @@ import ctypes
 import math
 import os
 
-import numpy as np
-
+from robopianist_amd import _abi
 from robopianist_amd.learning import (F32, F64, MAX_ACTIONS, MAX_FIELDS, MAX_HIDDEN, STEP_FIRST, STEP_LAST, STEP_MID,  # noqa: F401
-                                      LOG_2PI, LearnError, Mlp, _unwrap, field_table, mlp_table, moments, pack)
+                                      LOG_2PI, DeviceLearner, LearnError, Mlp, _train_and_evaluate, _unwrap, field_table,
+                                      mlp_table, moments, pack)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("RP_SAC_LIB") or os.path.join(_HERE, "csrc", "librp_sac.so")
@@ -61,67 +61,22 @@ class TargetArgs(ctypes.Structure):
 _ARGS = {"sample": SampleArgs, "act": ActArgs, "target": TargetArgs}
 
 
-def declare(L, prefix: str = "rp_sac_"):
-    """Declares the ABI's prototypes on a loaded library whose symbols start with `prefix`."""
-    f = lambda name: getattr(L, prefix + name)
-    f("last_error").restype = ctypes.c_char_p
-    f("dim").argtypes = [ctypes.c_char_p]
-    for name, cls in _ARGS.items():
-        f(name).argtypes = [ctypes.POINTER(cls)]
-    return L
-
-
 def load_library(path: str = LIB_PATH):
     """Loads librp_sac.so; raises LearnError if it has not been built."""
     global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(path):
-        raise LearnError(
-            f"HIP off-policy learner library not found at {path}. Build it with "
-            "`python -c 'import __graft_entry__ as g; g.build()'` (hipcc, gfx950). "
-            "There is no CPU fallback.")
-    try:   # torch's HIP runtime first, as in engine.load_library
-        import torch  # noqa: F401
-    except ImportError:
-        pass
-    _lib = declare(ctypes.CDLL(path))
+    if _lib is None:
+        _lib = declare(_abi.open_library(path, "off-policy learner", LearnError))
     return _lib
 
 
-def make_args(entry: str, **values):
-    """A filled argument block of entry point `entry` ("sample", ...); fields that are not named stay zero / NULL."""
-    a = _ARGS[entry]()
-    a.struct_size = ctypes.sizeof(a)
-    names = dict((f[0], 0) for f in a._fields_)
-    for k, v in values.items():
-        if k not in names:
-            raise TypeError(f"rp_sac_{entry}_args has no field {k!r}")
-        setattr(a, k, v)
-    return a
+_entries = _abi.EntryTable("rp_sac_", _ARGS, LearnError, load_library)
+make_args, call_raw, last_error, dim, _call = (_entries.make_args, _entries.call_raw, _entries.last_error, _entries.dim,
+                                               _entries.call)
 
 
-def call_raw(entry: str, args) -> int:
-    """The C return code of rp_sac_<entry>(&args) (see last_error())."""
-    return getattr(load_library(), "rp_sac_" + entry)(ctypes.byref(args))
-
-
-def last_error() -> str:
-    return load_library().rp_sac_last_error().decode()
-
-
-def dim(name: str) -> int:
-    return load_library().rp_sac_dim(name.encode())
-
-
-def _call(entry: str, **values) -> None:
-    args = make_args(entry, **values)
-    if call_raw(entry, args) != 0:
-        raise LearnError(last_error())
-
-
-def _seed(seed, round_):
-    return dict(seed_lo=int(seed) & 0xFFFFFFFF, seed_hi=(int(seed) >> 32) & 0xFFFFFFFF, round=int(round_) & 0xFFFFFFFF)
+def declare(L, prefix: str = "rp_sac_"):
+    """Declares the ABI's prototypes on a loaded library whose symbols start with `prefix`."""
+    return _entries.declare(L, prefix)
 
 
 def critic_table(critics):
@@ -140,7 +95,8 @@ def sample(ring_obs, ring_action, ring_reward, ring_discount, ring_step_type, ob
     _call("sample", ring_obs=ring_obs, ring_action=ring_action, ring_reward=ring_reward, ring_discount=ring_discount,
           ring_step_type=ring_step_type, obs=obs, next_obs=next_obs, action=action, reward=reward, discount=discount,
           mask=mask, index=index, n_written=int(n_written), C=C, E=E, D=D, A=A, B=B, row_first=row_first,
-          row_count=B - row_first if row_count is None else row_count, hip_stream=hip_stream, **_seed(seed, round_))
+          row_count=B - row_first if row_count is None else row_count, hip_stream=hip_stream,
+          **_abi.seed_args(seed, round_))
 
 
 def act(obs, mean, inv_std, obs_clip, actor, D, H1, H2, A, n_rows, log_std_bounds=(-5.0, 2.0), action=None, logp=None,
@@ -151,7 +107,8 @@ def act(obs, mean, inv_std, obs_clip, actor, D, H1, H2, A, n_rows, log_std_bound
           log_std_max=float(log_std_bounds[1]), actor=ctypes.pointer(actor) if actor is not None else None,
           action=action, logp=logp, pre=pre, env_action=env_action, precision=precision,
           deterministic=int(bool(deterministic)), D=D, H1=H1, H2=H2, A=A, n_rows=n_rows, row_first=row_first,
-          row_count=n_rows - row_first if row_count is None else row_count, hip_stream=hip_stream, **_seed(seed, round_))
+          row_count=n_rows - row_first if row_count is None else row_count, hip_stream=hip_stream,
+          **_abi.seed_args(seed, round_))
 
 
 def target(next_obs, action, logp, reward, discount, mean, inv_std, obs_clip, gamma, log_alpha, critics, y, D, H1, H2, A,
@@ -199,7 +156,7 @@ def alpha_loss(log_alpha, logp_new, target_entropy, mask):
     return _masked_mean(-log_alpha * (logp_new.detach() + float(target_entropy)), mask)
 
 
-class SAC:
+class SAC(DeviceLearner):
     """Soft actor-critic (Haarnoja et al. 2018) with a tanh-squashed, state-dependent Gaussian policy, an ensemble of
     `n_critics` critics with Polyak-averaged targets and a learned temperature, over every env of `env` at once.  `env`
     is a batched `Environment` or a `CanonicalSpecWrapper` around one; the squashed action in [-1, 1]^A is what is
@@ -217,56 +174,29 @@ class SAC:
                  obs_clip: float = 10.0, seed: int = 0, norm_eps: float = 1e-8):
         import torch
         from torch import nn
-        self._env = base = _unwrap(env)
-        phys = base.physics
-        self._dev, self._dtype = torch.device(phys.device), phys.dtype
-        self._precision = 32 if phys.dtype == torch.float32 else 64
-        self.E, self.C, self.B = int(base.n_envs), int(capacity), int(batch_size)
+        super().__init__(env)
+        self.C, self.B = int(capacity), int(batch_size)
         if self.C < 2:
             raise ValueError("capacity must be >= 2 slots")
         if self.B < 1:
             raise ValueError("batch_size must be >= 1")
         if (self.C - 1) * self.E >= 2 ** 32:
             raise ValueError("(capacity - 1) x n_envs must stay below 2^32")
-        ospec = base.observation_spec()
-        self._keys = sorted(ospec)
-        self._widths = [int(np.prod(ospec[k].shape, dtype=np.int64)) for k in self._keys]
-        if not 1 <= len(self._keys) <= MAX_FIELDS or min(self._widths) < 1:
-            raise ValueError(f"SAC packs 1 .. {MAX_FIELDS} non-empty observation tensors, the spec has {len(self._keys)}")
-        self.D = int(sum(self._widths))
-        aspec = base.action_spec()
-        self.A = int(aspec.shape[0])
-        self.H1, self.H2 = (int(h) for h in hidden)
-        for h in (self.H1, self.H2):
-            if h < 16 or h > MAX_HIDDEN or h % 16:
-                raise ValueError(f"hidden sizes must be multiples of 16 in [16, {MAX_HIDDEN}], got {tuple(hidden)}")
-        if not 1 <= self.A <= MAX_ACTIONS:
-            raise ValueError(f"the action has {self.A} entries, the policy kernel takes 1 .. {MAX_ACTIONS}")
+        self._init_specs(hidden, obs_clip, seed, norm_eps)
         self.n_critics = int(n_critics)
         if not 1 <= self.n_critics <= MAX_CRITICS:
             raise ValueError(f"n_critics must be 1 .. {MAX_CRITICS}, got {n_critics}")
-        lo = np.asarray(aspec.minimum, np.float64)
-        rng = np.asarray(aspec.maximum, np.float64) - lo
-        self._bounds = (torch.as_tensor(lo, device=self._dev, dtype=self._dtype),
-                        torch.as_tensor(rng, device=self._dev, dtype=self._dtype))
         self.gamma, self.tau = float(gamma), float(tau)
         self.target_entropy = -float(self.A) if target_entropy is None else float(target_entropy)
         self.log_std_bounds = (float(log_std_bounds[0]), float(log_std_bounds[1]))
         if not self.log_std_bounds[0] <= self.log_std_bounds[1]:
             raise ValueError("log_std_bounds must be (min, max) with min <= max")
         self.learning_starts = int(learning_starts)
-        self.obs_clip, self.norm_eps = float(obs_clip), float(norm_eps)
-        self.seed, self._round = int(seed), 0
         self.n_written = 0
-
-        def mlp(n_in, n_out):
-            return nn.Sequential(nn.Linear(n_in, self.H1), nn.Tanh(), nn.Linear(self.H1, self.H2), nn.Tanh(),
-                                 nn.Linear(self.H2, n_out))
-
         with torch.random.fork_rng(devices=[]):   # (the global generator is left as it was)
             torch.manual_seed(self.seed)
-            self.actor = mlp(self.D, 2 * self.A)
-            self.critics = [mlp(self.D + self.A, 1) for _ in range(self.n_critics)]
+            self.actor = self._net(self.D, 2 * self.A)
+            self.critics = [self._net(self.D + self.A, 1) for _ in range(self.n_critics)]
         self.actor.to(self._dev)
         for c in self.critics:
             c.to(self._dev)
@@ -280,43 +210,16 @@ class SAC:
         self.alpha_optimizer = adam([self.log_alpha])
         # the gradient step's own draws (torch's rsample); a CPU device keeps the host tests possible
         self._gen = torch.Generator(device=self._dev).manual_seed(self.seed)
-        C, E, D, A, B = self.C, self.E, self.D, self.A, self.B
-        z = lambda *shape, dtype=torch.float32: torch.zeros(shape, dtype=dtype, device=self._dev)
+        C, E, D, A, B, z = self.C, self.E, self.D, self.A, self.B, self._zeros
         self._obs, self._reward, self._discount = z(C, E, D), z(C, E), z(C, E)
         self._step_type, self._action = z(C, E, dtype=torch.int32), z(C, E, A)
         self._logp, self._env_action = z(E), z(E, A, dtype=self._dtype)
-        self._ep_return, self._ep_len = z(E, dtype=torch.float64), z(E, dtype=torch.int32)
-        self._done_return, self._done_len = z(E, dtype=torch.float64), z(E, dtype=torch.int64)
-        self._done_count = z(E, dtype=torch.int32)
         # the minibatch
         self._b_obs, self._b_next, self._b_action = z(B, D), z(B, D), z(B, A)
         self._b_reward, self._b_discount, self._b_mask = z(B), z(B), z(B)
         self._b_next_action, self._b_next_logp, self._b_y = z(B, A), z(B), z(B)
-        # evaluation scratch (`act`): one slot of its own, no statistics
-        self._e_obs, self._e_reward, self._e_discount = z(E, D), z(E), z(E)
-        self._e_step_type, self._e_action, self._e_logp = z(E, dtype=torch.int32), z(E, A), z(E)
-        self._e_env_action = z(E, A, dtype=self._dtype)
-        # the normaliser
-        self._count = 0.0
-        self._mean, self._M2 = z(D, dtype=torch.float64), z(D, dtype=torch.float64)
-        self._mean_f32, self._inv_std_f32 = z(D), torch.ones(D, dtype=torch.float32, device=self._dev)
-        self._keep = None
 
     # -- accessors ---------------------------------------------------------------------------------------------------
-    @property
-    def env(self):
-        return self._env
-
-    @property
-    def observation_keys(self):
-        """The packed observation tensors, in column order."""
-        return list(self._keys)
-
-    @property
-    def normalizer(self):
-        """(count, mean [D] f64, M2 [D] f64, mean_f32 [D], inv_std_f32 [D]) -- live."""
-        return self._count, self._mean, self._M2, self._mean_f32, self._inv_std_f32
-
     @property
     def alpha(self):
         return float(self.log_alpha.detach().exp())
@@ -331,46 +234,6 @@ class SAC:
         return {"obs": self._b_obs, "next_obs": self._b_next, "action": self._b_action, "reward": self._b_reward,
                 "discount": self._b_discount, "mask": self._b_mask, "next_action": self._b_next_action,
                 "next_logp": self._b_next_logp, "y": self._b_y}
-
-    def _stream(self):
-        import torch
-        if self._dev.type != "cuda":
-            raise LearnError("the learner's kernels need a HIP device; there is no CPU fallback")
-        return torch.cuda.current_stream(self._dev).cuda_stream
-
-    @staticmethod
-    def _mlp(net):
-        for layer in (net[0], net[2], net[4]):
-            if not (layer.weight.is_contiguous() and layer.bias.is_contiguous()):
-                raise LearnError("the kernels read contiguous float32 parameters")
-        return mlp_table([t for i in (0, 2, 4) for t in (net[i].weight, net[i].bias)])
-
-    def _table(self, observation):
-        import torch
-        fields = []
-        for k, w in zip(self._keys, self._widths):
-            t = observation[k]
-            if t.dtype not in (torch.float32, torch.float64):
-                raise LearnError(f"observation {k!r} is {t.dtype}: pack takes float32 and float64")
-            if t.shape[0] != self.E or t.numel() != self.E * w or not t.is_contiguous() or t.device != self._dev:
-                raise LearnError(f"observation {k!r}: expected a contiguous [{self.E}, {w}] device tensor, got "
-                                 f"{tuple(t.shape)}")
-            fields.append((t.data_ptr(), w, F32 if t.dtype == torch.float32 else F64))
-        return field_table(fields)
-
-    def _pack(self, ts, slot, st):
-        import torch
-        for name, t in (("reward", ts.reward), ("discount", ts.discount)):
-            if t is not None and (t.dtype != self._dtype or not t.is_contiguous()):
-                raise LearnError(f"the TimeStep's {name} must be a contiguous tensor of the engine's dtype")
-        if ts.step_type.dtype != torch.int32:
-            raise LearnError("the TimeStep's step_type must be int32")
-        pack(self._table(ts.observation), self._precision, ts.step_type.data_ptr(),
-             None if ts.reward is None else ts.reward.data_ptr(), None if ts.discount is None else ts.discount.data_ptr(),
-             self._obs[slot].data_ptr(), self._reward[slot].data_ptr(), self._discount[slot].data_ptr(),
-             self._step_type[slot].data_ptr(), self.E, self.D,
-             stats=(self._ep_return.data_ptr(), self._ep_len.data_ptr(), self._done_return.data_ptr(),
-                    self._done_len.data_ptr(), self._done_count.data_ptr()), hip_stream=st)
 
     def _act(self, obs, n_rows, st, **out):
         act(obs.data_ptr(), self._mean_f32.data_ptr(), self._inv_std_f32.data_ptr(), self.obs_clip, self._mlp(self.actor),
@@ -408,20 +271,13 @@ class SAC:
     def _merge(self, first, end, st):
         """The TimeSteps first .. end - 1 that the ring still holds into the running moments: one launch, two where the
         slots wrap."""
-        C, E = self.C, self.E
+        C = self.C
         first = max(first, end - C)
         while first < end:
             s = first % C
             k = min(end - first, C - s)
-            moments(self._obs[s].data_ptr(), self._mean.data_ptr(), self._M2.data_ptr(), self._mean_f32.data_ptr(),
-                    self._inv_std_f32.data_ptr(), self._count, self.norm_eps, k * E, self.D, hip_stream=st)
-            self._count += float(k * E)
+            self._merge_moments(self._obs[s], k * self.E, st)
             first += k
-
-    def normalize(self, obs):
-        """What the kernels feed the first layer (torch, float32)."""
-        import torch
-        return torch.clamp((obs - self._mean_f32) * self._inv_std_f32, -self.obs_clip, self.obs_clip)
 
     # -- the gradient step ---------------------------------------------------------------------------------------------
     def sample_and_target(self):
@@ -507,26 +363,12 @@ class SAC:
         import torch
         with torch.cuda.device(self._dev):
             st = self._stream()
-            self._e_step_type.fill_(STEP_MID)
-            pack(self._table(observation), self._precision, self._e_step_type.data_ptr(), None, None,
-                 self._e_obs.data_ptr(), self._e_reward.data_ptr(), self._e_discount.data_ptr(),
-                 self._e_step_type.data_ptr(), self.E, self.D, hip_stream=st)
+            self._pack_observation(observation, st)
             self._act(self._e_obs, self.E, st, action=self._e_action.data_ptr(), logp=self._e_logp.data_ptr(),
                       env_action=self._e_env_action.data_ptr(), precision=self._precision, deterministic=deterministic)
             if not deterministic:
                 self._round += 1
-            self._keep = observation   # alive until the pack has run
         return self._e_env_action
-
-    def episode_stats(self):
-        """{"episodes", "mean_return", "mean_length"} of the episodes that ended since the last call (one read-back);
-        the counters start again from zero."""
-        n = int(self._done_count.sum())
-        out = {"episodes": n,
-               "mean_return": float(self._done_return.sum()) / n if n else float("nan"),
-               "mean_length": float(self._done_len.sum()) / n if n else float("nan")}
-        self._done_return.zero_(); self._done_len.zero_(); self._done_count.zero_()
-        return out
 
     # -- checkpoint / resume -------------------------------------------------------------------------------------------
     def state_dict(self, include_replay: bool = False):
@@ -541,14 +383,11 @@ class SAC:
               "log_alpha": c(self.log_alpha),
               "optimizers": {k: copy.deepcopy(getattr(self, k + "_optimizer").state_dict())
                              for k in ("actor", "critic", "alpha")},
-              "normalizer": {"count": self._count, "mean": c(self._mean), "M2": c(self._M2),
-                             "mean_f32": c(self._mean_f32), "inv_std_f32": c(self._inv_std_f32)},
+              "normalizer": self._normalizer_state(),
               "seed": self.seed, "round": self._round, "n_written": self.n_written, "generator": self._gen.get_state(),
               "newest": {"obs": c(self._obs[newest]), "reward": c(self._reward[newest]),
                          "discount": c(self._discount[newest]), "step_type": c(self._step_type[newest])},
-              "episodes": {"ep_return": c(self._ep_return), "ep_len": c(self._ep_len),
-                           "done_return": c(self._done_return), "done_len": c(self._done_len),
-                           "done_count": c(self._done_count)}}
+              "episodes": self._episodes_state()}
         if include_replay:
             sd["replay"] = {k: c(v) for k, v in self.ring().items()}
         return sd
@@ -565,11 +404,7 @@ class SAC:
             self.log_alpha.copy_(sd["log_alpha"])
         for k, s in sd["optimizers"].items():
             getattr(self, k + "_optimizer").load_state_dict(copy.deepcopy(s))   # (Adam would adopt sd's own tensors)
-        nz = sd["normalizer"]
-        self._count = float(nz["count"])
-        for dst, key in ((self._mean, "mean"), (self._M2, "M2"), (self._mean_f32, "mean_f32"),
-                         (self._inv_std_f32, "inv_std_f32")):
-            dst.copy_(nz[key])
+        self._load_shared_state(sd)
         self.seed, self._round, self.n_written = int(sd["seed"]), int(sd["round"]), int(sd["n_written"])
         self._gen.set_state(sd["generator"])
         if "replay" in sd:
@@ -581,8 +416,6 @@ class SAC:
         for buf, key in ((self._obs, "obs"), (self._reward, "reward"), (self._discount, "discount"),
                          (self._step_type, "step_type")):
             buf[newest].copy_(sd["newest"][key])
-        for key, v in sd["episodes"].items():
-            getattr(self, "_" + key).copy_(v)
 
 
 def train_and_evaluate(env, rounds: int, steps_per_round: int = 16, grad_steps: int = 4, time_limit: float = None,
@@ -590,37 +423,7 @@ def train_and_evaluate(env, rounds: int, steps_per_round: int = 16, grad_steps: 
     """What the examples' --train-sac does: `rounds` rounds of SAC on `env` (a batched Environment), one line per round
     with the mean return of the episodes that ended in it, then one deterministic episode of every env through a
     MidiEvaluationWrapper.  Stops early after `time_limit` seconds.  Returns (sac, log of the rounds, metrics)."""
-    import time
-    import torch
-    from robopianist_amd.wrappers import CanonicalSpecWrapper, MidiEvaluationWrapper
     sac = SAC(env, **sac_kwargs)
-    t0 = time.perf_counter()
-    rounds_log = []
-    last_mean = [float("nan")]
-
-    def report(i, s):
-        rounds_log.append(s)
-        if s["episodes"]:
-            last_mean[0] = s["mean_return"]
-        # (a round in which no episode ended shows the mean of the last round in which some did)
-        log(f"update {i + 1:4d}  episodes {s['episodes']:6d}  mean return {last_mean[0]:10.4f}  "
-            f"mean reward {s['mean_reward']:8.4f}  alpha {s.get('alpha', float('nan')):8.5f}  "
-            f"{time.perf_counter() - t0:7.1f} s")
-
-    for i in range(int(rounds)):
-        sac.train(1, steps_per_round, grad_steps, callback=lambda _, s, i=i: report(i, s))
-        if time_limit is not None and time.perf_counter() - t0 > time_limit:
-            log(f"stopped after {i + 1} updates: the time limit of {time_limit:.0f} s")
-            break
-    evaluated = CanonicalSpecWrapper(MidiEvaluationWrapper(sac.env))
-    ts = evaluated.reset()
-    done = torch.zeros(sac.E, dtype=torch.bool, device=ts.step_type.device)
-    for _ in range(100000):
-        ts = evaluated.step(sac.act(ts.observation, deterministic=True))
-        done |= ts.last()
-        if bool(done.all()):
-            break
-    metrics = evaluated.get_musical_metrics()
-    for k, v in metrics.items():
-        log(f"\t{k}: {v:.4f}")
+    train_one = lambda cb: sac.train(1, steps_per_round, grad_steps, callback=cb)
+    rounds_log, metrics = _train_and_evaluate(sac, rounds, train_one, ("alpha", "alpha"), time_limit, log)
     return sac, rounds_log, metrics

@@ -14,6 +14,8 @@ import os
 
 import numpy as np
 
+from robopianist_amd import _abi
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("RP_PLAN_LIB") or os.path.join(_HERE, "csrc", "librp_plan.so")
 
@@ -76,62 +78,22 @@ _ARGS = {"fork": ForkArgs, "sample": SampleArgs, "action": ActionArgs, "accumula
          "shift": ShiftArgs}
 
 
-def declare(L, prefix: str = "rp_plan_"):
-    """Declares the ABI's prototypes on a loaded library whose symbols start with `prefix`."""
-    f = lambda name: getattr(L, prefix + name)
-    f("last_error").restype = ctypes.c_char_p
-    f("dim").argtypes = [ctypes.c_char_p]
-    for name, cls in _ARGS.items():
-        f(name).argtypes = [ctypes.POINTER(cls)]
-    return L
-
-
 def load_library(path: str = LIB_PATH):
     """Loads librp_plan.so; raises PlanError if it has not been built."""
     global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(path):
-        raise PlanError(
-            f"HIP planner library not found at {path}. Build it with "
-            "`python -c 'import __graft_entry__ as g; g.build()'` (hipcc, gfx950). "
-            "There is no CPU fallback.")
-    try:   # torch's HIP runtime first, as in engine.load_library
-        import torch  # noqa: F401
-    except ImportError:
-        pass
-    _lib = declare(ctypes.CDLL(path))
+    if _lib is None:
+        _lib = declare(_abi.open_library(path, "planner", PlanError))
     return _lib
 
 
-def make_args(entry: str, **values):
-    """A filled argument block of entry point `entry` ("fork", ...); fields that are not named stay zero / NULL."""
-    a = _ARGS[entry]()
-    a.struct_size = ctypes.sizeof(a)
-    for k, v in values.items():
-        if k not in dict((f[0], 0) for f in a._fields_):
-            raise TypeError(f"rp_plan_{entry}_args has no field {k!r}")
-        setattr(a, k, v)
-    return a
+_entries = _abi.EntryTable("rp_plan_", _ARGS, PlanError, load_library)
+make_args, call_raw, last_error, dim, _call = (_entries.make_args, _entries.call_raw, _entries.last_error, _entries.dim,
+                                               _entries.call)
 
 
-def call_raw(entry: str, args) -> int:
-    """The C return code of rp_plan_<entry>(&args) (see last_error())."""
-    return getattr(load_library(), "rp_plan_" + entry)(ctypes.byref(args))
-
-
-def last_error() -> str:
-    return load_library().rp_plan_last_error().decode()
-
-
-def dim(name: str) -> int:
-    return load_library().rp_plan_dim(name.encode())
-
-
-def _call(entry: str, **values) -> None:
-    args = make_args(entry, **values)
-    if call_raw(entry, args) != 0:
-        raise PlanError(last_error())
+def declare(L, prefix: str = "rp_plan_"):
+    """Declares the ABI's prototypes on a loaded library whose symbols start with `prefix`."""
+    return _entries.declare(L, prefix)
 
 
 def field_table(fields):
@@ -151,9 +113,9 @@ def fork(table, G, K, env_first=0, env_count=None, hip_stream=None):
 
 
 def sample(nominal, sigma, lo, hi, knots, seed, round_, G, K, P, nu, env_first=0, env_count=None, hip_stream=None):
-    _call("sample", nominal=nominal, sigma=sigma, lo=lo, hi=hi, knots=knots, seed_lo=int(seed) & 0xFFFFFFFF,
-          seed_hi=(int(seed) >> 32) & 0xFFFFFFFF, round=int(round_) & 0xFFFFFFFF, G=G, K=K, P=P, nu=nu, env_first=env_first,
-          env_count=G * K - env_first if env_count is None else env_count, hip_stream=hip_stream)
+    _call("sample", nominal=nominal, sigma=sigma, lo=lo, hi=hi, knots=knots, G=G, K=K, P=P, nu=nu,
+          env_first=env_first, env_count=G * K - env_first if env_count is None else env_count, hip_stream=hip_stream,
+          **_abi.seed_args(seed, round_))
 
 
 def action(knots, out, precision, spline, h, H, P, nu, n_rows, row_first=0, row_count=None, hip_stream=None):

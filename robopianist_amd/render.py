@@ -12,6 +12,7 @@ import os
 
 import numpy as np
 
+from robopianist_amd import _abi
 from robopianist_amd.model import cameras, render_tables
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -68,16 +69,7 @@ def load_library(path: str = LIB_PATH):
     global _lib
     if _lib is not None:
         return _lib
-    if not os.path.exists(path):
-        raise RenderError(
-            f"HIP render library not found at {path}. Build it with "
-            "`python -c 'import __graft_entry__ as g; g.build()'` (hipcc, gfx950). "
-            "There is no CPU fallback.")
-    try:   # torch's HIP runtime first, as in engine.load_library
-        import torch  # noqa: F401
-    except ImportError:
-        pass
-    L = ctypes.CDLL(path)
+    L = _abi.open_library(path, "render", RenderError)
     L.rp_render_last_error.restype = ctypes.c_char_p
     L.rp_render_create.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                    ctypes.POINTER(ctypes.c_void_p)]

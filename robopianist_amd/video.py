@@ -18,6 +18,8 @@ from typing import Optional, Sequence, Tuple, Union
 
 import numpy as np
 
+from robopianist_amd import _abi
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("RP_VIDEO_LIB") or os.path.join(_HERE, "csrc", "librp_video.so")
 
@@ -72,17 +74,7 @@ def load_library(path: Optional[str] = None):
     global _lib
     if _lib is not None and path is None:
         return _lib
-    p = LIB_PATH if path is None else path
-    if not os.path.exists(p):
-        raise VideoError(
-            f"HIP video library not found at {p}. Build it with "
-            "`python -c 'import __graft_entry__ as g; g.build()'` (hipcc, gfx950). "
-            "There is no CPU fallback.")
-    try:   # torch's HIP runtime first, as in engine.load_library
-        import torch  # noqa: F401
-    except ImportError:
-        pass
-    L = ctypes.CDLL(p)
+    L = _abi.open_library(LIB_PATH if path is None else path, "video", VideoError)
     declare(L)
     if path is None:
         _lib = L

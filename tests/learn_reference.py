@@ -9,6 +9,7 @@ twin (plan_reference.z).
 
 from __future__ import annotations
 
+import hashlib
 import math
 
 import numpy as np
@@ -168,3 +169,34 @@ def moments(obs, count, mean, M2, eps):
     nb, mb, Mb = batch_moments(obs)
     n, mean, M2 = chan_merge(count, np.asarray(mean, np.float64), np.asarray(M2, np.float64), nb, mb, Mb)
     return (n, mean, M2) + publish(n, mean, M2, eps)
+
+
+# ---- a learner's checkpoint, as the layout tests of PPO and SAC compare it ------------------------------------------------
+def state_tree(x):
+    """The key tree of a state dict: tensors as (dtype, shape), other leaves as their type's name."""
+    import torch
+    if isinstance(x, torch.Tensor):
+        return (str(x.dtype), tuple(x.shape))
+    if isinstance(x, dict):
+        return {k: state_tree(v) for k, v in x.items()}
+    if isinstance(x, (list, tuple)):
+        return [state_tree(v) for v in x]
+    return type(x).__name__
+
+
+def adam_tree(sd):
+    """Of an optimizer's state dict, what is this project's: the state's keys and the parameter groups' indices."""
+    return {"state": state_tree(sd["state"]), "params": [g["params"] for g in sd["param_groups"]]}
+
+
+def digest(tensors):
+    h = hashlib.sha256()
+    for t in tensors:
+        h.update(t.detach().cpu().numpy().tobytes())
+    return h.hexdigest()
+
+
+def mlp_tree(n_in, n_out, H1=16, H2=32):
+    f = "torch.float32"
+    return {"0.weight": (f, (H1, n_in)), "0.bias": (f, (H1,)), "2.weight": (f, (H2, H1)), "2.bias": (f, (H2,)),
+            "4.weight": (f, (n_out, H2)), "4.bias": (f, (n_out,))}

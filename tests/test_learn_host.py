@@ -345,3 +345,28 @@ def test_one_update_on_a_twin_made_rollout_changes_every_parameter():
         learning.PPO(_SpecEnv(E, (4, 3), A), hidden=(20, 32))
     with pytest.raises(ValueError, match="step_canonical"):
         learning.PPO(object())
+
+
+# ---- the checkpoint's layout and the initial parameters -------------------------------------------------------------------------
+def test_state_dict_layout_and_initial_parameters_are_pinned():
+    """Two instances of the same code agree whatever the code does; this compares with literals.  The digest was
+    recorded by running these lines at the commit before the learners got their common base class."""
+    E, D, A = 4, 7, 3
+    ppo = learning.PPO(_SpecEnv(E, (4, 3), A), hidden=(16, 32), horizon=2, seed=5)
+    sd = ppo.state_dict()
+    f32, f64, i32, i64 = "torch.float32", "torch.float64", "torch.int32", "torch.int64"
+    assert {k: lr.adam_tree(v) if k == "optimizer" else lr.state_tree(v) for k, v in sd.items()} == {
+        "actor": lr.mlp_tree(D, A), "critic": lr.mlp_tree(D, 1), "log_std": (f32, (A,)),
+        "optimizer": {"state": {}, "params": [list(range(13))]},
+        "normalizer": {"count": "float", "mean": (f64, (D,)), "M2": (f64, (D,)), "mean_f32": (f32, (D,)),
+                       "inv_std_f32": (f32, (D,))},
+        "seed": "int", "round": "int", "started": "bool",
+        "last": {"obs": (f32, (E, D)), "reward": (f32, (E,)), "discount": (f32, (E,)), "step_type": (i32, (E,)),
+                 "value": (f32, (E,))},
+        "episodes": {"ep_return": (f64, (E,)), "ep_len": (i32, (E,)), "done_return": (f64, (E,)), "done_len": (i64, (E,)),
+                     "done_count": (i32, (E,))}}
+    assert list(sd) == ["actor", "critic", "log_std", "optimizer", "normalizer", "seed", "round", "started", "last",
+                        "episodes"]
+    if torch.__version__ == "2.10.0+rocm7.0":   # (the initialisers' draws belong to torch)
+        assert lr.digest(list(sd["actor"].values()) + list(sd["critic"].values()) + [sd["log_std"]]) == \
+            "51a8854c8c0090ab0e528c5f76e4b64d00150c068d01856d281a2406ec59939b"

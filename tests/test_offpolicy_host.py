@@ -365,3 +365,36 @@ def test_one_gradient_step_changes_every_parameter_and_moves_the_targets_by_tau(
         offpolicy.SAC(object())
     with pytest.raises(offpolicy.LearnError, match="collect"):
         fresh.update()
+
+
+# ---- the checkpoint's layout and the initial parameters -------------------------------------------------------------------------
+def test_state_dict_layout_and_initial_parameters_are_pinned():
+    """Two instances of the same code agree whatever the code does; this compares with literals.  The digest was
+    recorded by running these lines at the commit before the learners got their common base class."""
+    E, D, A, C = 4, 7, 3, 4
+    sac = offpolicy.SAC(_SpecEnv(E, (4, 3), A), hidden=(16, 32), n_critics=3, capacity=C, batch_size=8, seed=5)
+    f32, f64, i32, i64 = "torch.float32", "torch.float64", "torch.int32", "torch.int64"
+    expected = {
+        "actor": lr.mlp_tree(D, 2 * A), "critics": [lr.mlp_tree(D + A, 1)] * 3, "targets": [lr.mlp_tree(D + A, 1)] * 3,
+        "log_alpha": (f32, (1,)),
+        "optimizers": {"actor": {"state": {}, "params": [list(range(6))]},
+                       "critic": {"state": {}, "params": [list(range(18))]},
+                       "alpha": {"state": {}, "params": [[0]]}},
+        "normalizer": {"count": "float", "mean": (f64, (D,)), "M2": (f64, (D,)), "mean_f32": (f32, (D,)),
+                       "inv_std_f32": (f32, (D,))},
+        "seed": "int", "round": "int", "n_written": "int", "generator": ("torch.uint8", (5056,)),
+        "newest": {"obs": (f32, (E, D)), "reward": (f32, (E,)), "discount": (f32, (E,)), "step_type": (i32, (E,))},
+        "episodes": {"ep_return": (f64, (E,)), "ep_len": (i32, (E,)), "done_return": (f64, (E,)), "done_len": (i64, (E,)),
+                     "done_count": (i32, (E,))}}
+    replay = {"obs": (f32, (C, E, D)), "reward": (f32, (C, E)), "discount": (f32, (C, E)), "step_type": (i32, (C, E)),
+              "action": (f32, (C, E, A))}
+    for include_replay in (False, True):
+        sd = sac.state_dict(include_replay=include_replay)
+        want = dict(expected, replay=replay) if include_replay else expected
+        assert {k: {n: lr.adam_tree(o) for n, o in v.items()} if k == "optimizers" else lr.state_tree(v)
+                for k, v in sd.items()} == want
+        assert list(sd) == list(want)
+    if torch.__version__ == "2.10.0+rocm7.0":   # (the initialisers' draws belong to torch)
+        params = [sd["actor"]] + sd["critics"] + sd["targets"]
+        assert lr.digest([v for m in params for v in m.values()] + [sd["log_alpha"]]) == \
+            "4171ee497d8533ae8ed74d6524f952a590fbcc1f1ce401fde65a762ac6694d1d"

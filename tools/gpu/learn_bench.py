@@ -98,7 +98,7 @@ def main():
 
     ts_kept = env.step_canonical(ua, bounds, False)
     st = torch.cuda.current_stream(dev).cuda_stream
-    actor, critic = ppo._nets()
+    actor, critic = ppo._mlp(ppo.actor), ppo._mlp(ppo.critic)
 
     def acts(n=2000):
         for _ in range(n):
