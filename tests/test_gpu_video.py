@@ -98,6 +98,167 @@ def test_a_small_cap_reports_the_need_and_writes_nothing_past_it():
     assert int(length[0]) == len(want) and out[0].cpu().numpy().tobytes() == want
 
 
+def _awkward_caps(case):
+    """{what: bytes_cap} from the restatement's bytes alone: the caps that fall on the bytes a store of two (a 0xFF
+    and its stuffed zero, the two bytes of a marker) or a store by another lane or kernel (the header, a seam byte, a
+    segment placed in a later round of the layout) can get wrong."""
+    want, st = vr.case_reference(case)
+    head = len(vr.header(case[1][0], case[1][1], case[2]))
+    seg_at, zeros = st["seg_at"], st["stuffed_at"]
+    caps = {"header - 1": head - 1, "header": head, "header + 1": head + 1}
+    assert zeros, "no stuffed byte in this case"
+    for name, z in (("first", zeros[0]), ("last", zeros[-1])):
+        assert want[z - 1] == 0xFF and want[z] == 0
+        caps[f"{name} stuffed zero"] = z            # the 0xFF is written, its zero is not
+        caps[f"{name} stuffed zero + 1"] = z + 1
+    if st["group_edge_at"]:
+        caps["stuffed zero of lane 63"] = st["group_edge_at"][0] + 1
+    # the markers: a restart marker where there is one, the end of image where the frame is one segment
+    # the markers: restart markers 0 and 7 (after which the count wraps) and the one before segment 64; the end of image
+    for s in sorted({0, 7, 63, st["segments"] - 1}):
+        if s < st["segments"]:
+            m = seg_at[s + 1] - 2
+            assert want[m] == 0xFF and want[m + 1] == (0xD9 if s == st["segments"] - 1 else 0xD0 + s % 8)
+            caps[f"marker of segment {s}, second byte"] = m + 1   # the 0xFF is written, the number is not
+            caps[f"marker of segment {s}, first byte"] = m
+    for k, at in enumerate(st["seam_at"]):
+        caps[f"seam byte {k}"] = at
+        caps[f"seam byte {k} + 1"] = at + 1
+    for k, z in enumerate(st["seam_prev_at"]):
+        assert want[z - 1] == 0xFF and want[z] == 0
+        caps[f"stuffed zero {k} that ends a chunk"] = z
+        caps[f"stuffed zero {k} that ends a chunk, + 1"] = z + 1
+    if st["segments"] > 64:
+        caps["first byte of segment 64"] = seg_at[64]
+        caps["first byte of segment 64, + 1"] = seg_at[64] + 1
+    assert all(0 < c < len(want) for c in caps.values())
+    return caps
+
+
+AWKWARD_CASES = (vr.SEAM_FF_CASE, vr.SEAM_PREV_FF_CASE, ("noise", (520, 8), 100, 0))
+
+
+@pytest.mark.parametrize("case", AWKWARD_CASES, ids=vr.case_id)
+def test_caps_on_the_awkward_bytes(case):
+    """Every cap of _awkward_caps, alone and as the middle row of three (frame_first = 1, frame_count = 1): the need is
+    reported, the row holds the file up to the cap, and nothing else changes: neither the guard behind the row, nor the
+    neighbouring rows, nor their lengths."""
+    want, st = vr.case_reference(case)
+    (H, W), quality = case[1], case[2]
+    caps = _awkward_caps(case)
+    if case == vr.SEAM_FF_CASE:
+        assert st["seam_ff"] and any(want[at] == 0xFF and caps[f"seam byte {k} + 1"] == at + 1 for k, at in enumerate(st["seam_at"]))
+    elif case == vr.SEAM_PREV_FF_CASE:
+        assert "stuffed zero 0 that ends a chunk" in caps and "marker of segment 7, second byte" in caps
+    else:
+        assert st["segments"] == 65 and "first byte of segment 64" in caps and "stuffed zero of lane 63" in caps
+    image = np.array(vr.case_image(case))
+    one = video.Encoder(H, W, 1, quality=quality)
+    three = video.Encoder(H, W, 3, quality=quality)
+    rgb1 = torch.as_tensor(image[None], device=_dev())
+    rgb3 = torch.as_tensor(np.stack([vr.noise(H, W, 101), image, vr.noise(H, W, 102)]), device=_dev())
+    stream = torch.cuda.current_stream().cuda_stream
+    for what, cap in caps.items():
+        guard = torch.full((cap + 4096,), 0x5A, dtype=torch.uint8, device=_dev())
+        length = torch.zeros(1, dtype=torch.int32, device=_dev())
+        a = video.make_args(0, 1, cap, rgb=rgb1.data_ptr(), out_bytes=guard.data_ptr(), length=length.data_ptr(), hip_stream=stream)
+        assert one.encode_raw(a) == 0, one.last_error()
+        torch.cuda.synchronize()
+        g = guard.cpu().numpy()
+        assert int(length[0]) == -len(want), what
+        assert g[:cap].tobytes() == want[:cap], f"{what}: cap {cap}"
+        assert (g[cap:] == 0x5A).all(), f"{what}: cap {cap}, written at {cap + int(np.flatnonzero(g[cap:] != 0x5A)[0])}"
+        # the middle row of three
+        guard = torch.full((3 * cap + 4096,), 0x5A, dtype=torch.uint8, device=_dev())
+        length = torch.full((3,), -7, dtype=torch.int32, device=_dev())
+        a = video.make_args(1, 1, cap, rgb=rgb3.data_ptr(), out_bytes=guard.data_ptr(), length=length.data_ptr(), hip_stream=stream)
+        assert three.encode_raw(a) == 0, three.last_error()
+        torch.cuda.synchronize()
+        g = guard.cpu().numpy()
+        assert length.cpu().tolist() == [-7, -len(want), -7], what
+        assert g[cap:2 * cap].tobytes() == want[:cap], f"{what}: cap {cap}, row 1 of 3"
+        assert (g[:cap] == 0x5A).all() and (g[2 * cap:] == 0x5A).all(), f"{what}: cap {cap}, a neighbouring row was written"
+
+
+def test_a_mixed_batch_across_two_rounds_of_segments():
+    """Four frames of 65 segments in one call, all of different lengths: each frame's segments 64 are placed by its own
+    carried sum.  Then a window against poisoned rows, and a second run."""
+    cases = [("flat", (520, 8), 90, 0), ("noise", (520, 8), 90, 0), ("noise", (520, 8), 90, 7), ("block_checkerboard", (520, 8), 90, 0)]
+    wants = [vr.case_reference(c)[0] for c in cases]
+    assert len({len(w) for w in wants}) == 4
+    enc = video.Encoder(520, 8, 4, quality=90)
+    assert enc._L.rp_video_dim(enc._h, b"segments") == 65 and enc._L.rp_video_dim(enc._h, b"chunk_blocks") == vr.CHUNK_BLOCKS
+    rgb = torch.as_tensor(np.stack([vr.case_image(c) for c in cases]), device=_dev())
+    out, length = enc.encode(rgb)
+    torch.cuda.synchronize()
+    first = (out.clone(), length.clone())
+    o, n = out.cpu().numpy(), length.cpu().numpy()
+    for f, want in enumerate(wants):
+        assert n[f] == len(want), f"frame {f}: length {n[f]}, the restatement has {len(want)}"
+        got = o[f, :n[f]].tobytes()
+        if got != want:
+            at = next(i for i in range(n[f]) if got[i] != want[i])
+            raise AssertionError(f"frame {f}: first differing byte at {at} of {n[f]} (header {len(enc.header)})")
+        assert not o[f, n[f]:].any()
+    out.zero_(); length.zero_()
+    enc.encode(rgb)
+    torch.cuda.synchronize()
+    assert torch.equal(out, first[0]) and torch.equal(length, first[1])
+    out.fill_(0xA5); length.fill_(-7)
+    enc.encode(rgb, frame_first=1, frame_count=2)
+    torch.cuda.synchronize()
+    o, n = out.cpu().numpy(), length.cpu().numpy()
+    for f, want in enumerate(wants):
+        if f in (1, 2):
+            assert n[f] == len(want) and o[f, :n[f]].tobytes() == want and (o[f, n[f]:] == 0xA5).all()
+        else:
+            assert n[f] == -7 and (o[f] == 0xA5).all()
+
+
+def test_rows_beyond_four_gib_of_output():
+    """8 x 344 at quality 100 with bytes_cap = max_bytes (54,167): 79,300 frames are 2^32 bytes of rows and eight rows
+    more, so a row offset formed in 32 bits puts the later frames on top of the first ones.  Frame f is image f % 7 of
+    a bank of seven; every length is compared on the device, and the frames at both ends and on either side of the
+    2^32th byte byte for byte.  (`rgb` is 0.65 GB and the coefficients 1.3 GB: only `bytes` crosses 2^32.  On an
+    MI355X the test takes 0.3 s.)"""
+    import time
+    H, W, quality = 8, 344, 100
+    cap = vr.max_bytes(H, W, quality)
+    N = -(-2 ** 32 // cap) + 8
+    bank = [vr.noise(H, W, 1), vr.noise(H, W, 2), vr.saturated(H, W, 0), vr.block_checkerboard(H, W), vr.flat(H, W),
+            vr.rendered_like(H, W), vr.gradient(H, W)]
+    wants = [vr.encode(img, quality) for img in bank]
+    assert len({len(w) for w in wants}) == 7
+    below = (2 ** 32 - 1) // cap            # the last row that starts below 2^32
+    assert below * cap < 2 ** 32 <= (below + 1) * cap and below + 1 < N - 1
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    enc = video.Encoder(H, W, N, quality=quality)
+    assert enc.max_bytes == cap
+    index = torch.arange(N, device=_dev()) % 7
+    rgb = torch.as_tensor(np.stack(bank), device=_dev())[index].contiguous()
+    out, length = enc.encode(rgb)
+    torch.cuda.synchronize()
+    t1 = time.perf_counter()
+    try:
+        assert out.shape == (N, cap) and out.numel() > 2 ** 32
+        table = torch.tensor([len(w) for w in wants], dtype=torch.int32, device=_dev())
+        wrong = torch.nonzero(length != table[index]).flatten()
+        assert wrong.numel() == 0, f"{wrong.numel()} wrong lengths, the first at frame {int(wrong[0])}"
+        for f in (0, 1, below, below + 1, N - 1):
+            want = wants[f % 7]
+            row = out[f].cpu().numpy()
+            assert row[:len(want)].tobytes() == want, f"frame {f}"
+            assert not row[len(want):].any(), f"frame {f}: bytes past the file were written"
+    finally:
+        del out, length, rgb
+        enc._out.clear()
+        del enc
+        torch.cuda.empty_cache()
+    print(f"{N} frames of {H} x {W}, rows of {cap} bytes: create, build rgb and encode took {t1 - t0:.3f} s, "
+          f"the whole test {time.perf_counter() - t0:.3f} s")
+
+
 def test_refusals_launch_nothing():
     for bad in (dict(height=0), dict(width=0), dict(quality=0), dict(quality=101), dict(max_frames=0), dict(height=65536)):
         kw = dict(height=8, width=8, max_frames=1, quality=90)
@@ -175,6 +336,26 @@ def test_render_jpeg_equals_the_restatement_of_the_rendered_image():
     only = physics.render_jpeg(30, 44, "piano/back", quality=90, key_rgb=key_rgb, envs=[1])
     assert only == [files[1]]
     assert physics.render_jpeg(30, 44, "piano/back", quality=30, key_rgb=key_rgb)[0] == vr.encode(images[0], 30)
+
+
+def test_render_jpeg_of_a_tall_frame_equals_the_restatement():
+    """The caller's route through more than 64 segments: 520 x 8, two envs with different keys."""
+    env = _scene_env(2)
+    env.reset()
+    physics = env.physics
+    key_rgb = torch.zeros((2, 88, 3), dtype=torch.uint8, device=physics.device)
+    key_rgb[0] = 230
+    key_rgb[1, ::2] = torch.tensor([30, 200, 60], dtype=torch.uint8, device=physics.device)
+    files = physics.render_jpeg(520, 8, "piano/back", quality=90, key_rgb=key_rgb)
+    images = physics.render(520, 8, "piano/back", key_rgb=key_rgb).cpu().numpy()
+    assert len(files) == 2 and images.shape == (2, 520, 8, 3)
+    for e in range(2):
+        st = {}
+        assert files[e] == vr.encode(images[e], 90, st), f"env {e}"
+        assert st["segments"] == 65
+        im = vr.decode(files[e])
+        assert im.size == (8, 520) and im.mode == "RGB"
+        assert vr.psnr(np.asarray(im), images[e]) > 25.0
 
 
 def _riff_chunks(data):

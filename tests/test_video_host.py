@@ -73,6 +73,10 @@ def test_host_build_equals_the_restatement_and_pillow_decodes_it(case):
     assert im.size == (case[1][1], case[1][0]) and im.mode == "RGB"
     if case[0] in ("flat", "block_checkerboard") and case[2] == 100:
         assert (np.asarray(im) == vr.case_image(case)).all(), "quality 100 keeps a flat or block-wise flat image exactly"
+    if case in vr.TALL_CASES:
+        # a decoder that is not ours follows the restart markers over 65 and 129 segments: one out of sequence, or a
+        # segment out of place, and it decodes something else from there on (the floor is render_jpeg's)
+        assert vr.psnr(np.asarray(im), vr.case_image(case)) > 25.0
 
 
 def test_exact_decoding_cases_are_in_the_list():
@@ -93,7 +97,7 @@ def test_the_cases_are_what_they_claim():
     blocks = {s["segment_blocks"] for s in stats}
     hv = vr.HostVideo(8, 8, 1, 90)
     chunk = hv._L.rpvh_dim(hv._h, b"chunk_blocks")
-    assert chunk == 64
+    assert chunk == 64 == vr.CHUNK_BLOCKS, "the restatement counts its seams with the library's chunk size"
     assert any(b > chunk for b in blocks) and any(b > 2 * chunk for b in blocks), "no segment longer than a chunk"
     assert chunk - 1 in blocks, "63 blocks: one short of a chunk (3 blocks per tile, so 64 itself cannot occur)"
     assert not any(b == chunk for b in blocks) and chunk % 3 != 0
@@ -101,6 +105,36 @@ def test_the_cases_are_what_they_claim():
     # the extremes sit on the segments that cross a chunk, too
     long_noise = vr.case_reference(("noise", (80, 176), 100, 1))[1]
     assert long_noise["no_eob"] and long_noise["stuffed"] and long_noise["segments"] == 10
+    # the layout's rounds of 64 segments: a second and a third round, and sizes that differ along the frame, so that a
+    # segment placed by a wrong sum lands on other bytes
+    assert any(s["segments"] > 64 for s in stats) and any(s["segments"] > 128 for s in stats)
+    for case in vr.TALL_CASES:
+        st = vr.case_reference(case)[1]
+        sizes = np.diff(st["seg_at"])
+        assert st["segments"] > 64 and len(sizes) == st["segments"]
+        assert len(set(sizes.tolist())) > 4 and len(set(sizes[:64].tolist())) > 4, vr.case_id(case)
+    assert {vr.case_reference(c)[1]["segments"] for c in vr.TALL_CASES} == {65, 129}
+    assert max(s["chunks"] for s in stats) >= 7, "bits are carried six times in no case"
+    assert any(s["chunks"] >= 7 and s["segments"] >= 3 for s in stats), "many chunks in many segments"
+    # what can fall on a seam between two chunks
+    for event in ("seam_ff", "seam_aligned", "seam_prev_ff", "group_edge_ff"):
+        assert any(s[event] for s in stats), f"no case with {event}"
+    assert vr.case_reference(vr.SEAM_FF_CASE)[1]["seam_ff"] == 1
+    assert vr.case_reference(vr.SEAM_ALIGNED_CASE)[1]["seam_aligned"] == 1
+    assert vr.case_reference(vr.SEAM_PREV_FF_CASE)[1]["seam_prev_ff"] == 1
+    assert vr.case_reference(("noise", (80, 176), 100, 1))[1]["group_edge_ff"] == 7
+    assert vr.search_seam_seed("seam_ff", (8, 344), 100, 8) == vr.SEAM_FF_CASE[3], "how the seed was found"
+    assert vr.search_seam_seed("seam_aligned", (8, 344), 100, 8) == vr.SEAM_ALIGNED_CASE[3]
+    assert vr.search_seam_seed("seam_prev_ff", (80, 176), 98, 12) == vr.SEAM_PREV_FF_CASE[3]
+    # how full a chunk's bit buffer gets: the dense cases fill it further than anything before them, and furthest of all
+    before = max(vr.case_reference(c)[1]["max_chunk_bits"] for c in vr.base_case_list())
+    others = max(vr.case_reference(c)[1]["max_chunk_bits"] for c in ALL_CASES if c not in vr.DENSE_CASES)
+    for case in vr.DENSE_CASES:
+        st = vr.case_reference(case)[1]
+        print(f"{vr.case_id(case)}: max_block_bits {st['max_block_bits']}, max_chunk_bits {st['max_chunk_bits']} "
+              f"(before: {before}, the other cases: {others})")
+        assert st["max_chunk_bits"] > before and st["max_chunk_bits"] > others
+    assert max(s["max_block_bits"] for s in stats) == max(vr.case_reference(c)[1]["max_block_bits"] for c in vr.DENSE_CASES)
 
 
 def test_fidelity_against_libjpeg():

@@ -165,8 +165,53 @@ def _value_bits(v, s):
     return (v if v >= 0 else v + (1 << s) - 1) & ((1 << s) - 1)
 
 
-def encode(rgb, quality, stats=None) -> bytes:
-    """The JPEG file of one image.  `stats` (a dict) collects what the symbol stream contains."""
+CHUNK_BLOCKS = 64   # blocks the device codes side by side (rp_video_dim "chunk_blocks"; the host test compares the two)
+
+
+def _chunk_stats(st, data, ends, start, chunk_blocks):
+    """What one segment adds to the chunk counters of `stats`.  `data` are the segment's bytes before stuffing (padded),
+    `ends` the bit count after each of its blocks, `start` the file offset of data[0].  Chunk j holds blocks
+    [j chunk_blocks, (j + 1) chunk_blocks); its whole bytes are data[lo:hi], with lo where the previous chunk's whole
+    bytes ended and hi = (bits up to its end) // 8; the bits behind them are carried.  The last chunk takes the pad."""
+    raw = np.frombuffer(data, np.uint8)
+    is_ff = raw == 0xFF
+    at = start + np.arange(len(raw)) + np.concatenate([[0], np.cumsum(is_ff)[:-1]])   # file offset of each data byte
+    st["stuffed_at"] += [int(x) + 1 for x in at[is_ff]]
+    st["max_block_bits"] = max(st["max_block_bits"], int(np.diff([0] + ends).max()))
+    edges = [ends[min(k + chunk_blocks, len(ends)) - 1] for k in range(0, len(ends), chunk_blocks)]
+    edges[-1] = 8 * len(raw)
+    st["chunks"] = max(st["chunks"], len(edges))
+    lo = 0
+    for j, end in enumerate(edges):
+        hi = end // 8
+        # what the chunk's bit buffer holds: the carried bits, the chunk's own and (last chunk) the pad
+        st["max_chunk_bits"] = max(st["max_chunk_bits"], end - 8 * lo)
+        st["group_edge_ff"] += int(is_ff[lo + 63:hi:64].sum())
+        st["group_edge_at"] += [int(x) for x in at[lo + 63:hi:64][is_ff[lo + 63:hi:64]]]
+        if j < len(edges) - 1:
+            assert hi > lo
+            if end % 8 == 0:
+                st["seam_aligned"] += 1
+            else:
+                st["seam_at"].append(int(at[hi]))
+                st["seam_ff"] += bool(is_ff[hi])
+            st["seam_prev_ff"] += bool(is_ff[hi - 1])
+            if is_ff[hi - 1]:
+                st["seam_prev_at"].append(int(at[hi - 1]) + 1)
+        lo = hi
+
+
+def encode(rgb, quality, stats=None, chunk_blocks=CHUNK_BLOCKS) -> bytes:
+    """The JPEG file of one image.  `stats` (a dict) collects what the symbol stream contains: counts of the symbols
+    and, from the symbol stream alone, of what falls on the seams between chunks of `chunk_blocks` blocks:
+      seam_ff        bytes that hold bits of two chunks and equal 0xFF
+      seam_aligned   chunks (but the last of a segment) that end on a byte boundary
+      seam_prev_ff   chunks (but the last) whose last whole byte is 0xFF
+      group_edge_ff  0xFF bytes at index 63 mod 64 among one chunk's whole bytes
+      max_block_bits, max_chunk_bits (the carried bits and the pad included), chunks (per segment), segments
+    and where things are in the file: seg_at (the first byte of each segment, then the file's length; segment s's
+    marker is the two bytes before seg_at[s + 1]), stuffed_at (the stuffed zeros), seam_at (the bytes that hold bits of
+    two chunks), seam_prev_at (the stuffed zeros of seam_prev_ff), group_edge_at (the 0xFF bytes of group_edge_ff)."""
     rgb = np.asarray(rgb)
     H, W = rgb.shape[:2]
     coef = coefficients(rgb, quality)
@@ -175,8 +220,11 @@ def encode(rgb, quality, stats=None) -> bytes:
     dc = [huffman_codes(*dht[0x00]), huffman_codes(*dht[0x01])]
     ac = [huffman_codes(*dht[0x10]), huffman_codes(*dht[0x11])]
     st = stats if stats is not None else {}
-    for k in ("zrl", "no_eob", "neg_dc", "neg_ac", "stuffed", "stuffed_pad"):
+    for k in ("zrl", "no_eob", "neg_dc", "neg_ac", "stuffed", "stuffed_pad", "seam_ff", "seam_aligned", "seam_prev_ff",
+              "group_edge_ff", "max_block_bits", "max_chunk_bits", "chunks"):
         st.setdefault(k, 0)
+    for k in ("seg_at", "stuffed_at", "seam_at", "seam_prev_at", "group_edge_at"):
+        st.setdefault(k, [])
     st["max_dc_size"] = st.get("max_dc_size", 0)
     st["max_ac_size"] = st.get("max_ac_size", 0)
     st["segments"], st["segment_blocks"] = nby, 3 * nbx
@@ -184,6 +232,8 @@ def encode(rgb, quality, stats=None) -> bytes:
     for ty in range(nby):
         acc, nbits = 0, 0
         pred = [0, 0, 0]
+        ends = []
+        st["seg_at"].append(len(out))
         for tx in range(nbx):
             for c in range(3):
                 t = 1 if c else 0
@@ -214,13 +264,16 @@ def encode(rgb, quality, stats=None) -> bytes:
                     acc, nbits = (acc << n) | code, nbits + n
                 else:
                     st["no_eob"] += 1
+                ends.append(nbits)
         pad = -nbits % 8
         acc, nbits = (acc << pad) | ((1 << pad) - 1), nbits + pad
         data = acc.to_bytes(nbits // 8, "big")
         st["stuffed"] += data.count(b"\xff")
         st["stuffed_pad"] += bool(pad) and data[-1] == 0xFF
+        _chunk_stats(st, data, ends, len(out), chunk_blocks)
         out += data.replace(b"\xff", b"\xff\x00")
         out += b"\xff" + bytes([0xD9 if ty == nby - 1 else 0xD0 + ty % 8])
+    st["seg_at"].append(len(out))
     return bytes(out)
 
 
@@ -298,8 +351,46 @@ def search_pad_stuff_seed(limit=200):
     return None
 
 
+def saturated(H, W, seed=0):
+    """Noise whose every channel is 0 or 255: the most pixel energy there is, hence the longest codes."""
+    return (np.random.default_rng(seed).integers(0, 2, (H, W, 3), dtype=np.uint8) * 255).astype(np.uint8)
+
+
+SEEDED = dict(noise=noise, saturated=saturated)
+
+
+def search_seam_seed(event, size, quality, limit, first=0):
+    """The first seed in [first, limit) whose noise of `size` at `quality` shows `event` (one of the chunk counters of
+    encode's stats) at least once, or None: how the SEAM_*_CASEs below were found."""
+    for seed in range(first, limit):
+        st = {}
+        encode(noise(size[0], size[1], seed), quality, st)
+        if st[event]:
+            return seed
+    return None
+
+
+# ---- the wide cases: what the wave-level bookkeeping of the device's packing can get wrong ---------------------------
+# More than 64 segments (the layout scans them 64 at a time and carries the sum): 520 x 8 is one more than a round;
+# 1025 x 1 three rounds with padding below and to the right; 513 x 17 65 segments of 9 blocks, padded both ways.
+TALL_CASES = (("noise", (520, 8), 90, 0), ("noise", (520, 8), 100, 0), ("noise", (1025, 1), 90, 0),
+              ("noise", (513, 17), 90, 0))
+# 387 blocks: seven chunks, bits carried six times; 24 rows: three such segments in one frame.
+MANY_CHUNK_CASES = (("noise", (8, 1032), 100, 0), ("rendered_like", (8, 1032), 90, 0),
+                    ("noise", (24, 1032), 100, 0), ("rendered_like", (24, 1032), 90, 0))
+# Found by search_seam_seed(event, (8, 344), 100, 2000), the first seed each; the count is the event's in that case.
+SEAM_FF_CASE = ("noise", (8, 344), 100, 4)        # seam_ff 1: the byte that chunk 1's bits complete is 0xFF
+SEAM_ALIGNED_CASE = ("noise", (8, 344), 100, 3)   # seam_aligned 1: a chunk ends on a byte boundary, nothing is carried
+# seam_prev_ff 1 (and seam_aligned 2): a chunk whose last whole byte is 0xFF.  Quality 100 has none: seeds 0..1999 of
+# 8 x 344 and of 80 x 176 (24,000 seams) show no such chunk.  search_seam_seed("seam_prev_ff", (80, 176), 98, 600).
+SEAM_PREV_FF_CASE = ("noise", (80, 176), 98, 9)
+# Every channel 0 or 255. Reaches max_block_bits 881 and max_chunk_bits 51,218 at 8 x 176, 900 and 51,383 at 8 x 344
+# (the buffer is sized for 1660 and 106,240; the fullest chunk of the cases before these held 44,897 bits).
+DENSE_CASES = (("saturated", (8, 176), 100, 0), ("saturated", (8, 344), 100, 0))
+
+
 @functools.lru_cache(maxsize=None)
-def case_list():
+def base_case_list():
     """((content, (H, W), quality, seed), ...): every size with noise at 90 and the gradient at 50; every content at
     every quality at 30 x 44; the extremes (quality 100 noise: every coefficient is there, so no EOB, long segments and
     0xFF bytes; the checkerboard of blocks: DC differences of size 11; the sign pattern: AC values of size 10) on the
@@ -318,6 +409,13 @@ def case_list():
     return tuple(dict.fromkeys(cases))
 
 
+@functools.lru_cache(maxsize=None)
+def case_list():
+    """base_case_list(), then the wide cases: tall frames, many chunks, the seam events, the dense chunks."""
+    wide = TALL_CASES + MANY_CHUNK_CASES + (SEAM_FF_CASE, SEAM_ALIGNED_CASE, SEAM_PREV_FF_CASE) + DENSE_CASES
+    return tuple(dict.fromkeys(base_case_list() + wide))
+
+
 def case_id(case):
     content, (H, W), quality, seed = case
     return f"{content}-{H}x{W}-q{quality}" + (f"-s{seed}" if seed else "")
@@ -325,7 +423,7 @@ def case_id(case):
 
 def case_image(case):
     content, (H, W), quality, seed = case
-    img = noise(H, W, seed) if content == "noise" else CONTENTS[content](H, W)
+    img = SEEDED[content](H, W, seed) if content in SEEDED else CONTENTS[content](H, W)
     img.setflags(write=False)
     return img
 
