@@ -96,7 +96,11 @@ def main() -> None:
     ap.add_argument("--train-sac", type=int, default=0, metavar="ROUNDS",
                     help="train a policy with offpolicy.SAC for that many rounds (16 control steps and 4 gradient steps "
                          "each) instead; prints the same lines and the F1 of the trained policy at the end")
-    ap.add_argument("--time-limit", type=float, default=None, help="--train-ppo, --train-sac: stop after that many seconds")
+    ap.add_argument("--train-droq", type=int, default=0, metavar="ROUNDS",
+                    help="train a policy with droq.DroQ for that many rounds (16 control steps and one actor step of 20 "
+                         "critic steps each) instead; prints the same lines and the F1 of the trained policy at the end")
+    ap.add_argument("--time-limit", type=float, default=None,
+                    help="--train-ppo, --train-sac, --train-droq: stop after that many seconds")
     args = ap.parse_args()
     if args.video and not args.record:
         ap.error("--video needs --record")
@@ -112,8 +116,16 @@ def main() -> None:
             warnings.simplefilter("ignore")
             return _load(args, n_envs)
 
-    if args.train_ppo > 0 and args.train_sac > 0:
-        ap.error("--train-ppo and --train-sac are two learners: choose one")
+    if (args.train_ppo > 0) + (args.train_sac > 0) + (args.train_droq > 0) > 1:
+        ap.error("--train-ppo, --train-sac and --train-droq are three learners: choose one")
+    if args.train_droq > 0:
+        if (args.fingertip_pianist or args.plan or args.action_sequence or args.pixels or args.hear or args.record
+                or args.canonicalize):
+            ap.error("--train-droq trains on the plain environment: it goes with the task flags only")
+        from robopianist_amd import droq
+        droq.train_and_evaluate(load(args.n_envs), args.train_droq, time_limit=args.time_limit, seed=args.seed,
+                                batch_size=min(4096, 16 * args.n_envs))
+        return
     if args.train_sac > 0:
         if (args.fingertip_pianist or args.plan or args.action_sequence or args.pixels or args.hear or args.record
                 or args.canonicalize):

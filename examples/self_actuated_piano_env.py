@@ -28,12 +28,16 @@ def main() -> None:
     ap.add_argument("--train-sac", type=int, default=0, metavar="ROUNDS",
                     help="train a policy with offpolicy.SAC for that many rounds (16 control steps and 4 gradient steps "
                          "each) instead; prints the same lines and the F1 of the trained policy at the end")
-    ap.add_argument("--time-limit", type=float, default=None, help="--train-ppo, --train-sac: stop after that many seconds")
+    ap.add_argument("--train-droq", type=int, default=0, metavar="ROUNDS",
+                    help="train a policy with droq.DroQ for that many rounds (16 control steps and one actor step of 20 "
+                         "critic steps each) instead; prints the same lines and the F1 of the trained policy at the end")
+    ap.add_argument("--time-limit", type=float, default=None,
+                    help="--train-ppo, --train-sac, --train-droq: stop after that many seconds")
     args = ap.parse_args()
-    if args.train_ppo > 0 and args.train_sac > 0:
-        ap.error("--train-ppo and --train-sac are two learners: choose one")
-    if args.train_ppo > 0 or args.train_sac > 0:
-        from robopianist_amd import learning, offpolicy
+    if (args.train_ppo > 0) + (args.train_sac > 0) + (args.train_droq > 0) > 1:
+        ap.error("--train-ppo, --train-sac and --train-droq are three learners: choose one")
+    if args.train_ppo > 0 or args.train_sac > 0 or args.train_droq > 0:
+        from robopianist_amd import droq, learning, offpolicy
         with warnings.catch_warnings():
             warnings.simplefilter("ignore")
             task = SelfActuatedPiano(midi=music.load(args.midi), n_steps_lookahead=1,
@@ -42,6 +46,9 @@ def main() -> None:
         if args.train_sac > 0:
             offpolicy.train_and_evaluate(env, args.train_sac, time_limit=args.time_limit,
                                          batch_size=min(4096, 16 * args.n_envs))
+        elif args.train_droq > 0:
+            droq.train_and_evaluate(env, args.train_droq, time_limit=args.time_limit,
+                                    batch_size=min(4096, 16 * args.n_envs))
         else:
             learning.train_and_evaluate(env, args.train_ppo, time_limit=args.time_limit)
         return

@@ -1,0 +1,276 @@
+"""ctypes binding of the DroQ target kernel's C ABI (include/learn/rp_droq.h, librp_droq.so) and `DroQ`, dropout
+Q-functions (Hiroe et al. 2022) on top of `offpolicy.SAC`: the replay ring, the sampler and the policy are SAC's,
+unchanged; the critics are Linear -> Dropout -> LayerNorm -> ReLU twice and `utd` critic steps are taken per actor step.
+
+The entry point is a module function taking raw device addresses (`target`); it enqueues one kernel on the caller's HIP
+stream and reads nothing back.  An actor step draws its utd x B rows with one `rp_sac_sample` launch and acts on all
+their next observations with one `rp_sac_act` launch; every critic step is one `rp_droq_target` launch on its B rows
+plus plain torch (the loss, autograd with torch's own dropout, Adam, the Polyak step).  Like the engine, the library has
+no CPU fallback: a missing library is an error.
+"""
+
+from __future__ import annotations
+
+import ctypes
+import os
+
+from robopianist_amd import _abi, offpolicy
+from robopianist_amd.learning import LearnError, Mlp, _train_and_evaluate
+from robopianist_amd.offpolicy import SAC, _masked_mean, actor_loss, alpha_loss, critic_loss, squashed_gaussian
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+LIB_PATH = os.environ.get("RP_DROQ_LIB") or os.path.join(_HERE, "csrc", "librp_droq.so")
+
+EXPORTED_SYMBOLS = ("rp_droq_target", "rp_droq_dim", "rp_droq_last_error")
+
+MAX_CRITICS = offpolicy.MAX_CRITICS
+COUNTER = 32   # the last Philox counter word of critic i, layer L is COUNTER + 2 i + L
+
+_lib = None
+
+_p, _i, _u32, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_float
+
+
+class Critic(ctypes.Structure):
+    """rp_droq_critic."""
+    _fields_ = [("net", Mlp), ("g1", _p), ("be1", _p), ("g2", _p), ("be2", _p)]
+
+
+class TargetArgs(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_size_t), ("next_obs", _p), ("action", _p), ("logp", _p), ("reward", _p),
+                ("discount", _p), ("mean", _p), ("inv_std", _p), ("obs_clip", _f), ("gamma", _f), ("log_alpha", _p),
+                ("critics", ctypes.POINTER(Critic)), ("n_critics", _i), ("y", _p), ("q_min", _p), ("q", _p),
+                ("drop_threshold", _u32), ("keep_scale", _f), ("ln_eps", _f), ("seed_lo", _u32), ("seed_hi", _u32),
+                ("round", _u32), ("D", _i), ("H1", _i), ("H2", _i), ("A", _i), ("B", _i), ("row_first", _i),
+                ("row_count", _i), ("hip_stream", _p)]
+
+
+_ARGS = {"target": TargetArgs}
+
+
+def load_library(path: str = LIB_PATH):
+    """Loads librp_droq.so; raises LearnError if it has not been built."""
+    global _lib
+    if _lib is None:
+        _lib = declare(_abi.open_library(path, "DroQ target", LearnError))
+    return _lib
+
+
+_entries = _abi.EntryTable("rp_droq_", _ARGS, LearnError, load_library)
+make_args, call_raw, last_error, dim, _call = (_entries.make_args, _entries.call_raw, _entries.last_error, _entries.dim,
+                                               _entries.call)
+
+
+def declare(L, prefix: str = "rp_droq_"):
+    """Declares the ABI's prototypes on a loaded library whose symbols start with `prefix`."""
+    return _entries.declare(L, prefix)
+
+
+def drop_threshold(p: float) -> int:
+    """The word below which a unit is dropped: a Philox word is below it with probability p (to 2^-32)."""
+    return min(int(p * 2 ** 32), 2 ** 32 - 1)
+
+
+def critic_entry(tensors):
+    """An rp_droq_critic from the ten tensors (w1, b1, w2, b2, w3, b3, g1, be1, g2, be2) of a critic."""
+    c = Critic()
+    for (name, _), t in zip(Mlp._fields_, tensors[:6]):
+        setattr(c.net, name, t.data_ptr())
+    c.g1, c.be1, c.g2, c.be2 = (t.data_ptr() for t in tensors[6:])
+    return c
+
+
+def critic_table(critics):
+    """A ctypes array of rp_droq_critic from a sequence of `Critic`."""
+    critics = list(critics)
+    if not 1 <= len(critics) <= MAX_CRITICS:
+        raise LearnError(f"the target takes 1 .. {MAX_CRITICS} critics per launch, got {len(critics)}")
+    tab = (Critic * len(critics))()
+    for i, c in enumerate(critics):
+        tab[i] = c
+    return tab
+
+
+def target(next_obs, action, logp, reward, discount, mean, inv_std, obs_clip, gamma, log_alpha, critics, y, D, H1, H2, A,
+           B, q_min=None, q=None, threshold=0, keep_scale=1.0, ln_eps=1e-5, seed=0, round_=0, row_first=0,
+           row_count=None, hip_stream=None):
+    """`critics`: a sequence of `Critic` (the target networks).  `threshold`: `drop_threshold(p)`."""
+    tab = critic_table(critics)
+    _call("target", next_obs=next_obs, action=action, logp=logp, reward=reward, discount=discount, mean=mean,
+          inv_std=inv_std, obs_clip=float(obs_clip), gamma=float(gamma), log_alpha=log_alpha, critics=tab,
+          n_critics=len(tab), y=y, q_min=q_min, q=q, drop_threshold=int(threshold), keep_scale=float(keep_scale),
+          ln_eps=float(ln_eps), D=D, H1=H1, H2=H2, A=A, B=B, row_first=row_first,
+          row_count=B - row_first if row_count is None else row_count, hip_stream=hip_stream,
+          **_abi.seed_args(seed, round_))
+
+
+class DroQ(SAC):
+    """DroQ (Hiroe et al. 2022): `SAC` whose critics are Linear -> Dropout(`dropout`) -> LayerNorm -> ReLU twice, with
+    `utd` critic steps (the update-to-data ratio) per actor step.  The actor stays SAC's tanh network.
+
+    `update(g)` takes g actor steps.  Each draws utd x `batch_size` rows in one sampler launch and acts on all their
+    next observations in one launch (the actor does not change in between); critic step u then computes its TD target
+    on the rows [u B, (u + 1) B) with `rp_droq_target`, whose dropout masks come from the learner's (seed, round), and
+    takes its Adam and Polyak steps in torch.  The actor and the temperature step on the last range."""
+
+    def __init__(self, env, *sac_args, dropout: float = 0.01, utd: int = 20, ln_eps: float = 1e-5, **sac_kwargs):
+        self.dropout, self.utd, self.ln_eps = float(dropout), int(utd), float(ln_eps)
+        if not 0.0 <= self.dropout < 1.0:
+            raise ValueError(f"dropout must lie in [0, 1), got {dropout}")
+        if self.utd < 1:
+            raise ValueError(f"utd must be >= 1, got {utd}")
+        if not self.ln_eps > 0.0:
+            raise ValueError(f"ln_eps must be > 0, got {ln_eps}")
+        self._threshold = drop_threshold(self.dropout)
+        self._keep_scale = 1.0 / (1.0 - self.dropout)
+        super().__init__(env, *sac_args, **sac_kwargs)
+        # the minibatch: utd ranges of B rows, drawn and acted on at once
+        n, D, A, z = self.utd * self.B, self.D, self.A, self._zeros
+        self._u_obs, self._u_next, self._u_action = z(n, D), z(n, D), z(n, A)
+        self._u_reward, self._u_discount, self._u_mask = z(n), z(n), z(n)
+        self._u_next_action, self._u_next_logp, self._u_y = z(n, A), z(n), z(n)
+        self._set_range(self.utd - 1)
+
+    def _net(self, n_in, n_out):
+        """SAC's constructor draws the actor (n_out = 2 A) and then the critics (n_out = 1) through here."""
+        from torch import nn
+        if n_out != 1:
+            return super()._net(n_in, n_out)
+        p, eps = self.dropout, self.ln_eps
+        return nn.Sequential(nn.Linear(n_in, self.H1), nn.Dropout(p), nn.LayerNorm(self.H1, eps), nn.ReLU(),
+                             nn.Linear(self.H1, self.H2), nn.Dropout(p), nn.LayerNorm(self.H2, eps), nn.ReLU(),
+                             nn.Linear(self.H2, 1))
+
+    def _critic_table(self, net):
+        """`net` as rp_droq_critic: the addresses of the parameters as they are now."""
+        import torch
+        tensors = [t for i in (0, 4, 8) for t in (net[i].weight, net[i].bias)]
+        tensors += [t for i in (2, 6) for t in (net[i].weight, net[i].bias)]
+        for t in tensors:
+            if not t.is_contiguous() or t.dtype != torch.float32:
+                raise LearnError(f"{self._reads} contiguous float32 parameters")
+        return critic_entry(tensors)
+
+    # -- the minibatch ---------------------------------------------------------------------------------------------------
+    def _set_range(self, u):
+        """The minibatch views (`_b_*`, what `minibatch()` and `gradient_step()` read) on range u."""
+        r = slice(u * self.B, (u + 1) * self.B)
+        self._b_obs, self._b_next, self._b_action = self._u_obs[r], self._u_next[r], self._u_action[r]
+        self._b_reward, self._b_discount, self._b_mask = self._u_reward[r], self._u_discount[r], self._u_mask[r]
+        self._b_next_action, self._b_next_logp, self._b_y = self._u_next_action[r], self._u_next_logp[r], self._u_y[r]
+
+    def draw_and_act(self):
+        """The two launches of an actor step that cover all utd ranges: the utd x B rows of the minibatch, and the
+        policy at their next observations."""
+        import torch
+        n = self.utd * self.B
+        with torch.cuda.device(self._dev):
+            st = self._stream()
+            offpolicy.sample(self._obs.data_ptr(), self._action.data_ptr(), self._reward.data_ptr(),
+                             self._discount.data_ptr(), self._step_type.data_ptr(), self._u_obs.data_ptr(),
+                             self._u_next.data_ptr(), self._u_action.data_ptr(), self._u_reward.data_ptr(),
+                             self._u_discount.data_ptr(), self._u_mask.data_ptr(), self.n_written, self.C, self.E, self.D,
+                             self.A, n, seed=self.seed, round_=self._round, hip_stream=st)
+            self._act(self._u_next, n, st, action=self._u_next_action.data_ptr(), logp=self._u_next_logp.data_ptr())
+
+    def target_range(self, u):
+        """The TD target of range u from the target critics as they are now (one launch); returns `minibatch()` on it."""
+        import torch
+        with torch.cuda.device(self._dev):
+            target(self._u_next.data_ptr(), self._u_next_action.data_ptr(), self._u_next_logp.data_ptr(),
+                   self._u_reward.data_ptr(), self._u_discount.data_ptr(), self._mean_f32.data_ptr(),
+                   self._inv_std_f32.data_ptr(), self.obs_clip, self.gamma, self.log_alpha.data_ptr(),
+                   [self._critic_table(t) for t in self.targets], self._u_y.data_ptr(), self.D, self.H1, self.H2, self.A,
+                   self.utd * self.B, threshold=self._threshold, keep_scale=self._keep_scale, ln_eps=self.ln_eps,
+                   seed=self.seed, round_=self._round, row_first=u * self.B, row_count=self.B, hip_stream=self._stream())
+        self._set_range(u)
+        return self.minibatch()
+
+    def sample_and_target(self):
+        """SAC's meaning at utd == 1: the minibatch, the policy at its next observations, the TD target."""
+        if self.utd != 1:
+            raise LearnError("sample_and_target() is one gradient step's launches: with utd > 1 use update()")
+        self.draw_and_act()
+        batch = self.target_range(0)
+        self._round += 1
+        return batch
+
+    # -- the gradient steps ----------------------------------------------------------------------------------------------
+    def critic_step(self, batch):
+        """The critics' Adam step on `batch` (torch's own dropout: the modules are in train() mode) and the targets'
+        Polyak step over all parameters, LayerNorm's included.  Returns the loss (a tensor)."""
+        import torch
+        xa = torch.cat([self.normalize(batch["obs"]), batch["action"]], dim=1)
+        lc = critic_loss([c(xa).squeeze(-1) for c in self.critics], batch["y"], batch["mask"])
+        self.critic_optimizer.zero_grad(set_to_none=True)
+        lc.backward()
+        self.critic_optimizer.step()
+        with torch.no_grad():
+            torch._foreach_lerp_([p for t in self.targets for p in t.parameters()],
+                                 [p for c in self.critics for p in c.parameters()], self.tau)
+        return lc.detach()
+
+    def actor_step(self, batch):
+        """The actor's and the temperature's Adam steps on `batch`; the critics stay in train() mode, as in the paper."""
+        import torch
+        mask = batch["mask"]
+        xn = self.normalize(batch["obs"])
+        eps = torch.randn(xn.shape[0], self.A, generator=self._gen, device=xn.device)
+        a_new, logp_new, _ = squashed_gaussian(self.actor(xn), eps, self.log_std_bounds)
+        xa_new = torch.cat([xn, a_new], dim=1)
+        q_new = torch.stack([c(xa_new).squeeze(-1) for c in self.critics]).min(0).values
+        la = actor_loss(self.log_alpha, logp_new, q_new, mask)
+        self.actor_optimizer.zero_grad(set_to_none=True)
+        la.backward()   # (the critics' gradients of this pass are dropped by their next zero_grad)
+        self.actor_optimizer.step()
+        lt = alpha_loss(self.log_alpha, logp_new, self.target_entropy, mask)
+        self.alpha_optimizer.zero_grad(set_to_none=True)
+        lt.backward()
+        self.alpha_optimizer.step()
+        return {"actor_loss": la.detach(), "alpha_loss": lt.detach(), "alpha": self.log_alpha.detach().exp()[0],
+                "entropy": -_masked_mean(logp_new.detach(), mask), "masked": 1.0 - mask.mean()}
+
+    def gradient_step(self, batch):
+        """One critic step (with its Polyak step) and one actor and temperature step on `batch`: SAC's meaning."""
+        lc = self.critic_step(batch)
+        return dict({"critic_loss": lc}, **self.actor_step(batch))
+
+    def update(self, g: int = 1):
+        """g actor steps of utd critic steps each; returns the statistics of the last one as floats."""
+        if self.n_written < 2:
+            raise LearnError("update() needs at least two TimeSteps in the ring: call collect() first")
+        stats = {}
+        for _ in range(int(g)):
+            self.draw_and_act()
+            for u in range(self.utd):
+                batch = self.target_range(u)
+                lc = self.critic_step(batch)
+            stats = dict({"critic_loss": lc}, **self.actor_step(batch))
+            self._round += 1
+        return {k: float(v) for k, v in stats.items()}
+
+    # -- checkpoint / resume -------------------------------------------------------------------------------------------
+    def state_dict(self, include_replay: bool = False):
+        """SAC's (Module.state_dict carries the LayerNorm parameters), plus "dropout", "utd" and "ln_eps"."""
+        sd = super().state_dict(include_replay)
+        sd["droq"] = {"dropout": self.dropout, "utd": self.utd, "ln_eps": self.ln_eps}
+        return sd
+
+    def load_state_dict(self, sd):
+        mine = {"dropout": self.dropout, "utd": self.utd, "ln_eps": self.ln_eps}
+        for k, v in mine.items():
+            if "droq" not in sd or sd["droq"].get(k) != v:
+                got = sd.get("droq", {}).get(k, "nothing")
+                raise ValueError(f"the checkpoint was written with {k} = {got}, this learner has {k} = {v}")
+        super().load_state_dict(sd)
+
+
+def train_and_evaluate(env, rounds: int, steps_per_round: int = 16, grad_steps: int = 1, time_limit: float = None,
+                       log=print, **droq_kwargs):
+    """What the examples' --train-droq does: `rounds` rounds of DroQ on `env` (a batched Environment), one line per
+    round with the mean return of the episodes that ended in it, then one deterministic episode of every env through a
+    MidiEvaluationWrapper.  Stops early after `time_limit` seconds.  Returns (droq, log of the rounds, metrics)."""
+    learner = DroQ(env, **droq_kwargs)
+    train_one = lambda cb: learner.train(1, steps_per_round, grad_steps, callback=cb)
+    rounds_log, metrics = _train_and_evaluate(learner, rounds, train_one, ("alpha", "alpha"), time_limit, log)
+    return learner, rounds_log, metrics
