@@ -785,7 +785,7 @@ struct Engine : EngineBase {
     const double floor_ = sizeof(T) == 4 ? 1e-6 : 0.0;   // (single precision cannot resolve a tighter portal distance)
     if (tol > 0) M.mpr_tol = (T)(tol > floor_ ? tol : floor_);
     if (poly_tol > 0) M.mpr_tol_poly = (T)(poly_tol > floor_ ? poly_tol : floor_);
-    else if (tol > 0) M.mpr_tol_poly = M.mpr_tol;
+    else M.mpr_tol_poly = M.mpr_tol;   // (<= 0: back to `tolerance`, whether this call changed it or not)
   }
   void tolerances(double tol, double ls_tol) override {
     if (tol > 0) M.tolerance = (T)tol;

@@ -297,7 +297,9 @@ class BatchedPhysics:
 
     def set_mpr_tolerance(self, tolerance=0.0, polytope_tolerance=0.0):
         """Stopping tolerance of the hull / cylinder narrow phase (default: MuJoCo's uniform 1e-6);
-        `polytope_tolerance` = box / hull pairs refine to that instead (include/rp_engine.h)."""
+        `polytope_tolerance` > 0 = box / hull pairs refine to that instead (include/rp_engine.h).  `tolerance` <= 0 leaves
+        the tolerance as it is; `polytope_tolerance` <= 0 sets the polytope tolerance back to the tolerance, so the call
+        without arguments undoes an earlier polytope tolerance and keeps the tolerance.  fp32 engines clamp both at 1e-6."""
         self._check(self._L.rp_set_mpr_tolerance(self._h, float(tolerance), float(polytope_tolerance)))
 
     def set_solver_tolerance(self, tolerance=0.0, ls_tolerance=0.0):

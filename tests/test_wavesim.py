@@ -50,15 +50,18 @@ def test_fused_substeps_on_the_wave_emulator_match_the_per_stage_schedule(wavesi
     assert float(m.group(1)) < 1e-9 and float(m.group(2)) < 1e-9, out.stdout
 
 
-def _run_parity_fn(lib, fn, *args, timeout=900):
-    """Runs one scenario function of tests/test_gpu_parity.py (engine vs oracle) against the emulator build."""
+def _run_parity_fn(lib, fn, *args, timeout=900, module="test_gpu_parity", scene=None):
+    """Runs one scenario function of a GPU test module (tests/test_gpu_parity.py unless `module` names another: engine vs
+    oracle) against the emulator build, on the capsule-fingertip scene or on build_scene(**scene)."""
     env = dict(os.environ, RP_ENGINE_LIB=lib, WAVESIM_SITE="0", RP_SKIP_SELF_CHECK="1")
     code = ("import sys, warnings; sys.path.insert(0, %r); sys.path.insert(0, %r)\n"
-            "import test_gpu_parity as t\nfrom robopianist_amd.model import scene\n"
+            "import %s as t\nfrom robopianist_amd.model import scene\n"
             "warnings.simplefilter('ignore')\n"
-            "si = scene.build_scene(gravity_compensation=True, primitive_fingertip_collisions=True)\n"
-            "print('RESULT', *t.%s(si, %s))\n") % (os.path.dirname(HERE), HERE, fn, ", ".join(repr(a) for a in args))
-    out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=timeout)
+            "si = scene.build_scene(gravity_compensation=True, **%r)\n"
+            "print('RESULT', *t.%s(si, %s))\n") % (os.path.dirname(HERE), HERE, module, scene or dict(primitive_fingertip_collisions=True),
+                                                   fn, ", ".join(repr(a) for a in args))
+    out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=timeout,
+                         cwd=os.path.dirname(HERE))
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
     return [float(x) for x in re.search(r"RESULT (.*)", out.stdout).group(1).split()]
 
@@ -77,6 +80,33 @@ def test_legacy_step_false_on_the_wave_emulator(wavesim_lib):
     state before the last integration (the GPU twin: test_legacy_step_false_publishes_the_outputs_of_mj_step)."""
     maxcon, checks = _run_parity_fn(wavesim_lib, "legacy_step_off", 70)
     assert checks == 350 and maxcon >= 2, (maxcon, checks)
+
+
+def test_solver_and_mpr_options_on_the_wave_emulator(wavesim_lib):
+    """rp_set_solver_limits / rp_set_solver_tolerance against the blob's opt_* values and rp_set_mpr_tolerance's reset and
+    fp32 clamp without a GPU: the scenario functions of tests/test_gpu_solver_options.py on shorter windows, one env (the
+    GPU twins: test_setter_equals_the_model_option_bit_for_bit, test_mpr_polytope_tolerance_is_reset_by_zero,
+    test_mpr_tolerances_clamp_at_1e_6_in_fp32)."""
+    def run(fn, *args, scene=None):
+        return _run_parity_fn(wavesim_lib, fn, *args, module="test_gpu_solver_options", scene=scene)
+    lo, n = 420, 24
+    # A: a Newton cap of 4 with line searches of 6 evaluations, and the loose tolerances, setter == model option
+    for kind, calls in (("limits", ((4, 6),)), ("tolerance", ((1e-3, 0.3),))):
+        mismatch, differs, bound, nonfinite, warn, owarn = run("setter_equals_model_option", 64, kind, calls, lo, n, 1)
+        assert warn == 0 and owarn == 0 and nonfinite == 0, (kind, warn, owarn, nonfinite)
+        assert mismatch == 0 and differs >= 1, (kind, mismatch, differs)
+        assert kind != "limits" or bound >= 10, bound
+    # C1, the reset row: (0, 0) undoes a polytope tolerance (hull fingertips)
+    loose, reset, warn, owarn = run("mpr_settings_compared", 64, ((), ((1e-6, 1e-3),), ((1e-6, 1e-3), (0, 0))), lo, n, 1,
+                                    scene=dict(primitive_fingertip_collisions=False))
+    assert warn == 0 and owarn == 0, (warn, owarn)
+    assert loose >= 1, loose
+    assert reset == 0, reset
+    # C2: the fp32 floor of both tolerances (cylinder knuckles, hull fingertips)
+    tight, back, loose, warn, owarn = run("mpr_settings_compared", 32, ((), ((1e-10, 1e-10),), ((1e-3, 1e-3), (1e-10, 1e-10)), ((1e-3, 1e-3),)),
+                                          lo, n, 1, scene=dict(primitive_fingertip_collisions=False, cylinder_colliders=True))
+    assert warn == 0 and owarn == 0, (warn, owarn)
+    assert tight == 0 and back == 0 and loose >= 1, (tight, back, loose)
 
 
 def test_split_position_stage_on_the_wave_emulator(wavesim_lib):
