@@ -232,7 +232,7 @@ int rp_solver_kernel_envs(rp_engine* e, double* avg_envs);
 /* 1 if the launches the last rp_solver_kernel_time call reported were fused-substeps launches, 0 if they were
  * per-stage solver launches (bench.py names the timed kernel from this, not from a heuristic). */
 int rp_solver_kernel_fused(rp_engine* e);
-/* Debug aid: per-phase shader-clock counters of env 0 (see rp_kernels.hpp PROF).
+/* Debug aid: per-phase shader-clock counters of env 0 (see rp_model.hpp PROF).
  * Reads and clears the counters (out may be NULL), then enables/disables them. */
 int rp_profile(rp_engine* e, long long* out, int n, int enable);
 const char* rp_last_error(void);

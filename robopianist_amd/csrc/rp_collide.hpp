@@ -1,10 +1,10 @@
 // rp_collide.hpp -- the POOLED narrow phase of the split position stage (round 5).
 //
-// The one-kernel position stage (rp_stage_body<T, 0>, PART 0) runs its narrow phase with one wave per env: the ~25
+// The one-kernel position stage (rp_position_body<T, 0>, PART 0) runs its narrow phase with one wave per env: the ~25
 // candidates an env has after the fp32 prefilters sit in ~25 lanes, and the wave walks EVERY routine a candidate of
 // its pass needs -- capsule-capsule, capsule-box, box-box, the portal refinement of the hull pairs -- one after the
 // other with ~10 of 64 lanes working (measured: a third of the stage's shader cycles).  Here the candidates of ALL envs
-// of a launch are pooled by pair type (rp_stage_body<T, 0, ..., PART 1> appends them to RpStage::tlist): a wave takes 64
+// of a launch are pooled by pair type (rp_position_body<T, 0, ..., PART 1> appends them to RpStage::tlist): a wave takes 64
 // candidates of ONE type, whatever envs they came from, and walks one routine with every lane busy.  Results go back
 // to the candidate's own records (RpStage::cres / cres_n), so where a candidate landed on the pooled list -- which
 // depends on the order in which the front part's waves arrive -- never shows in the output.

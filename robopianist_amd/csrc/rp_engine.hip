@@ -1,7 +1,8 @@
 // rp_engine.hip — host side of the C ABI declared in include/rp_engine.h.
 // Parses the model blob (robopianist_amd/model/compile.py:to_blob + engine
 // tables), uploads the fixed-topology tables, owns the env-major state arrays and
-// launches the stage kernels rp_stage_kernel<T, MODE> (rp_kernels.hpp) on the engine's HIP stream.
+// launches the stage kernels (rp_kernels.hpp; their bodies: rp_position_body there, rp_lean_solver_body in rp_solver2.hpp,
+// rp_full_solver_body in rp_solver_full.hpp) on the engine's HIP stream.
 #include "rp_kernels.hpp"
 #include "rp_schedule.hpp"
 
@@ -58,7 +59,7 @@ __global__ __launch_bounds__(512) void rp_order_kernel(int* order_all, const int
   // are independent); the counter is cleared by that stage's last workgroup
   if (heavy_list) {
     for (int e = x + RP_ORDER_CLASSES * (int)threadIdx.x; e < n; e += RP_ORDER_CLASSES * blockDim.x) {
-      const bool on = hdr[(base + e) * 8 + 6] != 1 && !(active && active[base + e] == 0);
+      const bool on = hdr[(base + e) * rpk::HDR_N + rpk::HDR_CLASS] != 1 && !(active && active[base + e] == 0);
       if (on) heavy_list[base + atomicAdd(heavy_cnt, 1)] = base + e;
       if (listed) listed[base + e] = on ? 1 : 0;   // (the snapshot the split position launches test: RpState::listed)
     }
@@ -70,8 +71,8 @@ __global__ __launch_bounds__(512) void rp_order_kernel(int* order_all, const int
   __syncthreads();
   auto key_of = [&](int e) -> int {
     if (active && active[e] == 0) return 0;
-    const int nc = hdr[e * 8], nk = hdr[e * 8 + 1];
-    const int nd = __popc((unsigned)hdr[e * 8 + 2]) + __popc((unsigned)hdr[e * 8 + 3]);
+    const int nc = hdr[e * rpk::HDR_N + rpk::HDR_NCON], nk = hdr[e * rpk::HDR_N + rpk::HDR_NKT];
+    const int nd = __popc((unsigned)hdr[e * rpk::HDR_N + rpk::HDR_DIRTY_LO]) + __popc((unsigned)hdr[e * rpk::HDR_N + rpk::HDR_DIRTY_HI]);
     if (nc < 0 || nk < 0) return 1;   // (hand-over not written yet)
     // k cycles / 4, five Newton iterations
     const int k = 1 + (26 + 5 * (30 + nd + (nd >> 2) + nd * nd / 200 + 2 * nk) + 3 * nc) / 4;
@@ -593,10 +594,10 @@ struct Engine : EngineBase {
     rm_rows = RPK_NLX(md()); rm_cols = md() + 1;
     B.lanef = dalloc<T>(E * RPK_NLF * 64);
     B.lanei = dalloc<int>(E * RPK_NLI * 64);
-    B.hdr = dalloc<int>(E * 8);
+    B.hdr = dalloc<int>(E * rpk::HDR_N);
     B.entJ = dalloc<T>(E * RpCaps<T>::NE * 3);
     B.entM = dalloc<int>(E * RpCaps<T>::NE * 2);
-    B.slots = dalloc<int>(E * 64);
+    B.slots = dalloc<int>(E * rpk::SLOT_N);
     B.keyslot = dalloc<int>(E * (RPK_NKEYS / 4));
     B.covf = dalloc<T>(E * (RPK_NC - RPK_NCL) * 12);
     B.covi = dalloc<int>(E * (RPK_NC - RPK_NCL) * 4);
@@ -605,10 +606,10 @@ struct Engine : EngineBase {
     hipMemset(B.RM, 0xFF, sizeof(T) * E * RPK_NLX(md()) * (md() + 1));
     hipMemset(B.lanef, 0xFF, sizeof(T) * E * RPK_NLF * 64);
     hipMemset(B.lanei, 0xFF, sizeof(int) * E * RPK_NLI * 64);
-    hipMemset(B.hdr, 0xFF, sizeof(int) * E * 8);
+    hipMemset(B.hdr, 0xFF, sizeof(int) * E * rpk::HDR_N);
     hipMemset(B.entJ, 0xFF, sizeof(T) * E * RpCaps<T>::NE * 3);
     hipMemset(B.entM, 0xFF, sizeof(int) * E * RpCaps<T>::NE * 2);
-    hipMemset(B.slots, 0xFF, sizeof(int) * E * 64);
+    hipMemset(B.slots, 0xFF, sizeof(int) * E * rpk::SLOT_N);
     hipMemset(B.keyslot, 0xFF, sizeof(int) * E * (RPK_NKEYS / 4));
     S.key_trace = nullptr;
     S.prof = nullptr;
@@ -862,7 +863,7 @@ struct Engine : EngineBase {
       case RP_TREE_OFFSET: *p = S.tree_offset; *bytes = sizeof(T) * E * ntree * 3; *writable = true; return true;
       case RP_ENV_COST: *p = S.cost_sol; *bytes = sizeof(int) * E; return true;
       case RP_DEBUG_MASS_ROWS: *p = B.RM; *bytes = sizeof(T) * E * RPK_NLX(md()) * (md() + 1); return true;
-      case RP_DEBUG_HANDOVER_HDR: *p = B.hdr; *bytes = sizeof(int) * E * 8; return true;
+      case RP_DEBUG_HANDOVER_HDR: *p = B.hdr; *bytes = sizeof(int) * E * rpk::HDR_N; return true;
       case RP_SENSOR_TORQUE: if (!d_sens_torque) return false; *p = d_sens_torque; *bytes = sizeof(T) * E * nv; return true;
       case RP_SENSOR_TOUCH: if (!d_sens_touch) return false; *p = d_sens_touch; *bytes = sizeof(T) * E * nsite; return true;
     }

@@ -1,6 +1,6 @@
-// rp_kernels.hpp — the two stage kernels of the batched step (position/velocity stage and
-// constraint-solver stage), their LDS layouts, and the reset kernel.  Lane roles, tables and
-// hand-over buffers: rp_model.hpp.
+// rp_kernels.hpp — the position / velocity stage of the batched step (and the sensor stage built on it), its LDS
+// layouts, the __global__ kernels of every stage, and the reset kernel.  Lane roles, tables and hand-over buffers:
+// rp_model.hpp; the solver stages: rp_solver2.hpp (lean), rp_solver_full.hpp (full capacity).
 #pragma once
 #include <type_traits>
 #include "rp_model.hpp"
@@ -9,10 +9,8 @@
 #include "rp_collide.hpp"
 #include "rp_dense.hpp"
 #include "rp_solver2.hpp"
+#include "rp_solver_full.hpp"
 
-#ifdef RPK_NO_BOXBOX   // perf experiment: what the box-box routine costs the position kernel
-#define RPK_BOXBOX(...) 0
-#else
 // (the box-box routine is a real call: its arguments and result live in memory, so they are copies --
 // the capsule paths' own arrays stay in registers)
 // (up to eight points: the first three go on in registers like every other pair's, points four to eight stay in
@@ -24,28 +22,8 @@
     const int n_ = box_box(o_, bx_, a_, a_ + 3, a_ + 12, b_, b_ + 3, b_ + 12);                  \
     (rc_)[0] = o_[0]; (rc_)[1] = o_[1]; (rc_)[2] = o_[2];                                       \
     return n_; }()
-#endif
 namespace rpk {
-// ----------------------------------------------------------------- shared memory
-// LDS budget drives occupancy (fp64: 40.5 KB -> 4 workgroups per CU).  Scratch of the
-// position/velocity stage and scratch of the solver are never live together, so they
-// share storage; only what crosses from one stage into the other is persistent.
-template <typename T>
-struct SmemShared {  // used by both stages
-  union {
-    T vec[2][RPK_WAVE];
-    short work[RPK_WORK][2];  // position stage, collision only: candidate pairs
-  };
-  unsigned long long slotmask[16];
-  short slotkey[16];
-  short slotlink[16];
-  signed char keyslot[RPK_NKEYS];
-  unsigned prof[RPK_NPROF_STAGE];   // per-launch phase cycle counts of env 0 (debug aid)
-#ifdef RPK_OCC_TEST  // occupancy experiment: pad the LDS footprint to force one workgroup per SIMD
-  char occ_pad[RPK_OCC_TEST];
-#endif
-};
-template <typename T, int MODE, int MD = RPK_MAXD> struct Smem;
+// ----------------------------------------------------------------- shared memory (SmemShared: rp_model.hpp)
 // ---- position / velocity stage (mj_step1)
 template <typename T, int MD>
 struct Smem<T, 0, MD> : SmemShared<T> {
@@ -116,26 +94,6 @@ struct Smem<T, 2, MD> : Smem<T, 0, MD> {
   T fext[RPK_NLX(MD)][6];   // contact forces on each link: spatial force about the tree reference point
   T touch[RPK_WAVE];   // touch sensor sums per engine site
 };
-// ---- acceleration stage (mj_step2: constraint solver + Euler)
-template <typename T, int MD>
-struct Smem<T, 1, MD> : SmemShared<T> {
-  T R[RPK_WAVE][MD + 1];  // tree factor rows (L), incl. key-leaf rows
-  T Dg[RPK_WAVE];               // tree factor diagonal
-  T xs[RPK_WAVE];               // solve staging
-  T H[(RpCaps<T>::HMAX + 1) * (RpCaps<T>::HMAX + 2) / 2];  // dense block of the cross-coupled rows + rhs row
-  T RM[RPK_NLX(MD)][MD + 1];   // mass-matrix rows: RM[i][e] = M[i][anc_e(i)]
-  T keyvec[2][RPK_NKEYS];
-  T entJ[RpCaps<T>::NE][3];            // contact Jacobian entries (see RpStage)
-  int entM[RpCaps<T>::NE][2];
-  T cC[RpCaps<T>::NC][6];       // per-contact 3x3 weight of the current Newton iteration
-  T cv[RpCaps<T>::NC][3];       // per-contact 3-vector staging (J x, or the contact force)
-  T jt[RPK_WAVE];               // J^T f staging, one value per solver row
-  T actf[RPK_WAVE];
-};
-
-// rows owned by one lane: friction-loss row of its hand dof, one limit row per dof
-// slot (hand, key, key+64), four pyramidal rows of its contact.
-template <typename T> struct Rows { T fr, lim[3], con[4]; };
 }  // namespace rpk
 
 // physics.reset() for the envs selected by a device-side mask (null = all).
@@ -160,25 +118,20 @@ __global__ void rp_reset_kernel(RpState<T> S, const T* qpos0, const unsigned cha
 }
 
 // ============================================================================
-// The stage kernels.  MODE 0: position/velocity stage (mj_step1: kinematics, CRB, collision,
-// constraint rows; also physics.forward()).  MODE 1: acceleration stage (mj_step2: Newton
-// solver + Euler).  FIXED_TL > 0 specialises the solver for trunks of exactly that many links.
+// The position / velocity stage (mj_step1: kinematics, CRB, collision, constraint rows; also physics.forward()):
+// MODE 0, and the sensor stage, MODE 2: the same plus the acceleration-stage sensors.  The solver stages (mj_step2)
+// are rp_lean_solver_body (rp_solver2.hpp) and rp_full_solver_body (rp_solver_full.hpp).
 // The host launches  pos, then n_substeps x (sol, pos);  RpStage carries the hand-over.
 // ============================================================================
-#ifndef RPK_SOL64_WAVES
-#define RPK_SOL64_WAVES 1
-#endif
 // PART (MODE 0 only): 0 = the whole position / velocity stage; 1 = its front part (kinematics, CRB, broad phase, fp32
 // prefilters: leaves link / geom frames and the candidate list, RpStage::frames .. tlist); 2 = its back part (collects the
 // pooled narrow phase's results in the whole stage's emission order, then constraint rows, Jacobians, velocity stage).
-template <typename T, int MODE, int FIXED_TL = 0, int MD = RPK_MAXD, int MESH = 0, bool EXT = false, int PART = 0>
-__device__ __forceinline__ void rp_stage_body(const RpModel<T>& M, const RpState<T>& S, const RpStage<T>& B, const int substep,
-                                              const int nsub, const int env, void* ext, const int lane) {
+template <typename T, int MODE, int MD = RPK_MAXD, int MESH = 0, bool EXT = false, int PART = 0>
+__device__ __forceinline__ void rp_position_body(const RpModel<T>& M, const RpState<T>& S, const RpStage<T>& B, const int substep,
+                                                 const int nsub, const int env, void* ext, const int lane) {
+  static_assert(MODE == 0 || MODE == 2, "position / velocity stage (0) or sensor stage (2)");
   using namespace rpk;
   using N = Num<T>;
-  if constexpr (MODE == 1) {
-    if (S.lean && B.hdr[env * 8 + 6] == 1) return;   // a light env: rp_lean_solver_kernel steps it
-  }
   // PB: the back part as a kernel of its own (rp_pos_back_kernel: 198 registers, no scratch) has the registers to request the
   // tables of a phase TOGETHER -- clamped indices, unconditional reads into locals, a scheduling barrier, selects -- where the
   // register-bound builds of this body read every table where it is used and under its predicate: a branch, one load and a
@@ -195,11 +148,6 @@ __device__ __forceinline__ void rp_stage_body(const RpModel<T>& M, const RpState
   const int env_active = S.active ? S.active[env] : 1;  // tested after the prologue loads are in flight
   using SM_ = std::conditional_t<(MODE == 0 && PART == 1), SmemFront<T, MD>, Smem<T, MODE, MD>>;
   SM_& sm = rp_smem<SM_, EXT>(ext);
-  constexpr int TC = MD > 9 ? 8 : 4;            // trunk links the chain-blocked solver holds
-  constexpr int NT = TC * (TC + 1) / 2, NREC = NT + TC;  // packed trunk block / per-chain record
-  // the chain records of the tree elimination live at the end of the dense block's LDS (sm.H); the
-  // packed block (rows + its rhs row) may grow up to there
-  constexpr int HSIZE = (RpCaps<T>::HMAX + 1) * (RpCaps<T>::HMAX + 2) / 2;
 #ifdef RPK_POISON_LDS  // debug build: nothing may depend on what a previous workgroup left in LDS
   {
     unsigned* w_ = reinterpret_cast<unsigned*>(&sm);
@@ -212,7 +160,6 @@ __device__ __forceinline__ void rp_stage_body(const RpModel<T>& M, const RpState
   long long prof_t = (long long)__builtin_readcyclecounter();
   const long long kernel_t0 = prof_t;
   const int nl = M.nlink, nk = M.nkey, nv = M.nv, nu = M.nu;
-  const int HREC0 = HSIZE - M.ntree * 5 * NREC;   // first chain record in sm.H = capacity of the packed dense block
   const T h = M.timestep;
 
   // ------------------------------------------------------------ lane constants
@@ -251,35 +198,7 @@ __device__ __forceinline__ void rp_stage_body(const RpModel<T>& M, const RpState
     }
     __builtin_amdgcn_sched_barrier(0);
   }
-  // (not const: the position stage re-reads the record after the collision phase instead of carrying
-  // fourteen integers through it -- it is register-bound there)
-  int parent = isl ? tp[0] : -1;
-  int depth = isl ? tp[1] : -1;
-  int jtype = isl ? tp[2] : 0;
-  int sibrank = isl ? tp[3] : 0;
-  int ltree = isl ? tp[4] : 0;
-  int ldof = isl ? tp[5] : 0;
-  // chain structure (lanes are in preorder: trunk chain, then up to 5 leaf chains)
-  int tbase = isl ? tp[6] : 0, TL = isl ? tp[7] : 0;
-  int ndesc = isl ? tp[8] : 0;
-  // chain lanes: first depth past the end of my chain / chain index; bit c of chainmask:
-  // leaf chain c of my tree exists
-  const int chain_end = isl ? tp[11] : 0, mychain = isl ? tp[12] : 0, chainmask = isl ? tp[13] : 0;
-  // lane of my ancestor at depth e (e <= depth)
-  auto anc_at = [&](int e) -> int { return e < TL ? tbase + e : lane - (depth - e); };
-  int llimited = isl ? tp[9] : 0;
-  int lact = isl ? tp[10] : -1;
-  const T lactcoef = isl ? M.link_act_coef()[L] : (T)0;
-  int hasdof[3];
-  hasdof[0] = isl && llimited; hasdof[1] = lane < nk; hasdof[2] = lane + 64 < nk;
-  const bool isk[2] = {lane < nk, lane + 64 < nk};
-  const int kid[2] = {lane, lane + 64};
-  int kdof[2], kact[2];
-#pragma unroll
-  for (int s = 0; s < 2; s++) {
-    kdof[s] = isk[s] ? kdof_raw[s] : 0;
-    kact[s] = isk[s] ? kact_raw[s] : -1;
-  }
+  RPK_LANE_CONSTANTS
 // Per-lane model constants are re-read from the (L2-resident) tables inside the stage
 // that uses them instead of being pinned in registers for the whole kernel: the kernel
 // is register-bound, and `fresh()` keeps the compiler from hoisting the loads back out
@@ -372,42 +291,24 @@ __device__ __forceinline__ void rp_stage_body(const RpModel<T>& M, const RpState
     lflB_ = isl ? fresh(M.link_fl_B())[L] : (T)0;                                            \
   }                                                                                        \
   const T lflB = lflB_;
-#define RPK_LOAD_DYN                                                                       \
-  const T ldamp = isl ? fresh(M.link_damping())[L] : (T)0;                                   \
-  const T lstiff = isl ? fresh(M.link_stiffness())[L] : (T)0;                                \
-  const T lsref = isl ? fresh(M.link_springref())[L] : (T)0;                                 \
-  const T lfloss = isl ? fresh(M.link_floss())[L] : (T)0;                                    \
-  const T lflR = isl ? fresh(M.link_fl_R())[L] : (T)1;                                       \
-  const T lflD = (T)1 / lflR;                                                              \
-  T kM[2], kstiff[2], ksref[2], kdamp[2], kmass[2], khx[2];                                \
-  _Pragma("unroll") for (int s = 0; s < 2; s++) {                                          \
-    const int K = isk[s] ? kid[s] : 0;                                                     \
-    kM[s] = isk[s] ? fresh(M.key_M())[K] : (T)1;                                             \
-    kstiff[s] = isk[s] ? fresh(M.key_stiffness())[K] : (T)0;                                 \
-    ksref[s] = isk[s] ? fresh(M.key_springref())[K] : (T)0;                                  \
-    kdamp[s] = isk[s] ? fresh(M.key_damping())[K] : (T)0;                                    \
-    kmass[s] = isk[s] ? fresh(M.key_mass())[K] : (T)0;                                       \
-    khx[s] = isk[s] ? fresh(M.key_half())[3 * K] : (T)0;                                     \
-  }
   // actuator owned by this lane (hand actuators only; key actuators live with the key)
   const bool isa = lane < nu && M.act_kind()[lane < nu ? lane : 0] == 0;
   const int A = lane < nu ? lane : 0;
 
   // ------------------------------------------------------------------- state
   const size_t eo = (size_t)env * nv;
-  T q[3], qd[3], qw[3], qapp[3];
-  if constexpr (MODE != 0) {
-    // (the solver builds keep the reads under their predicates: they are over their register budget, and the batch below
-    // cost the fp32 build 22 more spilled registers)
+  T q[3], qd[3], qw[3];
+  T qapp[3];   // (dead, as the control below: see there)
+  if constexpr (MODE == 2) {
+    // (the sensor stage reads under the predicates, as the full-capacity solver stage does; the batch below is the position
+    // stage's, which every substep waits for)
     q[0] = isl ? S.qpos[eo + ldof] : (T)0; qd[0] = isl ? S.qvel[eo + ldof] : (T)0;
     qw[0] = isl ? S.warm[eo + ldof] : (T)0;
-    qapp[0] = (isl && S.qfrc_applied) ? S.qfrc_applied[eo + ldof] : (T)0;
 #pragma unroll
     for (int s = 0; s < 2; s++) {
       q[1 + s] = isk[s] ? S.qpos[eo + kdof[s]] : (T)0;
       qd[1 + s] = isk[s] ? S.qvel[eo + kdof[s]] : (T)0;
       qw[1 + s] = isk[s] ? S.warm[eo + kdof[s]] : (T)0;
-      qapp[1 + s] = (isk[s] && S.qfrc_applied) ? S.qfrc_applied[eo + kdof[s]] : (T)0;
     }
   } else {
     // (ldof / kdof are 0 for lanes without the dof: every address is the env's own state)
@@ -428,6 +329,10 @@ __device__ __forceinline__ void rp_stage_body(const RpModel<T>& M, const RpState
       qw[1 + s] = isk[s] ? qw_[1 + s] : (T)0; qapp[1 + s] = isk[s] ? qa_[1 + s] : (T)0;
     }
   }
+  // (This stage uses neither the applied forces nor the controls: these reads, left from the time when it shared its prologue
+  // with the solver stage, are dead code.  They stay all the same: without the clamped control reads every build of this body
+  // allocates its registers differently, without the applied forces' the front part schedules differently -- measured one by
+  // one, docs/LAB_NOTEBOOK.md "The stage split" -- and code this close to the register limit changes only with a benchmark.)
   T ctrl = (lane < nu) ? S.ctrl[(size_t)env * nu + lane] : (T)0;
   if (lane < nu && M.act_ctrllimited()[A])
     ctrl = fmin(M.act_ctrlrange()[2 * A + 1], fmax(M.act_ctrlrange()[2 * A], ctrl));
@@ -439,10 +344,8 @@ __device__ __forceinline__ void rp_stage_body(const RpModel<T>& M, const RpState
       c = fmin(M.act_ctrlrange()[2 * kact[s] + 1], fmax(M.act_ctrlrange()[2 * kact[s]], c));
     kctrl[s] = c;
   }
-  T time = S.time[env];
   if (env_active == 0) return;  // masked env (all loads above are speculative and harmless)
   if constexpr (PB) { if (ncand_pre < 0) return; }   // (the front part did not run for this env: masked, or heavy)
-
 
   PROF(0);
   // values produced by the position/velocity stage and consumed by the next
@@ -457,9 +360,8 @@ __device__ __forceinline__ void rp_stage_body(const RpModel<T>& M, const RpState
   // of link `lk` at depth e is arithmetic: trunk base + e on the trunk, lk - (depth - e)
   // on lk's own chain.  (depth, trunk length, trunk base) of the links a lane needs:
   int sTL = 0, sTB = 0, salink = 0;          // slot lanes: anchor link of my key
-  auto anc_of = [](int lk, int dl, int tl, int tb, int e) -> int { return e < tl ? tb + e : lk - (dl - e); };
   T ksin[2] = {0, 0}, kcos[2] = {1, 1};
-  int ncon = 0, nkt = 0, nent = 0, maxm = 0;  // contacts, touched keys, Jacobian entries, max per contact
+  int ncon = 0, nkt = 0;  // contacts, touched keys
   // rows
   T fr_aref = 0;
   int lim_sign[3] = {0, 0, 0};
@@ -470,926 +372,9 @@ __device__ __forceinline__ void rp_stage_body(const RpModel<T>& M, const RpState
   T con_dist = 0;
   unsigned long long dirty_mask = 0;  // rows that need the dense block (uniform)
   unsigned long long con_maskA = 0, con_maskB = 0;
-  int niter_last = 0;
 
   const size_t lf = (size_t)env * RPK_NLF * 64 + lane, li = (size_t)env * RPK_NLI * 64 + lane;
-#define LF(i) B.lanef[lf + (size_t)(i) * 64]
-#define LI(i) B.lanei[li + (size_t)(i) * 64]
   {
-    // ======================================================================
-    // MODE 1: ACCELERATION STAGE + EULER  (mj_step2)
-    // ======================================================================
-    if constexpr (MODE == 1) {
-      // ---- what the position/velocity kernel left behind
-      {
-        ncon = B.hdr[env * 8]; nkt = B.hdr[env * 8 + 1];
-        dirty_mask = ((unsigned long long)(unsigned)B.hdr[env * 8 + 3] << 32) | (unsigned)B.hdr[env * 8 + 2];
-        nent = B.hdr[env * 8 + 4]; maxm = B.hdr[env * 8 + 5];
-        // (fields only some lanes own cross for those lanes only: fewer cache lines per env)
-        qbias = LF(0);
-        if (lane < nu) { alen = LF(1); avel = LF(2); }
-        ksin[0] = LF(3); kcos[0] = LF(5);
-        if (isk[1]) { ksin[1] = LF(4); kcos[1] = LF(6); }
-        fr_aref = LF(7);
-        {
-          const int ls = LI(0);
-          lim_sign[0] = (ls & 3) - 1; lim_sign[1] = ((ls >> 2) & 3) - 1; lim_sign[2] = ((ls >> 4) & 3) - 1;
-        }
-#pragma unroll
-        for (int k = 0; k < 3; k++) if (lim_sign[k] != 0) { lim_D[k] = LF(8 + k); lim_aref[k] = LF(11 + k); }
-        if (lane < ncon) {  // the contact lanes' fields: only those lanes' cache lines cross (other lanes: the defaults)
-          con_D = LF(14); con_mu = LF(15);
-#pragma unroll
-          for (int k = 0; k < 3; k++) { con_n[k] = LF(16 + k); con_t1[k] = LF(19 + k); con_t2[k] = LF(22 + k); }
-#pragma unroll
-          for (int k = 0; k < 4; k++) con_aref[k] = LF(25 + k);
-          con_A = LI(1); con_B = LI(2); con_slot = LI(3); con_cross = LI(4);
-          con_maskA = ((unsigned long long)(unsigned)LI(6) << 32) | (unsigned)LI(5);
-          con_maskB = ((unsigned long long)(unsigned)LI(8) << 32) | (unsigned)LI(7);
-        }
-        sdepth = LI(9);
-        if (isl) {
-#pragma unroll
-          for (int e = 0; e <= MD; e++) {
-            Mr[e] = B.RM[((size_t)env * RPK_NLX(MD) + lane) * (MD + 1) + e];
-            sm.RM[lane][e] = Mr[e];
-          }
-        }
-        for (int i = lane; i < nent; i += 64) {
-          const size_t e = (size_t)env * RpCaps<T>::NE + i;
-          sm.entJ[i][0] = B.entJ[e * 3]; sm.entJ[i][1] = B.entJ[e * 3 + 1]; sm.entJ[i][2] = B.entJ[e * 3 + 2];
-          sm.entM[i][0] = B.entM[e * 2]; sm.entM[i][1] = B.entM[e * 2 + 1];
-        }
-        if (lane < 16) {
-          const int* sl = B.slots + (size_t)env * 64;
-          sm.slotkey[lane] = (short)sl[lane];
-          sm.slotlink[lane] = (short)sl[16 + lane];
-          sm.slotmask[lane] = ((unsigned long long)(unsigned)sl[48 + lane] << 32) | (unsigned)sl[32 + lane];
-        }
-        if (lane < RPK_NKEYS / 4) ((int*)sm.keyslot)[lane] = B.keyslot[(size_t)env * (RPK_NKEYS / 4) + lane];
-        WSYNC();
-        {
-          const int sl_ = LI(11);
-          salink = sl_ & 255; sTL = (sl_ >> 8) & 255; sTB = (sl_ >> 16) & 255;
-        }
-      }
-      RPK_LOAD_DYN
-      // ---- actuation [MJ: mj_fwdActuation]
-      T aforce = 0;
-      if (isa) {
-        aforce = M.act_gain()[A] * ctrl + M.act_bias()[3 * A] + M.act_bias()[3 * A + 1] * alen +
-                 M.act_bias()[3 * A + 2] * avel;
-        if (M.act_forcelimited()[A])
-          aforce = fmin(M.act_forcerange()[2 * A + 1], fmax(M.act_forcerange()[2 * A], aforce));
-        sm.actf[lane] = aforce;
-        S.act_force[(size_t)env * nu + lane] = aforce;
-      }
-      WSYNC();
-      T qfs[3], qs[3];
-      {
-        T qact = (isl && lact >= 0) ? lactcoef * sm.actf[lact] : (T)0;
-        T qpas = -lstiff * (q[0] - lsref) - ldamp * qd[0];
-        qfs[0] = isl ? (qpas - qbias + qapp[0] + qact) : (T)0;
-#pragma unroll
-        for (int s = 0; s < 2; s++) {
-          // passive spring/damper, gravity torque m*g*(hx)*cos(q) about +y, actuator
-          // (all key constants are 0 for lanes without a key: no branch needed)
-          const T grav = -kmass[s] * M.gz * khx[s] * kcos[s] - kmass[s] * M.gx * khx[s] * ksin[s];
-          T f = -kstiff[s] * (q[1 + s] - ksref[s]) - kdamp[s] * qd[1 + s] + grav + qapp[1 + s];
-          {
-            if (isk[s] && kact[s] >= 0) {
-              T af = M.act_gain()[kact[s]] * kctrl[s];
-              if (M.act_forcelimited()[kact[s]])
-                af = fmin(M.act_forcerange()[2 * kact[s] + 1], fmax(M.act_forcerange()[2 * kact[s]], af));
-              f += M.act_coef()[2 * kact[s]] * af;
-              S.act_force[(size_t)env * nu + kact[s]] = af;
-            }
-          }
-          qfs[1 + s] = f;
-          qs[1 + s] = f / kM[s];
-        }
-      }
-      PROF(1);
-      // ---- hybrid tree-sparse / dense factor + solve [MJ: mj_factorM / mj_solveLD by levels].
-      // Row r of the symmetric system is held by lane r as Rr[e] = A[r][anc_e(r)]
-      // (diag at e = depth).  Touched keys (nslots of them, lanes nl..nl+nslots-1)
-      // are extra leaves hanging under their anchor link.  Rows whose bit is clear in
-      // `dm` ("clean") only couple to their ancestors and are eliminated leaf-to-root
-      // with no fill-in.  The rows in `dm` ("dirty": supports of cross-chain contacts,
-      // an ancestor-closed set) receive the Schur complement and are solved with a
-      // small dense Cholesky.  The caller has already put the cross-contact blocks into the packed
-      // block sm.H (zeroed + accumulated during the Hessian assembly); the Schur rows are added here.
-      auto tree_solve = [&](T* Rr, T rhs, int nslots, unsigned long long dm) -> T {
-        // trunk length of this lane's tree; a compile-time constant in the FIXED_TL build
-        // (every predicate on it folds: -20 % instructions in the chain elimination)
-        const int TLX = FIXED_TL > 0 ? FIXED_TL : TL;
-        // Chain-blocked elimination.  Each tree is a trunk chain (<= TC links) carrying up
-        // to five leaf chains (<= 5 links).  The first lane of every chain ("leader")
-        // gathers its chain's rows and eliminates the clean links, deepest first, entirely
-        // in registers; what that leaves on the trunk is summed per trunk row, the trunk
-        // leader eliminates the clean trunk links, the dense block (if any) solves the
-        // dirty rows, and the leaders back-substitute.  Same arithmetic as the level-by-
-        // level L^T D L, five LDS hand-overs instead of one per tree level.
-        const bool isslot = !isl && lane < nl + nslots;
-        const bool dirty = (dm >> lane) & 1;
-        const int mydiag = isl ? depth : sdepth + 1;
-        // LDS reads below are issued unconditionally on in-bounds addresses and the value
-        // is selected afterwards: a conditional read costs a branch and serialises the wait.
-        T Dslot = 1;
-        // ---- key leaves first (they hang under chain links): the slot lanes publish their
-        // scaled rows, the link lanes fold them into their register rows
-        if (nslots > 0) {
-          if (isslot) {
-            T Dk = (T)1;
-#pragma unroll
-            for (int e = 0; e <= MD; e++) if (e == mydiag) Dk = Rr[e];
-            if (!dirty) {
-              if (!(Dk >= RPK_MINVAL)) { Dk = RPK_MINVAL; warn |= 4; }
-              Dslot = Dk;
-            }
-            const T inv = dirty ? (T)1 : rcp_nr(Dk);
-#pragma unroll
-            for (int e = 0; e <= MD; e++) if (e <= mydiag) sm.R[lane][e] = e < mydiag ? Rr[e] * inv : Rr[e];
-            sm.Dg[lane] = Dk;
-            sm.xs[lane] = rhs;
-          }
-          WSYNC();
-          if (isl) {
-            for (int sidx = 0; sidx < nslots; sidx++) {
-              const T* Lk = sm.R[nl + sidx];
-              T lrow[MD + 1];
-#pragma unroll
-              for (int e = 0; e <= MD; e++) lrow[e] = Lk[e];
-              const T lk = Lk[depth], dk = sm.Dg[nl + sidx], xk = sm.xs[nl + sidx];
-              if (((sm.slotmask[sidx] >> lane) & 1) && !((dm >> (nl + sidx)) & 1)) {
-                const T t = lk * dk;
-#pragma unroll
-                for (int e = 0; e <= MD; e++) if (e <= depth) Rr[e] -= t * lrow[e];
-                rhs -= lk * xk;
-              }
-            }
-          }
-        }
-        if (isl && depth >= TLX) {
-#pragma unroll
-          for (int e = 0; e <= MD; e++) if (e <= depth) sm.R[lane][e] = Rr[e];
-          sm.xs[lane] = rhs;
-        }
-        WSYNC();
-        PROF(20);
-        // ---- chain leaders: local variables 0..TC-1 = trunk, TC..TC+4 = my chain (depth order)
-        const bool leader = isl && depth == TLX && TLX > 0;
-        const int clen = chain_end - TLX;
-        T Ac[5][TC + 5];   // Ac[ci][j]: chain link ci vs local variable j <= TC+ci
-        T rc_[5], inv_[5];
-        T dT[NT], drT[TC];  // what the eliminated links leave on the trunk block / rhs
-        int mc[5];
-#pragma unroll
-        for (int k = 0; k < NT; k++) dT[k] = 0;
-#pragma unroll
-        for (int k = 0; k < TC; k++) drT[k] = 0;
-        if (leader) {
-#pragma unroll
-          for (int ci = 0; ci < 5; ci++) {
-            const bool pi = ci < clen;
-            mc[ci] = pi && !((dm >> (lane + ci)) & 1);
-            const T* row = sm.R[lane + ci];   // lane + ci < 64: always in bounds
-            const T* rowc = row + TLX;         // chain columns start at depth TLX
-            const T xr_ = sm.xs[lane + ci];
-            rc_[ci] = pi ? xr_ : (T)0;
-#pragma unroll
-            for (int j = 0; j < TC + 5; j++) {
-              if (j <= TC + ci) {
-                const bool pj = j < TC ? j < TLX : (j - TC) < clen;
-                const T raw = j < TC ? row[j] : rowc[j - TC];
-                Ac[ci][j] = (pi && pj) ? raw : (j == TC + ci ? (T)1 : (T)0);
-              }
-            }
-          }
-#pragma unroll
-          for (int ci = 4; ci >= 0; ci--) {
-            const int v = TC + ci;
-            T dv = Ac[ci][v];
-            if (mc[ci] && !(dv >= RPK_MINVAL)) { dv = RPK_MINVAL; warn |= 4; }
-            const T iv = mc[ci] ? rcp_nr(dv) : (T)0;
-            inv_[ci] = iv;
-            T l[TC + 4];
-#pragma unroll
-            for (int i = 0; i < TC + 4; i++) if (i < v) l[i] = Ac[ci][i] * iv;
-            // chain rows above me
-#pragma unroll
-            for (int ci2 = 0; ci2 < 4; ci2++) {
-              if (ci2 < ci) {
-                const int i = TC + ci2;
-#pragma unroll
-                for (int j = 0; j < TC + 5; j++) if (j <= i) Ac[ci2][j] -= l[i] * Ac[ci][j];
-                rc_[ci2] -= l[i] * rc_[ci];
-              }
-            }
-            // trunk block
-#pragma unroll
-            for (int i = 0; i < TC; i++) {
-#pragma unroll
-              for (int j = 0; j < TC; j++) if (j <= i) dT[i * (i + 1) / 2 + j] -= l[i] * Ac[ci][j];
-              drT[i] -= l[i] * rc_[ci];
-            }
-#pragma unroll
-            for (int i = 0; i < TC + 4; i++) if (i < v && mc[ci]) Ac[ci][i] = l[i];
-          }
-          // rows / rhs of the links I did not eliminate go back for the dense block (the
-          // LDS rows of eliminated links are dead, so every present row is stored)
-#pragma unroll
-          for (int ci = 0; ci < 5; ci++) {
-            if (ci < clen) {
-              T* row = sm.R[lane + ci];
-              T* rowc = row + TLX;
-#pragma unroll
-              for (int j = 0; j < TC; j++) if (j < TLX) row[j] = Ac[ci][j];
-#pragma unroll
-              for (int j = TC; j < TC + 5; j++) if (j <= TC + ci) rowc[j - TC] = Ac[ci][j];
-              sm.xs[lane + ci] = rc_[ci];
-            }
-          }
-          // trunk deltas, one NREC-entry record per chain, at the end of the dense block's storage (the
-          // block itself already holds the cross-contact terms; its capacity check leaves this room)
-          T* rec = sm.H + HREC0 + (size_t)(ltree * 5 + mychain) * NREC;
-#pragma unroll
-          for (int k = 0; k < NT; k++) rec[k] = dT[k];
-#pragma unroll
-          for (int k = 0; k < TC; k++) rec[NT + k] = drT[k];
-        }
-        WSYNC();
-        // ---- trunk rows collect the chains' contributions (fixed order: deterministic)
-        if (isl && depth < TLX) {
-          const int tro = depth * (depth + 1) / 2;
-#pragma unroll
-          for (int c = 0; c < 5; c++) {
-            const T* rec = sm.H + HREC0 + (size_t)(ltree * 5 + c) * NREC;
-            T dv[TC];
-#pragma unroll
-            for (int e = 0; e < TC; e++) dv[e] = rec[tro + e < NT ? tro + e : NT - 1];
-            const T dr = rec[NT + depth];
-            const bool has = (chainmask >> c) & 1;
-#pragma unroll
-            for (int e = 0; e < TC; e++) if (has && e <= depth) Rr[e] += dv[e];
-            if (has) rhs += dr;
-          }
-#pragma unroll
-          for (int e = 0; e < TC; e++) if (e <= depth) sm.R[lane][e] = Rr[e];
-          sm.xs[lane] = rhs;
-        }
-        WSYNC();
-        // ---- trunk leader eliminates the clean trunk links (deepest first)
-        const bool tleader = isl && depth == 0;
-        T At[TC][TC], rt[TC], invt[TC];
-        int mt[TC];
-        if (tleader) {
-#pragma unroll
-          for (int i = 0; i < TC; i++) {
-            const bool pi = i < TLX;
-            mt[i] = pi && !((dm >> (lane + i)) & 1);
-            const T xin = sm.xs[lane + i];
-            rt[i] = pi ? xin : (T)0;
-#pragma unroll
-            for (int j = 0; j < TC; j++) {
-              if (j <= i) {
-                const T raw = sm.R[lane + i][j];
-                At[i][j] = pi ? raw : (j == i ? (T)1 : (T)0);
-              }
-            }
-          }
-#pragma unroll
-          for (int v = TC - 1; v >= 0; v--) {
-            T dv = At[v][v];
-            if (mt[v] && !(dv >= RPK_MINVAL)) { dv = RPK_MINVAL; warn |= 4; }
-            const T iv = mt[v] ? rcp_nr(dv) : (T)0;
-            invt[v] = iv;
-            T l[TC - 1];
-#pragma unroll
-            for (int i = 0; i < TC - 1; i++) if (i < v) l[i] = At[v][i] * iv;
-#pragma unroll
-            for (int i = 0; i < TC - 1; i++) {
-              if (i < v) {
-#pragma unroll
-                for (int j = 0; j < TC - 1; j++) if (j <= i) At[i][j] -= l[i] * At[v][j];
-                rt[i] -= l[i] * rt[v];
-              }
-            }
-#pragma unroll
-            for (int i = 0; i < TC - 1; i++) if (i < v && mt[v]) At[v][i] = l[i];
-          }
-#pragma unroll
-          for (int i = 0; i < TC; i++) {
-            if (i < TLX) {  // (rows of eliminated links are dead: store them all)
-#pragma unroll
-              for (int j = 0; j < TC; j++) if (j <= i) sm.R[lane + i][j] = At[i][j];
-              sm.xs[lane + i] = rt[i];
-            }
-          }
-        }
-        WSYNC();
-        PROF(21);
-        // ---- dense block on the dirty rows (Schur complement + cross-contact terms)
-        if (dm) {   // (the caller passes dm = 0 when the block would not fit: RP_WARN_DENSE_FULL)
-          T x = (isl || isslot) ? sm.xs[lane] : (T)0;
-          WSYNC();
-          const int nD = __popcll(dm);
-          auto cidx = [&](int l) -> int { return __popcll(dm & lanemask_lt(l)); };
-          const int ci = cidx(lane);
-          // every (row, ancestor) element has exactly one owner lane: plain read-modify-write
-          if (dirty) {
-            if (isl) {
-              for (int e = 0; e <= depth; e++) sm.H[tri(ci, cidx(anc_at(e)))] += sm.R[lane][e];
-            } else {
-              sm.H[tri(ci, ci)] += sm.R[lane][mydiag];
-#pragma unroll
-              for (int e = 0; e < MD; e++) {
-                if (e <= sdepth) {
-                  const int a_ = anc_of(salink, sdepth, sTL, sTB, e);
-                  if ((dm >> a_) & 1) sm.H[tri(ci, cidx(a_))] += sm.R[lane][e];
-                }
-              }
-            }
-          }
-          WSYNC();
-          PROF(22);
-          PROF(23);
-          // the rhs of compact row r (owned by a dirty lane) is row nD of the packed block
-          if (dirty) sm.H[tri(nD, 0) + ci] = x;
-          WSYNC();
-          T xr = dense_factor_solve(sm.H, nD, lane, &warn);
-          WSYNC();
-          if (lane < nD) sm.Dg[lane] = xr;
-          WSYNC();
-          if (dirty) sm.xs[lane] = sm.Dg[ci];
-          WSYNC();
-        }
-        PROF(25);
-        // ---- back-substitution: trunk leader, then chain leaders, then key leaves
-        if (tleader) {
-          T xt[TC];
-#pragma unroll
-          for (int v = 0; v < TC; v++) xt[v] = sm.xs[lane + v];
-#pragma unroll
-          for (int v = 0; v < TC; v++) {
-            T xv = rt[v] * invt[v];
-#pragma unroll
-            for (int i = 0; i < TC - 1; i++) if (i < v) xv -= At[v][i] * xt[i];
-            xt[v] = mt[v] ? xv : (v < TLX ? xt[v] : (T)0);
-            if (v < TLX) sm.xs[lane + v] = xt[v];
-          }
-        }
-        WSYNC();
-        if (leader) {
-          T xl[TC + 5];
-#pragma unroll
-          for (int j = 0; j < TC; j++) { const T xin = sm.xs[tbase + j]; xl[j] = j < TLX ? xin : (T)0; }
-#pragma unroll
-          for (int ci = 0; ci < 5; ci++) xl[TC + ci] = sm.xs[lane + ci];
-#pragma unroll
-          for (int ci = 0; ci < 5; ci++) {
-            const int v = TC + ci;
-            T xv = rc_[ci] * inv_[ci];
-#pragma unroll
-            for (int i = 0; i < TC + 4; i++) if (i < v) xv -= Ac[ci][i] * xl[i];
-            xl[v] = mc[ci] ? xv : (ci < clen ? xl[v] : (T)0);
-            if (ci < clen) sm.xs[lane + ci] = xl[v];
-          }
-        }
-        WSYNC();
-        T x = isl ? sm.xs[lane] : (T)0;
-        if (isslot) {
-          x = sm.xs[lane];
-          if (!dirty) {
-            x = rhs / Dslot;
-#pragma unroll
-            for (int e = 0; e < MD; e++)
-              if (e <= sdepth) x -= sm.R[lane][e] * sm.xs[anc_of(salink, sdepth, sTL, sTB, e)];
-          }
-        }
-        WSYNC();
-        return x;
-      };
-      // ---- qacc_smooth = M^-1 qfrc_smooth (M is always tree-sparse)
-      {
-        T Rr[MD + 1];
-#pragma unroll
-        for (int e = 0; e <= MD; e++) Rr[e] = Mr[e];
-        qs[0] = tree_solve(Rr, qfs[0], 0, 0ull);
-      }
-
-      PROF(2);
-      // ---- constraint solve [MJ: mj_solNewton]
-      const int nsys = nl + nkt;
-      const bool hascon = lane < ncon && con_D > 0;
-      const T scale = (T)1 / (M.meaninertia * (T)(nv > 1 ? nv : 1));
-      T qa[3], Ma[3], qfc[3];
-      Rows<T> jar, frc;
-      int fr_quad = 0, lim_act[3] = {0, 0, 0}, con_act[4] = {0, 0, 0, 0};
-
-      // Contact terms run on "entry lanes": entry = (contact, one dof it touches) with the
-      // 3-vector d(contact point velocity)/d(qvel of that dof).  Lane l of pass p owns entry
-      // 64 p + l; sums over the entries of a contact / over the contacts of a dof are
-      // fire-and-forget LDS adds.
-      // y = J x for the rows owned by this lane (x in per-lane slot registers)
-      auto mulJ = [&](const T* x, Rows<T>& out) {
-        sm.vec[0][lane] = x[0];
-        if (isk[0]) sm.keyvec[0][kid[0]] = x[1];
-        if (isk[1]) sm.keyvec[0][kid[1]] = x[2];
-        if (lane < ncon) { sm.cv[lane][0] = 0; sm.cv[lane][1] = 0; sm.cv[lane][2] = 0; }
-        WSYNC();
-        out.fr = x[0];
-#pragma unroll
-        for (int s = 0; s < 3; s++) out.lim[s] = (T)lim_sign[s] * x[s];
-        for (int e0 = 0; e0 < nent; e0 += 64) {
-          const int e = e0 + lane < nent ? e0 + lane : nent - 1;
-          const int m0 = sm.entM[e][0];
-          const int ln = RPK_EM_LANE(m0), c = RPK_EM_CON(m0);
-          const T j0 = sm.entJ[e][0], j1 = sm.entJ[e][1], j2 = sm.entJ[e][2];
-          const T xl = sm.vec[0][ln];
-          const T xk = sm.keyvec[0][sm.slotkey[ln >= nl ? ln - nl : 0]];
-          const T xv = ln < nl ? xl : xk;
-          if (e0 + lane < nent) {
-            lds_add(&sm.cv[c][0], j0 * xv); lds_add(&sm.cv[c][1], j1 * xv); lds_add(&sm.cv[c][2], j2 * xv);
-          }
-        }
-        WSYNC();
-        T vc[3] = {0, 0, 0};
-        if (lane < ncon) { vc[0] = sm.cv[lane][0]; vc[1] = sm.cv[lane][1]; vc[2] = sm.cv[lane][2]; }
-        T vn = dot3(con_n, vc), v1 = con_mu * dot3(con_t1, vc), v2 = con_mu * dot3(con_t2, vc);
-        out.con[0] = vn + v1; out.con[1] = vn - v1; out.con[2] = vn + v2; out.con[3] = vn - v2;
-        WSYNC();
-      };
-      // forces + active set from jar; returns this lane's share of the constraint cost
-      auto update = [&](const Rows<T>& ja, Rows<T>& f) -> T {
-        T cost = 0;
-        f.fr = 0; fr_quad = 0;
-        if (isl && lfloss > 0) {
-          T x = ja.fr, rf = lflR * lfloss;
-          if (x <= -rf) { f.fr = lfloss; cost += -(T)0.5 * rf * lfloss - lfloss * x; }
-          else if (x >= rf) { f.fr = -lfloss; cost += -(T)0.5 * rf * lfloss + lfloss * x; }
-          else { f.fr = -lflD * x; fr_quad = 1; cost += (T)0.5 * lflD * x * x; }
-        }
-#pragma unroll
-        for (int s = 0; s < 3; s++) {
-          f.lim[s] = 0; lim_act[s] = 0;
-          if (lim_sign[s] != 0 && ja.lim[s] < 0) {
-            f.lim[s] = -lim_D[s] * ja.lim[s]; lim_act[s] = 1;
-            cost += (T)0.5 * lim_D[s] * ja.lim[s] * ja.lim[s];
-          }
-        }
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-          f.con[r] = 0; con_act[r] = 0;
-          if (hascon && ja.con[r] < 0) {
-            f.con[r] = -con_D * ja.con[r]; con_act[r] = 1;
-            cost += (T)0.5 * con_D * ja.con[r] * ja.con[r];
-          }
-        }
-        return cost;
-      };
-      // out = J^T f
-      auto mulJT = [&](const Rows<T>& f, T* out) {
-        out[0] = f.fr + (T)lim_sign[0] * f.lim[0];
-        out[1] = (T)lim_sign[1] * f.lim[1];
-        out[2] = (T)lim_sign[2] * f.lim[2];
-        T fn = f.con[0] + f.con[1] + f.con[2] + f.con[3];
-        T f1 = con_mu * (f.con[0] - f.con[1]), f2 = con_mu * (f.con[2] - f.con[3]);
-        if (lane < ncon) {
-#pragma unroll
-          for (int k = 0; k < 3; k++) sm.cv[lane][k] = fn * con_n[k] + f1 * con_t1[k] + f2 * con_t2[k];
-        }
-        sm.jt[lane] = 0;
-        WSYNC();
-        for (int e0 = 0; e0 < nent; e0 += 64) {
-          const int e = e0 + lane < nent ? e0 + lane : nent - 1;
-          const int m0 = sm.entM[e][0];
-          const int ln = RPK_EM_LANE(m0), c = RPK_EM_CON(m0);
-          const T v = sm.entJ[e][0] * sm.cv[c][0] + sm.entJ[e][1] * sm.cv[c][1] + sm.entJ[e][2] * sm.cv[c][2];
-          if (e0 + lane < nent) lds_add(&sm.jt[ln], v);
-        }
-        WSYNC();
-        if (isl) out[0] += sm.jt[lane];
-#pragma unroll
-        for (int s = 0; s < 2; s++) {
-          const int ks = isk[s] ? sm.keyslot[kid[s]] : -1;
-          const T v = sm.jt[ks >= 0 ? nl + ks : 0];
-          if (ks >= 0) out[1 + s] += v;
-        }
-        WSYNC();
-      };
-      auto gauss = [&](const T* qa_, const T* Ma_) -> T {
-        T g = 0;
-#pragma unroll
-        for (int s = 0; s < 3; s++) g += (Ma_[s] - qfs[s]) * (qa_[s] - qs[s]);
-        return (T)0.5 * g;
-      };
-      // y = M x with the tree-sparse rows: ancestor terms from this lane's own row
-      // (registers), descendant terms from the rows of the next `ndesc` lanes (preorder).
-      auto mulM = [&](const T* x, T* out) {
-        sm.xs[lane] = x[0];
-        WSYNC();
-        T y = 0;
-        if (isl) {
-          // (reads in flight together, terms in the old order: a predicated read per ancestor and a read pair per
-          // descendant were up to 35 dependent LDS round trips for a trunk link)
-          T xa_[MD + 1];
-#pragma unroll
-          for (int e = 0; e <= MD; e++) xa_[e] = sm.xs[e <= depth ? anc_at(e) : lane];
-          __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-          for (int e = 0; e <= MD; e++) { const T t_ = y + Mr[e] * xa_[e]; y = e <= depth ? t_ : y; }
-          int j = 1;
-          for (; j + 3 <= ndesc; j += 4) {
-            T m_[4], x_[4];
-#pragma unroll
-            for (int u = 0; u < 4; u++) { m_[u] = sm.RM[lane + j + u][depth]; x_[u] = sm.xs[lane + j + u]; }
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int u = 0; u < 4; u++) y += m_[u] * x_[u];
-          }
-          for (; j <= ndesc; j++) y += sm.RM[lane + j][depth] * sm.xs[lane + j];
-        }
-        out[0] = y;
-        out[1] = kM[0] * x[1];
-        out[2] = kM[1] * x[2];
-        WSYNC();
-      };
-      auto sub_aref = [&](Rows<T>& r) {
-        r.fr -= fr_aref;
-#pragma unroll
-        for (int s = 0; s < 3; s++) r.lim[s] -= lim_aref[s];
-#pragma unroll
-        for (int k = 0; k < 4; k++) r.con[k] -= con_aref[k];
-      };
-
-      // any constraint rows at all?  (uniform)
-      int anyrow = (isl && lfloss > 0) || lim_sign[0] || lim_sign[1] || lim_sign[2] || hascon;
-      anyrow = __ballot(anyrow) != 0ull;
-      niter_last = 0;
-      if (!anyrow) {
-#pragma unroll
-        for (int s = 0; s < 3; s++) { qa[s] = qs[s]; qfc[s] = 0; }
-      } else {
-        // warmstart [MJ: warmstart()]
-        Rows<T> jtmp;
-        mulJ(qs, jtmp); sub_aref(jtmp);
-        T cost_smooth = wave_sum(update(jtmp, frc));
-#pragma unroll
-        for (int s = 0; s < 3; s++) qa[s] = qw[s];
-        mulM(qa, Ma);
-        mulJ(qa, jar); sub_aref(jar);
-        T cost = wave_sum(update(jar, frc) + gauss(qa, Ma));
-#ifdef RP_SOLVER_TRACE   // (emulator-only diagnostics)
-        if (env == 0 && lane < ncon) printf("  contact %d: D %.6e aref %.6e %.6e jar(smooth) %.6e %.6e %.6e %.6e cross %d A %d B %d\n", lane, (double)con_D, (double)con_aref[0], (double)con_aref[2],
-                                (double)jtmp.con[0], (double)jtmp.con[1], (double)jtmp.con[2], (double)jtmp.con[3], con_cross, con_A, con_B);
-        if (lane == 0) printf("solver trace: env %d ncon %d nent %d cost_smooth %.10e cost_warm %.10e\n", env, ncon, nent, (double)cost_smooth, (double)cost);
-#endif
-        if (cost > cost_smooth) {
-#pragma unroll
-          for (int s = 0; s < 3; s++) { qa[s] = qs[s]; Ma[s] = qfs[s]; }
-          jar = jtmp;
-          cost = wave_sum(update(jar, frc) + gauss(qa, Ma));
-        }
-        mulJT(frc, qfc);
-        T grad[3];
-#pragma unroll
-        for (int s = 0; s < 3; s++) grad[s] = Ma[s] - qfs[s] - qfc[s];
-
-        PROF(3);
-        const int maxit = S.max_newton;
-        for (int iter = 0; iter < maxit; iter++) {
-          // ---- H = M + J^T D J on the coupled system (hand dofs + touched keys)
-          // key diagonals and gradients to the solver slots
-#pragma unroll
-          for (int s = 0; s < 2; s++) if (isk[s]) {
-            sm.keyvec[0][kid[s]] = kM[s] + (lim_act[1 + s] ? lim_D[1 + s] : (T)0);
-            sm.keyvec[1][kid[s]] = grad[1 + s];
-          }
-          WSYNC();
-          const bool isslot = !isl && lane < nsys;
-          T rhs = isl ? grad[0] : (T)0, slotdiag = 0;
-          if (isslot) {
-            int k = sm.slotkey[lane - nl];
-            slotdiag = sm.keyvec[0][k];
-            rhs = sm.keyvec[1][k];
-          }
-          const T mydiag_add = (fr_quad ? lflD : (T)0) + (lim_act[0] ? lim_D[0] : (T)0);
-          // per-contact 3x3 weight C = sum_r D_r w_r w_r^T with w = n +- mu t
-          T Cm[6];  // xx yy zz xy xz yz
-          {
-            T Dr[4];
-#pragma unroll
-            for (int r = 0; r < 4; r++) Dr[r] = con_act[r] ? con_D : (T)0;
-            T sn = Dr[0] + Dr[1] + Dr[2] + Dr[3];
-            T a1 = con_mu * (Dr[0] - Dr[1]), a2 = con_mu * (Dr[2] - Dr[3]);
-            T b1 = con_mu * con_mu * (Dr[0] + Dr[1]), b2 = con_mu * con_mu * (Dr[2] + Dr[3]);
-            const int ia[6] = {0, 1, 2, 0, 0, 1}, ib[6] = {0, 1, 2, 1, 2, 2};
-#pragma unroll
-            for (int e = 0; e < 6; e++) {
-              int a = ia[e], b = ib[e];
-              Cm[e] = sn * con_n[a] * con_n[b] + a1 * (con_n[a] * con_t1[b] + con_t1[a] * con_n[b]) +
-                      a2 * (con_n[a] * con_t2[b] + con_t2[a] * con_n[b]) + b1 * con_t1[a] * con_t1[b] +
-                      b2 * con_t2[a] * con_t2[b];
-            }
-          }
-          T x;
-          {
-            // rows: mass matrix + per-dof terms (link lanes), key diagonal (slot lanes) ...
-            if (lane < ncon) {
-#pragma unroll
-              for (int e = 0; e < 6; e++) sm.cC[lane][e] = Cm[e];
-            }
-            if (isl) {
-#pragma unroll
-              for (int e = 0; e <= MD; e++) if (e <= depth) sm.R[lane][e] = Mr[e] + (e == depth ? mydiag_add : (T)0);
-            } else if (isslot) {
-#pragma unroll
-              for (int e = 0; e <= MD; e++) if (e <= sdepth + 1) sm.R[lane][e] = e == sdepth + 1 ? slotdiag : (T)0;
-            }
-            WSYNC();
-            // ... + J^T C J of every contact.  Entry lane a of contact c holds u = C_c J_a and
-            // walks the entries b <= a of its contact (dofs in lane order: b is an ancestor
-            // of a, or the same dof): single-chain contacts add u.J_b to row(a)[col(b)] of the
-            // tree rows, cross-chain contacts to the packed dense block of the dirty rows (zeroed
-            // here; tree_solve adds the Schur complement of the clean rows to it) -- one pass over
-            // the entries for both destinations.
-            unsigned long long dmx = dirty_mask;
-            if (dmx && tri(__popcll(dmx) + 1, 0) > HREC0) { warn |= 32; dmx = 0; }  // cannot hold the block: drop cross terms
-            if (dmx) {
-              const int nD = __popcll(dmx);
-              for (int i = lane; i < tri(nD, 0); i += 64) sm.H[i] = 0;
-            }
-            auto cidx = [&](int l) -> int { return __popcll(dmx & lanemask_lt(l)); };
-            WSYNC();
-            {
-              for (int e0 = 0; e0 < nent; e0 += 64) {
-                const bool valid = e0 + lane < nent;
-                const int e = valid ? e0 + lane : nent - 1;
-                const int m0 = sm.entM[e][0], m1 = sm.entM[e][1];
-                const int ln = RPK_EM_LANE(m0), c = RPK_EM_CON(m0);
-                const int base = RPK_EM_BASE(m1), rank = RPK_EM_RANK(m1);
-                const T ja0 = sm.entJ[e][0], ja1 = sm.entJ[e][1], ja2 = sm.entJ[e][2];
-                const T* C = sm.cC[c];
-                const T C0 = C[0], C1 = C[1], C2 = C[2], C3 = C[3], C4 = C[4], C5 = C[5];
-                const T u0 = C0 * ja0 + C3 * ja1 + C4 * ja2;
-                const T u1 = C3 * ja0 + C1 * ja1 + C5 * ja2;
-                const T u2 = C4 * ja0 + C5 * ja1 + C2 * ja2;
-                const bool cross = RPK_EM_CROSS(m0) != 0;
-                const bool mine = valid && (!cross || dmx != 0);
-                const int cia = cross ? cidx(ln) : 0;
-                for (int k0 = 0; k0 < maxm; k0 += 4) {
-                  // four entries per trip: the twelve LDS reads go out together
-                  int mb[4];
-                  T val[4];
-#pragma unroll
-                  for (int u = 0; u < 4; u++) {
-                    const int b = base + k0 + u < nent ? base + k0 + u : nent - 1;
-                    mb[u] = sm.entM[b][0];
-                    val[u] = u0 * sm.entJ[b][0] + u1 * sm.entJ[b][1] + u2 * sm.entJ[b][2];
-                  }
-#pragma unroll
-                  for (int u = 0; u < 4; u++) {
-                    if (mine && k0 + u <= rank) {
-                      T* dst = cross ? &sm.H[tri(cia, cidx(RPK_EM_LANE(mb[u])))] : &sm.R[ln][RPK_EM_COL(mb[u])];
-                      lds_add(dst, val[u]);
-                    }
-                  }
-                }
-              }
-            }
-            WSYNC();
-            T Rr[MD + 1];
-#pragma unroll
-            for (int e = 0; e <= MD; e++) Rr[e] = sm.R[lane][e];
-            WSYNC();
-            PROF(4);
-            x = tree_solve(Rr, rhs, nkt, dmx);
-          }
-          T search[3];
-          search[0] = isl ? -x : (T)0;
-          if (!isl && lane < nsys) sm.keyvec[0][sm.slotkey[lane - nl]] = -x;
-          WSYNC();
-#pragma unroll
-          for (int s = 0; s < 2; s++) {
-            // branch-free on purpose (selects, no divergent region around the key slots: see
-            // the toolchain note in DESIGN.md); kM is 1 for lanes without a key
-            const int kk = isk[s] ? kid[s] : 0;
-            const int ks_ = sm.keyslot[kk];
-            const T via_slot = sm.keyvec[0][kk];
-            const T own = -grad[1 + s] / (kM[s] + (lim_act[1 + s] ? lim_D[1 + s] : (T)0));
-            search[1 + s] = isk[s] ? (ks_ >= 0 ? via_slot : own) : (T)0;
-          }
-          WSYNC();
-          PROF(5);
-          T snorm = N::sqrt(wave_sum(search[0] * search[0] + search[1] * search[1] + search[2] * search[2]));
-          if (!(snorm >= RPK_MINVAL)) break;
-          T Mv[3];
-          mulM(search, Mv);
-          Rows<T> jv;
-          mulJ(search, jv);
-          T g0 = 0, g1 = 0, g2 = 0;
-#pragma unroll
-          for (int s = 0; s < 3; s++) {
-            g0 += (Ma[s] - qfs[s]) * (qa[s] - qs[s]);
-            g1 += search[s] * (Ma[s] - qfs[s]);
-            g2 += search[s] * Mv[s];
-          }
-          g0 = (T)0.5 * wave_sum(g0); g1 = wave_sum(g1); g2 = (T)0.5 * wave_sum(g2);
-          PROF(6);
-          // ---- exact line search [MJ: PrimalSearch]
-          // [MJ: PrimalPrepare] along the search direction every row's cost is a quadratic in alpha while
-          // the row stays in one zone: q0 + alpha q1 + alpha^2 q2 with q = D (jar^2/2, jar jv, jv^2/2).
-          // The coefficients are formed once per Newton iteration; an evaluation then only tests each
-          // row's zone at alpha and sums the coefficients of the active rows [MJ: PrimalEval].  Rows a
-          // lane does not own get zero coefficients.
-          T qfr[3] = {0, 0, 0}, qfl[2] = {0, 0}, frf = -1;   // friction row: quadratic zone, linear zones (+-), zone bound R f
-          if (isl && lfloss > 0) {
-            frf = lflR * lfloss;
-            qfr[0] = (T)0.5 * lflD * jar.fr * jar.fr; qfr[1] = lflD * jar.fr * jv.fr; qfr[2] = (T)0.5 * lflD * jv.fr * jv.fr;
-            qfl[0] = -(T)0.5 * frf * lfloss; qfl[1] = lfloss * jar.fr;   // linear zones: qfl[0] -+ qfl[1], slope -+ lfloss jv
-          }
-          const T frs = lfloss * jv.fr;
-          T qlim[3][3], qcon[4][3];
-#pragma unroll
-          for (int s = 0; s < 3; s++) {
-            const T Dp = lim_sign[s] != 0 ? lim_D[s] : (T)0;
-            qlim[s][0] = (T)0.5 * Dp * jar.lim[s] * jar.lim[s]; qlim[s][1] = Dp * jar.lim[s] * jv.lim[s];
-            qlim[s][2] = (T)0.5 * Dp * jv.lim[s] * jv.lim[s];
-          }
-#pragma unroll
-          for (int r = 0; r < 4; r++) {
-            const T Dp = hascon ? con_D : (T)0;
-            qcon[r][0] = (T)0.5 * Dp * jar.con[r] * jar.con[r]; qcon[r][1] = Dp * jar.con[r] * jv.con[r];
-            qcon[r][2] = (T)0.5 * Dp * jv.con[r] * jv.con[r];
-          }
-          const bool any_con = ncon > 0;
-          // phi(alpha) and its first two derivatives; the one-sided Newton iterations on phi' never
-          // read the cost and skip that wave reduction
-          auto ls_eval = [&](T alpha, T& d1, T& d2, const bool with_cost) -> T {
-#ifdef RPK_LS_COUNTER
-            if (S.prof && env == 0 && lane == 0) sm.prof[26] += 1;  // evaluations (debug counter)
-#endif
-            T s0 = 0, s1 = 0, s2 = 0;
-            {
-              const T xx = jar.fr + alpha * jv.fr;
-              const bool lo_ = xx <= -frf, hi_ = xx >= frf;   // (frf < 0 on lanes without the row: both true, zero coefficients)
-              s0 = lo_ ? qfl[0] - qfl[1] : (hi_ ? qfl[0] + qfl[1] : qfr[0]);
-              s1 = lo_ ? -frs : (hi_ ? frs : qfr[1]);
-              s2 = (lo_ || hi_) ? (T)0 : qfr[2];
-              if (frf < 0) { s0 = 0; s1 = 0; }
-            }
-#pragma unroll
-            for (int s = 0; s < 3; s++) {
-              const T xx = jar.lim[s] + alpha * jv.lim[s];
-              if (xx < 0) { s0 += qlim[s][0]; s1 += qlim[s][1]; s2 += qlim[s][2]; }
-            }
-            if (any_con) {
-#pragma unroll
-              for (int r = 0; r < 4; r++) {
-                const T xx = jar.con[r] + alpha * jv.con[r];
-                if (xx < 0) { s0 += qcon[r][0]; s1 += qcon[r][1]; s2 += qcon[r][2]; }
-              }
-            }
-            s1 = wave_sum(s1) + g1; s2 = wave_sum(s2) + g2;
-            d1 = s1 + (T)2 * alpha * s2;
-            d2 = (T)2 * s2;
-            if (!with_cost) return (T)0;
-            s0 = wave_sum(s0) + g0;
-            return s0 + alpha * (s1 + alpha * s2);
-          };
-          T gtol = M.tolerance * M.ls_tolerance * snorm / scale;
-          // phi at alpha = 0 needs no row evaluation: phi(0) is the current cost,
-          // phi'(0) = grad . search, and phi''(0) = search^T H search = -phi'(0) because the
-          // search direction solves H search = -grad.  The first trial point is the full
-          // Newton step alpha = 1.
-          // (fp64 only: in fp32 the cost carried over from the last update and the cost
-          // formula of ls_eval differ by more than the improvements being compared.)
-          T f0, h0, c0;
-          if constexpr (sizeof(T) == 8) {
-            f0 = wave_sum(grad[0] * search[0] + grad[1] * search[1] + grad[2] * search[2]);
-            h0 = -f0; c0 = cost;
-          } else {
-            c0 = ls_eval((T)0, f0, h0, true);
-          }
-          // [MJ: engine_solver.c PrimalSearch, restated; the oracle's primal_search is the same
-          // procedure written sequentially]  All of this is wave-uniform scalar control flow; a
-          // point's cost is only reduced where the procedure reads it.  (Measured alternatives with
-          // fewer inlined copies of ls_eval -- a state machine around one evaluation site, a to-do
-          // list around two -- were 1 ... 4 % slower than this straight transcription.)
-          struct LsPnt { T a, c, d0, d1; };
-          auto ls_point = [&](T al, const bool with_cost) -> LsPnt {
-            LsPnt p; p.a = al; p.c = ls_eval(al, p.d0, p.d1, with_cost); return p;
-          };
-          T alpha = 0;
-          if (h0 > 0) {
-            const int max_ls = S.max_ls;
-            int evals = 2;                       // (alpha = 0 and the first Newton point)
-            const LsPnt p0 = {(T)0, c0, f0, h0};
-            LsPnt p1 = ls_point(-f0 / h0, true);  // always one Newton step
-            if (p0.c < p1.c) p1 = p0;
-            alpha = p1.a;
-            if (!(N::abs(p1.d0) < gtol)) {
-              const T dir = p1.d0 < 0 ? (T)1 : (T)-1;
-              LsPnt p2 = p1;
-              bool p2update = false, converged = false;
-              while (p1.d0 * dir <= -gtol && evals < max_ls) {   // one-sided search
-                p2 = p1; p2update = true;
-                p1 = ls_point(p1.a - p1.d0 / p1.d1, false); evals++;
-                if (N::abs(p1.d0) < gtol) { converged = true; break; }
-              }
-              alpha = p1.a;   // converged, or failed to bracket
-              if (!converged && evals < max_ls && p2update) {     // bracketed search
-                LsPnt p2next = p1;   // (its cost is never read: it is not converged, and the costs of the bracket ends are re-evaluated below)
-                LsPnt p1next = ls_point(p1.a - p1.d0 / p1.d1, true); evals++;
-                // [MJ: updateBracket] the candidate on p's side of the root whose slope is closest to zero
-                auto update_bracket = [&](LsPnt& p, const LsPnt& ca, const LsPnt& cb, const LsPnt& cc, LsPnt& pnext) -> bool {
-                  bool moved = false;
-                  auto consider = [&](const LsPnt& c) {
-                    if ((p.d0 < 0 && c.d0 < 0 && p.d0 < c.d0) || (p.d0 > 0 && c.d0 > 0 && p.d0 > c.d0)) { p = c; moved = true; }
-                  };
-                  consider(ca); consider(cb); consider(cc);
-                  if (moved) { pnext = ls_point(p.a - p.d0 / p.d1, true); evals++; }
-                  return moved;
-                };
-                bool settled = false;
-                while (evals < max_ls) {
-                  const LsPnt pmid = ls_point((T)0.5 * (p1.a + p2.a), true); evals++;
-                  const LsPnt ca = p1next, cb = p2next;   // this round's candidates: ca, cb, pmid
-                  T bestc = 0; bool found = false;
-                  if (N::abs(ca.d0) < gtol) { found = true; bestc = ca.c; alpha = ca.a; }
-                  if (N::abs(cb.d0) < gtol && (!found || cb.c < bestc)) { found = true; bestc = cb.c; alpha = cb.a; }
-                  if (N::abs(pmid.d0) < gtol && (!found || pmid.c < bestc)) { found = true; alpha = pmid.a; }
-                  if (found) { settled = true; break; }
-                  const bool b1 = update_bracket(p1, ca, cb, pmid, p1next);
-                  const bool b2 = update_bracket(p2, ca, cb, pmid, p2next);
-                  if (!b1 && !b2) { alpha = pmid.a; settled = true; break; }   // numerical accuracy reached
-                }
-                if (!settled) {   // evaluations exhausted: the better end of the bracket, if it beats alpha = 0
-                  T t1, t2;
-                  const T c1 = ls_eval(p1.a, t1, t2, true), c2 = ls_eval(p2.a, t1, t2, true);
-                  alpha = (c1 <= c2 && c1 < p0.c) ? p1.a : ((c2 <= c1 && c2 < p0.c) ? p2.a : (T)0);
-                }
-              }
-            }
-          }
-          PROF(7);
-          if (!(alpha > 0)) break;
-#pragma unroll
-          for (int s = 0; s < 3; s++) { qa[s] += alpha * search[s]; Ma[s] += alpha * Mv[s]; }
-          jar.fr += alpha * jv.fr;
-#pragma unroll
-          for (int s = 0; s < 3; s++) jar.lim[s] += alpha * jv.lim[s];
-#pragma unroll
-          for (int r = 0; r < 4; r++) jar.con[r] += alpha * jv.con[r];
-          T oldcost = cost;
-          cost = wave_sum(update(jar, frc) + gauss(qa, Ma));
-          mulJT(frc, qfc);
-          niter_last = iter + 1;
-          T gn = 0;
-#pragma unroll
-          for (int s = 0; s < 3; s++) { grad[s] = Ma[s] - qfs[s] - qfc[s]; gn += grad[s] * grad[s]; }
-          gn = N::sqrt(wave_sum(gn));
-          PROF(8);
-          if (scale * (oldcost - cost) < M.tolerance || scale * gn < M.tolerance) break;
-        }
-      }
-#pragma unroll
-      for (int s = 0; s < 3; s++) qw[s] = qa[s];
-      // forces of the pyramidal contact rows, for the acceleration-stage sensors (MODE 2)
-      if (S.con_force && lane < RPK_NCOUT) {
-#pragma unroll
-        for (int r = 0; r < 4; r++)
-          S.con_force[((size_t)env * RPK_NCOUT + lane) * 4 + r] = (anyrow && lane < ncon) ? frc.con[r] : (T)0;
-      }
-
-      PROF(8);
-      // ---- Euler with implicit joint damping [MJ: mj_Euler, eulerdamp]
-      T qe[3];
-      {
-        T Rr[MD + 1];
-#pragma unroll
-        for (int e = 0; e <= MD; e++) Rr[e] = Mr[e] + ((isl && e == depth) ? h * ldamp : (T)0);
-        qe[0] = tree_solve(Rr, qfs[0] + qfc[0], 0, 0ull);
-      }
-#pragma unroll
-      for (int s = 0; s < 2; s++) qe[1 + s] = (qfs[1 + s] + qfc[1 + s]) / (kM[s] + h * kdamp[s]);
-#pragma unroll
-      for (int s = 0; s < 3; s++) { qd[s] += h * qe[s]; q[s] += h * qd[s]; }
-      time += h;
-      PROF(9);
-      // ---- new state
-      if (isl) { S.qpos[eo + ldof] = q[0]; S.qvel[eo + ldof] = qd[0]; S.warm[eo + ldof] = qw[0]; }
-#pragma unroll
-      for (int s = 0; s < 2; s++) if (isk[s]) {
-        S.qpos[eo + kdof[s]] = q[1 + s]; S.qvel[eo + kdof[s]] = qd[1 + s]; S.warm[eo + kdof[s]] = qw[1 + s];
-      }
-    }
-
-    // ======================================================================
-    // MODE 0: POSITION + VELOCITY STAGE  (mj_step1)
-    // ======================================================================
-    if constexpr (MODE != 1) {
     // (the link's own spatial inertia is formed twice from the link frame in LDS -- here for the composite
     // inertias, and again after the collision phase for the bias forces -- with the same arithmetic, hence the
     // same bits: ten doubles carried across the collision phase instead were spilled inside its loops)
@@ -1739,13 +724,7 @@ __device__ __forceinline__ void rp_stage_body(const RpModel<T>& M, const RpState
     // (ROUND 5: the window walk in every build.  The split stage's front part has no narrow phase to share registers
     // with (160 VGPRs, no scratch) and takes the walk's 17 k cycles per mj_step; and since both ways of running the stage
     // must emit the same candidates in the same ORDER to stay bit-identical, the one-kernel hull builds follow (round 4
-    // measured them 0.6 % slower with it).  RPK_MESH_KEYLANES = the old loop, for experiments.)
-#ifdef RPK_MESH_KEYLANES
-    constexpr bool KEYLANES = MESH != 0;
-#else
-    constexpr bool KEYLANES = false;
-#endif
-    unsigned long long remK0 = 0, remK1 = 0;   // hull builds: the capsules near this lane's two keys
+    // measured them 0.6 % slower with it).)
     {
       // extents along world x, y, z of MY geom: a capsule's own axis-aligned extents |axis| * half length +
       // radius, the oriented box's for boxes (a palm box hovering over the keyboard is no candidate), the
@@ -1766,43 +745,6 @@ __device__ __forceinline__ void rp_stage_body(const RpModel<T>& M, const RpState
         }
       }
       const bool near_me = nk > 0 && gkc && (fcz - gez <= (float)M.key_zmax);
-      if constexpr (KEYLANES) {
-        unsigned long long near_mask = __ballot(near_me);
-        float kx[2], kz[2], kpx[2], kpy[2], ktop[2], khx_[2], khy_[2], krb_[2];
-#pragma unroll
-        for (int s = 0; s < 2; s++) {
-          // key box centre = anchor + R_y(q) (hx,0,0)
-          kx[s] = (float)(kpos[s][0] - khalf[s][0] + khalf[s][0] * kcos[s]);
-          kz[s] = (float)(kpos[s][2] - khalf[s][0] * ksin[s]);
-          kpx[s] = (float)kpos[s][0]; kpy[s] = (float)kpos[s][1];
-          ktop[s] = (float)(kpos[s][2] + khalf[s][2]) + 0.01f;
-          khx_[s] = (float)khalf[s][0] + 0.01f; khy_[s] = (float)khalf[s][1];
-          krb_[s] = (float)krb[s] * 1.0001f + 1e-6f;
-        }
-        // two near geoms per trip (their broadcasts and tests interleave)
-        while (near_mask) {
-          const int g0 = __ffsll((long long)near_mask) - 1;
-          near_mask &= near_mask - 1;
-          const bool two = near_mask != 0ull;
-          const int g1 = two ? __ffsll((long long)near_mask) - 1 : g0;
-          near_mask &= near_mask - 1;   // (0 & -1 = 0)
-#pragma unroll
-          for (int u = 0; u < 2; u++) {
-            const int g = u == 0 ? g0 : g1;
-            const float cx = bcast(fcx, g), cy = bcast(fcy, g), cz = bcast(fcz, g), rb = bcast(frb, g);
-            const float ex_ = bcast(gex, g), ey_ = bcast(gey, g), ez_ = bcast(gez, g);
-#pragma unroll
-            for (int s = 0; s < 2; s++) {
-              const float dx = kx[s] - cx, dy = kpy[s] - cy, dz = kz[s] - cz, rr = rb + krb_[s];
-              // bounding spheres, then a conservative box test (the key only rotates about
-              // y, so its y-extent is exact; x/z get a 1 cm allowance)
-              const bool hit = (u == 0 || two) && isk[s] && dx * dx + dy * dy + dz * dz <= rr * rr && fabsf(dy) <= khy_[s] + ey_ &&
-                               fabsf(cx - kpx[s]) <= khx_[s] + ex_ && cz - ez_ <= ktop[s];
-              if (s == 0) remK0 |= hit ? (1ull << g) : 0ull; else remK1 |= hit ? (1ull << g) : 0ull;
-            }
-          }
-        }
-      } else {
       float kx[2], kz[2], kpy[2], khy_[2];
 #pragma unroll
       for (int s = 0; s < 2; s++) {
@@ -1855,12 +797,11 @@ __device__ __forceinline__ void rp_stage_body(const RpModel<T>& M, const RpState
         kcount += __popcll(hm);
       }
       if (kcount > RPK_KLIST) { warn |= 16; kcount = RPK_KLIST; }   // (RP_WARN_WORK_FULL: more geom-key candidates than the list holds)
-      }
     }
     PROF(12);
 #ifndef RPK_MARK
     if (S.prof && env == 0) {
-      int ca = (int)wave_sum((float)__popcll(remA)), ck = KEYLANES ? (int)wave_sum((float)(__popcll(remK0) + __popcll(remK1))) : kcount;
+      int ca = (int)wave_sum((float)__popcll(remA)), ck = kcount;
       if (lane == 0) { sm.prof[28] += ca; sm.prof[29] += ck; }
     }
 #endif
@@ -1872,7 +813,7 @@ __device__ __forceinline__ void rp_stage_body(const RpModel<T>& M, const RpState
       // narrow phase below is the register-hungriest part of this kernel, and in one loop with it the
       // allocator spilled the drain loop's own variables -- every round then paid scratch round trips
       // (measured: 34 k cycles per mj_step in the capsule builds, 163 k in the hull builds)
-      while (gen_phase < (KEYLANES ? 3 : 2) && (PART == 1 || nwork < 64)) {
+      while (gen_phase < 2 && (PART == 1 || nwork < 64)) {
       // ---- one drain round: every lane contributes at most one candidate
       {
         // Geom-geom candidates are COMPACTED first: the sphere-overlap hits sit unevenly in the lanes (a palm box
@@ -1902,8 +843,7 @@ __device__ __forceinline__ void rp_stage_body(const RpModel<T>& M, const RpState
           lpos = 0;
           WSYNC();
         }
-        const unsigned long long rem = gen_phase == 1 ? remK0 : remK1;   // (hull builds)
-        bool has = gen_phase == 0 ? lpos + lane < lcount : (KEYLANES ? rem != 0ull : kpos_ + lane < kcount);
+        bool has = gen_phase == 0 ? lpos + lane < lcount : kpos_ + lane < kcount;
 #ifndef RPK_MARK
         if (S.prof && env == 0 && lane == 0) sm.prof[26] += 1;   // (diagnostic: drain rounds)
 #endif
@@ -1915,11 +855,6 @@ __device__ __forceinline__ void rp_stage_body(const RpModel<T>& M, const RpState
             const int item = has ? (int)sm.glist[lpos + lane] : 0;
             a = item >> 6; bit = item & 63;
             lpos += 64;
-          } else if constexpr (KEYLANES) {
-            bit = has ? __ffsll((long long)rem) - 1 : 0;
-            const unsigned long long rest = rem & (rem - 1);
-            if (gen_phase == 1) remK0 = rest; else remK1 = rest;
-            a = gen_phase == 1 ? kid[0] : kid[1];   // (key, geom)
           } else {
             const int item = has ? (int)sm.klist[kpos_ + lane] : 0;
             a = item & 127; bit = item >> 7;   // (key, geom)
@@ -2535,7 +1470,7 @@ __device__ __forceinline__ void rp_stage_body(const RpModel<T>& M, const RpState
     // The position / velocity stages are register-bound around the narrow phase: the state is re-read here
     // (L2 hits) instead of being carried -- that is: spilled to scratch and reloaded -- across the collision.
     // (PB: the back part's collection loop is no collision phase -- the prologue's values are carried, two dependent trips less)
-    if constexpr (MODE != 1 && !PB) {
+    if constexpr (!PB) {
       {
         const int4* rec = (const int4*)(fresh(M.lane_topo()) + 16 * L);
         const int4 r0 = rec[0], r1 = rec[1], r2 = rec[2];
@@ -2739,11 +1674,11 @@ __device__ __forceinline__ void rp_stage_body(const RpModel<T>& M, const RpState
       }
       const int nent = wave_max(lane < ncon ? base + cnt : 0), maxm = wave_max(cnt);
       if constexpr (MODE == 0) {
-        LI(10) = base | (cnt << 12);
+        LI(LI_ENT_RANGE) = base | (cnt << 12);
         if (lane == 0) {
-          B.hdr[env * 8 + 4] = nent; B.hdr[env * 8 + 5] = maxm;
+          B.hdr[env * HDR_N + HDR_NENT] = nent; B.hdr[env * HDR_N + HDR_MAXM] = maxm;
           // capacity class of this env's solve (rp_solver2.hpp): light = fits the lean solver stage
-          B.hdr[env * 8 + 6] = (S.lean && MD == RPK_MAXD && M.ntree <= 2 && ncon <= LeanCaps::NC && nent <= ((S.lean & RPK_LEAN_CAP) > 1 && (S.lean & RPK_LEAN_CAP) < LeanCaps::NE ? (S.lean & RPK_LEAN_CAP) : LeanCaps::NE) &&
+          B.hdr[env * HDR_N + HDR_CLASS] = (S.lean && MD == RPK_MAXD && M.ntree <= 2 && ncon <= LeanCaps::NC && nent <= ((S.lean & RPK_LEAN_CAP) > 1 && (S.lean & RPK_LEAN_CAP) < LeanCaps::NE ? (S.lean & RPK_LEAN_CAP) : LeanCaps::NE) &&
                                 __popcll(dirty_mask) <= LeanCaps::HMAX && nkt <= LeanCaps::NK && nl + nkt <= 64) ? 1 : 0;
         }
       }
@@ -2829,22 +1764,20 @@ __device__ __forceinline__ void rp_stage_body(const RpModel<T>& M, const RpState
       v_mass = M.link_mass()[L]; v_gscale = M.link_gscale()[L];
       __builtin_amdgcn_sched_barrier(0);
     }
-    if constexpr (MODE != 1) {
-      // the motion axis about the tree reference point again, from the link frames in LDS (same arithmetic
-      // as in mj_comPos above: same bits), instead of six more registers carried across the collision
-      if (isl) {
-        const T* p_tref = fresh(M.tree_ref());
-        const T axw[3] = {sm.xaxis[lane][0], sm.xaxis[lane][1], sm.xaxis[lane][2]};
-        if (jtype == JNT_SLIDE_) {
-          cdofr[0] = cdofr[1] = cdofr[2] = 0;
-          cdofr[3] = axw[0]; cdofr[4] = axw[1]; cdofr[5] = axw[2];
-        } else {
-          T off[3];
+    // the motion axis about the tree reference point again, from the link frames in LDS (same arithmetic
+    // as in mj_comPos above: same bits), instead of six more registers carried across the collision
+    if (isl) {
+      const T* p_tref = fresh(M.tree_ref());
+      const T axw[3] = {sm.xaxis[lane][0], sm.xaxis[lane][1], sm.xaxis[lane][2]};
+      if (jtype == JNT_SLIDE_) {
+        cdofr[0] = cdofr[1] = cdofr[2] = 0;
+        cdofr[3] = axw[0]; cdofr[4] = axw[1]; cdofr[5] = axw[2];
+      } else {
+        T off[3];
 #pragma unroll
-          for (int k = 0; k < 3; k++) off[k] = (PB ? v_tref[k] : p_tref[3 * ltree + k]) - sm.xanchor[lane][k];
-          cdofr[0] = axw[0]; cdofr[1] = axw[1]; cdofr[2] = axw[2];
-          cross3(cdofr + 3, axw, off);
-        }
+        for (int k = 0; k < 3; k++) off[k] = (PB ? v_tref[k] : p_tref[3 * ltree + k]) - sm.xanchor[lane][k];
+        cdofr[0] = axw[0]; cdofr[1] = axw[1]; cdofr[2] = axw[2];
+        cross3(cdofr + 3, axw, off);
       }
     }
     T cv[6] = {0, 0, 0, 0, 0, 0}, cdd[6] = {0, 0, 0, 0, 0, 0};
@@ -2983,35 +1916,35 @@ __device__ __forceinline__ void rp_stage_body(const RpModel<T>& M, const RpState
     }
     // ---- hand over to the solver kernel
     if constexpr (MODE == 0) {
-      LF(0) = qbias;
-      if (lane < nu) { LF(1) = alen; LF(2) = avel; }
-      LF(3) = ksin[0]; LF(5) = kcos[0];
-      if (isk[1]) { LF(4) = ksin[1]; LF(6) = kcos[1]; }
-      LF(7) = fr_aref;
+      LF(LF_QBIAS) = qbias;
+      if (lane < nu) { LF(LF_ALEN) = alen; LF(LF_AVEL) = avel; }
+      LF(LF_KSIN) = ksin[0]; LF(LF_KCOS) = kcos[0];
+      if (isk[1]) { LF(LF_KSIN + 1) = ksin[1]; LF(LF_KCOS + 1) = kcos[1]; }
+      LF(LF_FR_AREF) = fr_aref;
 #pragma unroll
-      for (int k = 0; k < 3; k++) if (lim_sign[k] != 0) { LF(8 + k) = lim_D[k]; LF(11 + k) = lim_aref[k]; }
+      for (int k = 0; k < 3; k++) if (lim_sign[k] != 0) { LF(LF_LIM_D + k) = lim_D[k]; LF(LF_LIM_AREF + k) = lim_aref[k]; }
       if (lane < ncon) {  // (the solver stage reads these for lanes < ncon only)
-        LF(14) = con_D; LF(15) = con_mu;
+        LF(LF_CON_D) = con_D; LF(LF_CON_MU) = con_mu;
 #pragma unroll
-        for (int k = 0; k < 3; k++) { LF(16 + k) = con_n[k]; LF(19 + k) = con_t1[k]; LF(22 + k) = con_t2[k]; }
+        for (int k = 0; k < 3; k++) { LF(LF_CON_N + k) = con_n[k]; LF(LF_CON_T1 + k) = con_t1[k]; LF(LF_CON_T2 + k) = con_t2[k]; }
 #pragma unroll
-        for (int k = 0; k < 4; k++) LF(25 + k) = con_aref[k];
-        LI(1) = con_A; LI(2) = con_B; LI(3) = con_slot; LI(4) = con_cross;
-        LI(5) = (int)(con_maskA & 0xffffffffu); LI(6) = (int)(con_maskA >> 32);
-        LI(7) = (int)(con_maskB & 0xffffffffu); LI(8) = (int)(con_maskB >> 32);
+        for (int k = 0; k < 4; k++) LF(LF_CON_AREF + k) = con_aref[k];
+        LI(LI_CON_A) = con_A; LI(LI_CON_B) = con_B; LI(LI_CON_SLOT) = con_slot; LI(LI_CON_CROSS) = con_cross;
+        LI(LI_MASKA_LO) = (int)(con_maskA & 0xffffffffu); LI(LI_MASKA_HI) = (int)(con_maskA >> 32);
+        LI(LI_MASKB_LO) = (int)(con_maskB & 0xffffffffu); LI(LI_MASKB_HI) = (int)(con_maskB >> 32);
       }
-      LI(0) = (lim_sign[0] + 1) | ((lim_sign[1] + 1) << 2) | ((lim_sign[2] + 1) << 4);
-      LI(9) = sdepth;
-      LI(11) = salink | (sTL << 8) | (sTB << 16);
+      LI(LI_LIM_SIGN) = (lim_sign[0] + 1) | ((lim_sign[1] + 1) << 2) | ((lim_sign[2] + 1) << 4);
+      LI(LI_SDEPTH) = sdepth;
+      LI(LI_SLOT_ANCHOR) = salink | (sTL << 8) | (sTB << 16);
       if (lane < 16) {
-        int* sl = B.slots + (size_t)env * 64;
-        sl[lane] = sm.slotkey[lane]; sl[16 + lane] = sm.slotlink[lane];
-        sl[32 + lane] = (int)(sm.slotmask[lane] & 0xffffffffu); sl[48 + lane] = (int)(sm.slotmask[lane] >> 32);
+        int* sl = B.slots + (size_t)env * SLOT_N;
+        sl[SLOT_KEY + lane] = sm.slotkey[lane]; sl[SLOT_LINK + lane] = sm.slotlink[lane];
+        sl[SLOT_MASK_LO + lane] = (int)(sm.slotmask[lane] & 0xffffffffu); sl[SLOT_MASK_HI + lane] = (int)(sm.slotmask[lane] >> 32);
       }
       if (lane < RPK_NKEYS / 4) B.keyslot[(size_t)env * (RPK_NKEYS / 4) + lane] = ((int*)sm.keyslot)[lane];
       if (lane == 0) {
-        B.hdr[env * 8] = ncon; B.hdr[env * 8 + 1] = nkt;
-        B.hdr[env * 8 + 2] = (int)(dirty_mask & 0xffffffffu); B.hdr[env * 8 + 3] = (int)(dirty_mask >> 32);
+        B.hdr[env * HDR_N + HDR_NCON] = ncon; B.hdr[env * HDR_N + HDR_NKT] = nkt;
+        B.hdr[env * HDR_N + HDR_DIRTY_LO] = (int)(dirty_mask & 0xffffffffu); B.hdr[env * HDR_N + HDR_DIRTY_HI] = (int)(dirty_mask >> 32);
       }
     }
 
@@ -3134,7 +2067,6 @@ __device__ __forceinline__ void rp_stage_body(const RpModel<T>& M, const RpState
       if (lane < M.nsite && S.sens_touch) S.sens_touch[(size_t)env * M.nsite + lane] = sm.touch[lane];
     }
     }  // PART != 1
-    }  // MODE 0
   }
 
   PROF(17);
@@ -3168,10 +2100,6 @@ __device__ __forceinline__ void rp_stage_body(const RpModel<T>& M, const RpState
     if (lane == 0) {
       S.warn[env] |= w;
       if constexpr (MODE == 0 && PART != 1) { if (!(S.stale_outputs && substep == nsub - 1)) S.ncon[env] = ncon; }
-      if constexpr (MODE == 1) {
-        S.solver_iter[env] = (niter_last & 255) | ((__popcll(dirty_mask) & 255) << 8) | ((nkt & 255) << 16);
-        S.time[env] = time;
-      }
     }
   }
   if (S.prof && env == 0 && lane < RPK_NPROF_STAGE) {
@@ -3179,15 +2107,25 @@ __device__ __forceinline__ void rp_stage_body(const RpModel<T>& M, const RpState
     atomicAdd((unsigned long long*)&S.prof[lane], (unsigned long long)sm.prof[lane]);
   }
   if constexpr (MODE != 2) {
-    int* cost = MODE == 0 ? S.cost_pos : S.cost_sol;
-    if (cost && lane == 0) cost[env] = (int)(((long long)__builtin_readcyclecounter() - kernel_t0) >> 8);
+    if (S.cost_pos && lane == 0) S.cost_pos[env] = (int)(((long long)__builtin_readcyclecounter() - kernel_t0) >> 8);
   }
-#undef LF
-#undef LI
 }
 
+// "The list's last reader clears it": every workgroup that walked RpState::heavy_list (n entries) reports in; the last
+// one records the longest list seen and clears the list's counters for the next substep.  (Thread 0 of each workgroup.)
+template <typename T>
+__device__ __forceinline__ void rp_heavy_list_done(const RpState<T>& S, const int n) {
+  __threadfence();
+  if (atomicAdd(S.heavy_done, 1) == (int)gridDim.x - 1) {
+    if (S.heavy_peak && n > *S.heavy_peak) *S.heavy_peak = n;
+    *S.heavy_cnt = 0; *S.heavy_done = 0; __threadfence();
+  }
+}
+
+// One kernel per stage: MODE 0 / 2 the position / sensor stage, MODE 1 the full-capacity solver stage (FIXED_TL: see
+// rp_full_solver_body; MESH: the position stage's narrow-phase build).
 template <typename T, int MODE, int FIXED_TL = 0, int MD = RPK_MAXD, int MESH = 0>
-__global__ __launch_bounds__(64, (MODE != 1 || sizeof(T) == 4) ? 2 : RPK_SOL64_WAVES) void rp_stage_kernel(RpModel<T> M, RpState<T> S, RpStage<T> B, int substep,
+__global__ __launch_bounds__(64, (MODE != 1 || sizeof(T) == 4) ? 2 : 1) void rp_stage_kernel(RpModel<T> M, RpState<T> S, RpStage<T> B, int substep,
                                                      int nsub) {
   // One env per workgroup -- or, for the full-capacity solver stage next to the lean one, a small grid walking
   // the compacted list of the envs outside the light class (RpState::heavy_list).
@@ -3195,20 +2133,15 @@ __global__ __launch_bounds__(64, (MODE != 1 || sizeof(T) == 4) ? 2 : RPK_SOL64_W
   const int n = listed ? *(volatile const int*)S.heavy_cnt : (int)gridDim.x;
   for (int i = blockIdx.x; i < n; i += gridDim.x) {
     const int env = listed ? S.heavy_list[i] : (S.order ? S.order[S.env_base + i] : S.env_base + i);
-    rp_stage_body<T, MODE, FIXED_TL, MD, MESH, false>(M, S, B, substep, nsub, env, nullptr, (int)threadIdx.x);
+    if constexpr (MODE == 1) rp_full_solver_body<T, FIXED_TL, MD, false>(M, S, B, env, nullptr, (int)threadIdx.x);
+    else rp_position_body<T, MODE, MD, MESH, false>(M, S, B, substep, nsub, env, nullptr, (int)threadIdx.x);
     if (!listed) break;
     __syncthreads();
   }
   if constexpr (MODE == 1) {
     // (the list's last reader clears it: this stage, or the position stage that follows it on the same stream,
     // rp_pos_list_kernel)
-    if (listed && !S.heavy_keep && threadIdx.x == 0) {
-      __threadfence();
-      if (atomicAdd(S.heavy_done, 1) == (int)gridDim.x - 1) {
-        if (S.heavy_peak && n > *S.heavy_peak) *S.heavy_peak = n;
-        *S.heavy_cnt = 0; *S.heavy_done = 0; __threadfence();
-      }
-    }
+    if (listed && !S.heavy_keep && threadIdx.x == 0) rp_heavy_list_done(S, n);
   }
 }
 
@@ -3218,13 +2151,13 @@ __global__ __launch_bounds__(64, (MODE != 1 || sizeof(T) == 4) ? 2 : RPK_SOL64_W
 template <typename T, int MESH>
 __global__ __launch_bounds__(64, 2) void rp_pos_front_kernel(RpModel<T> M, RpState<T> S, RpStage<T> B, int substep, int nsub) {
   const int env = S.order ? S.order[S.env_base + blockIdx.x] : S.env_base + (int)blockIdx.x;
-  rp_stage_body<T, 0, 0, RPK_MAXD, MESH, false, 1>(M, S, B, substep, nsub, env, nullptr, (int)threadIdx.x);
+  rp_position_body<T, 0, RPK_MAXD, MESH, false, 1>(M, S, B, substep, nsub, env, nullptr, (int)threadIdx.x);
 }
 template <typename T, int MESH>
 __global__ __launch_bounds__(64, 2) void rp_pos_back_kernel(RpModel<T> M, RpState<T> S, RpStage<T> B, int substep, int nsub) {
   if (blockIdx.x == 0 && threadIdx.x < RPK_NSTRIPE * RPK_NTYPE_PAD) B.tcount[B.tcount_off + threadIdx.x] = 0;
   const int env = S.order ? S.order[S.env_base + blockIdx.x] : S.env_base + (int)blockIdx.x;
-  rp_stage_body<T, 0, 0, RPK_MAXD, MESH, false, 2>(M, S, B, substep, nsub, env, nullptr, (int)threadIdx.x);
+  rp_position_body<T, 0, RPK_MAXD, MESH, false, 2>(M, S, B, substep, nsub, env, nullptr, (int)threadIdx.x);
 }
 
 // The position / velocity stage of the envs on the compacted list (the envs outside the light class), on the companion
@@ -3237,16 +2170,10 @@ __global__ __launch_bounds__(64, 2) void rp_pos_list_kernel(RpModel<T> M, RpStat
   for (int i = blockIdx.x; i < n; i += gridDim.x) {
     int lane = (int)threadIdx.x;
     asm volatile("" : "+v"(lane));
-    rp_stage_body<T, 0, 0, RPK_MAXD, MESH, false>(M, S, B, substep, nsub, S.heavy_list[i], nullptr, lane);
+    rp_position_body<T, 0, RPK_MAXD, MESH, false>(M, S, B, substep, nsub, S.heavy_list[i], nullptr, lane);
     __syncthreads();
   }
-  if (threadIdx.x == 0) {
-    __threadfence();
-    if (atomicAdd(S.heavy_done, 1) == (int)gridDim.x - 1) {
-      if (S.heavy_peak && n > *S.heavy_peak) *S.heavy_peak = n;
-      *S.heavy_cnt = 0; *S.heavy_done = 0; __threadfence();
-    }
-  }
+  if (threadIdx.x == 0) rp_heavy_list_done(S, n);
 }
 
 // ============================================================================
@@ -3256,7 +2183,7 @@ __global__ __launch_bounds__(64, 2) void rp_pos_list_kernel(RpModel<T> M, RpStat
 // 256 registers: the fused kernel has the occupancy of either).  With one launch per stage, every launch ended
 // with most SIMDs waiting for the few heaviest envs (measured: 38 % of the wave slots idle over an rp_step);
 // over ten substeps an env's cost averages out, and nothing waits at a launch boundary any more.
-// An env that leaves the light capacity class at substep k stops there (hdr[7] = k, appended to the list);
+// An env that leaves the light capacity class at substep k stops there (hdr[HDR_RESUME] = k, appended to the list);
 // rp_cleanup_steps_kernel, launched right after, takes such envs through their remaining substeps with the
 // full-capacity solver stage.  The hand-over between the two stages is global memory written and read by the
 // same wave: a fence + L1 invalidate separates them.
@@ -3286,16 +2213,16 @@ __global__ __launch_bounds__(64, 2) void rp_fused_steps_kernel(RpModel<T> M, RpS
     // spilled registers)
     int lane = (int)threadIdx.x;
     asm volatile("" : "+v"(lane));
-    if (*(volatile const int*)&B.hdr[env * 8 + 6] != 1) {
+    if (*(volatile const int*)&B.hdr[env * rpk::HDR_N + rpk::HDR_CLASS] != 1) {
       // outside the light class from here on: the clean-up launch continues with substep k
-      if (threadIdx.x == 0) { B.hdr[env * 8 + 7] = k; S.heavy_list[atomicAdd(S.heavy_cnt, 1)] = env; }
+      if (threadIdx.x == 0) { B.hdr[env * rpk::HDR_N + rpk::HDR_RESUME] = k; S.heavy_list[atomicAdd(S.heavy_cnt, 1)] = env; }
       return;
     }
     if (S.qpos_prev && k == nsub - 1) rp_save_prev_state(M, S, env);
     rp_lean_solver_body<T, true>(M, S, B, env, smem, lane);
     RPK_STAGE_FENCE();
     asm volatile("" : "+v"(lane));
-    rp_stage_body<T, 0, 0, RPK_MAXD, MESH, true>(M, S, B, k, nsub, env, smem, lane);
+    rp_position_body<T, 0, RPK_MAXD, MESH, true>(M, S, B, k, nsub, env, smem, lane);
     RPK_STAGE_FENCE();
   }
 }
@@ -3317,15 +2244,15 @@ __global__ __launch_bounds__(64, 2) void rp_fused_split_kernel(RpModel<T> M, RpS
   for (int k = 0; k < nsub; k++) {
     int lane = (int)threadIdx.x;
     asm volatile("" : "+v"(lane));
-    if (*(volatile const int*)&B.hdr[env * 8 + 6] != 1) {
-      if (threadIdx.x == 0) { B.hdr[env * 8 + 7] = k; S.heavy_list[atomicAdd(S.heavy_cnt, 1)] = env; }
+    if (*(volatile const int*)&B.hdr[env * rpk::HDR_N + rpk::HDR_CLASS] != 1) {
+      if (threadIdx.x == 0) { B.hdr[env * rpk::HDR_N + rpk::HDR_RESUME] = k; S.heavy_list[atomicAdd(S.heavy_cnt, 1)] = env; }
       return;
     }
     if (S.qpos_prev && k == nsub - 1) rp_save_prev_state(M, S, env);
     rp_lean_solver_body<T, true>(M, S, B, env, smem, lane);
     RPK_STAGE_FENCE();
     asm volatile("" : "+v"(lane));
-    rp_stage_body<T, 0, 0, RPK_MAXD, MESH, true, 1>(M, S, B, k, nsub, env, smem, lane);
+    rp_position_body<T, 0, RPK_MAXD, MESH, true, 1>(M, S, B, k, nsub, env, smem, lane);
     RPK_STAGE_FENCE();
     asm volatile("" : "+v"(lane));
     {
@@ -3337,7 +2264,7 @@ __global__ __launch_bounds__(64, 2) void rp_fused_split_kernel(RpModel<T> M, RpS
     }
     RPK_STAGE_FENCE();
     asm volatile("" : "+v"(lane));
-    rp_stage_body<T, 0, 0, RPK_MAXD, MESH, true, 2>(M, S, B, k, nsub, env, smem, lane);
+    rp_position_body<T, 0, RPK_MAXD, MESH, true, 2>(M, S, B, k, nsub, env, smem, lane);
     RPK_STAGE_FENCE();
   }
 }
@@ -3353,25 +2280,19 @@ __global__ __launch_bounds__(64, 1) void rp_cleanup_steps_kernel(RpModel<T> M, R
   Sh.lean = 0; Sh.heavy_list = nullptr;
   for (int i = blockIdx.x; i < n; i += gridDim.x) {
     const int env = S.heavy_list[i];
-    for (int k = *(volatile const int*)&B.hdr[env * 8 + 7]; k < nsub; k++) {
+    for (int k = *(volatile const int*)&B.hdr[env * rpk::HDR_N + rpk::HDR_RESUME]; k < nsub; k++) {
       int lane = (int)threadIdx.x;
       asm volatile("" : "+v"(lane));
       if (S.qpos_prev && k == nsub - 1) rp_save_prev_state(M, S, env);
       // the same solver build per substep as the per-stage schedule picks (light again: the lean stage; FIXED_TL as
       // the host picks it there), so that both schedules produce the same bits
-      if (*(volatile const int*)&B.hdr[env * 8 + 6] == 1) rp_lean_solver_body<T, true>(M, S, B, env, smem, lane);
-      else rp_stage_body<T, 1, FIXED_TL, RPK_MAXD, 0, true>(M, Sh, B, k, nsub, env, smem, lane);
+      if (*(volatile const int*)&B.hdr[env * rpk::HDR_N + rpk::HDR_CLASS] == 1) rp_lean_solver_body<T, true>(M, S, B, env, smem, lane);
+      else rp_full_solver_body<T, FIXED_TL, RPK_MAXD, true>(M, Sh, B, env, smem, lane);
       RPK_STAGE_FENCE();
       asm volatile("" : "+v"(lane));
-      rp_stage_body<T, 0, 0, RPK_MAXD, MESH, true>(M, S, B, k, nsub, env, smem, lane);
+      rp_position_body<T, 0, RPK_MAXD, MESH, true>(M, S, B, k, nsub, env, smem, lane);
       RPK_STAGE_FENCE();
     }
   }
-  if (threadIdx.x == 0) {
-    __threadfence();
-    if (atomicAdd(S.heavy_done, 1) == (int)gridDim.x - 1) {
-      if (S.heavy_peak && n > *S.heavy_peak) *S.heavy_peak = n;
-      *S.heavy_cnt = 0; *S.heavy_done = 0; __threadfence();
-    }
-  }
+  if (threadIdx.x == 0) rp_heavy_list_done(S, n);
 }

@@ -1,4 +1,4 @@
-// rp_kernels.hpp — fixed-topology batched rigid-body step for RoboPianist on gfx950.
+// rp_model.hpp — fixed-topology batched rigid-body step for RoboPianist on gfx950.
 //
 // One environment per 64-lane wavefront (one workgroup = one wave).  Lane roles:
 //   lane i < nlink        : hand link i (= hand dof i; 2 trees x 26 links)
@@ -28,10 +28,10 @@
 #ifndef RPK_NE
 #define RPK_NE 640      // max contact Jacobian entries (contact, dof) handed to the solver (fp64; see RpCaps)
 #endif
-// Contact Jacobian entry records (RpStage::entM) and the per-contact entry range (lane field LI(10)):
-//   entM[.][0] = dof lane | contact << 6 | column of the dof in its row layout << 12 | cross-chain << 16
-//   entM[.][1] = first entry of the contact | entries of the contact << 12 | rank of this entry << 18
-//   LI(10)     = first entry | entries << 12
+// Contact Jacobian entry records (RpStage::entM) and the per-contact entry range (lane field rpk::LI_ENT_RANGE):
+//   entM[.][0]   = dof lane | contact << 6 | column of the dof in its row layout << 12 | cross-chain << 16
+//   entM[.][1]   = first entry of the contact | entries of the contact << 12 | rank of this entry << 18
+//   LI_ENT_RANGE = first entry | entries << 12
 #define RPK_EM0(lane_, con_, col_, cross_) ((lane_) | ((con_) << 6) | ((col_) << 12) | ((cross_) << 16))
 #define RPK_EM1(base_, cnt_, rank_) ((base_) | ((cnt_) << 12) | ((rank_) << 18))
 #define RPK_EM_LANE(m0_) ((m0_) & 63)
@@ -208,7 +208,7 @@ struct RpState {
   // solver stage -- the cost predictor of the ordered launch
   int *cost_pos, *cost_sol;
   // capacity classes of the solver stage: when set, the position stage marks every env whose constraint system
-  // fits rpk::LeanCaps as "light" (hdr[6] = 1); rp_lean_solver_kernel (two waves per SIMD) steps those and the
+  // fits rpk::LeanCaps as "light" (hdr[HDR_CLASS] = 1); rp_lean_solver_kernel (two waves per SIMD) steps those and the
   // full-capacity solver stage skips them.  (RPK_LEAN_CAP: the bits of the on / entry-cap value; RPK_LEAN_JOINT: the lean
   // stage keeps ONE dense block for the dirty rows of both hands, rp_solver2.hpp)
   int lean;
@@ -220,12 +220,12 @@ struct RpState {
   int *heavy_cnt, *heavy_done;   // entries in the list; finished workgroups (the last one clears both)
   int* heavy_peak;               // may be null: the longest list seen (the host sizes that stage's grid from it, one step late)
   // The position / velocity stage of a substep may run as two launches: the slice's launch skips the envs outside the
-  // light class (skip_heavy: hdr[6] of the substep just solved), a small grid on the companion stream walks the list
+  // light class (skip_heavy: hdr[HDR_CLASS] of the substep just solved), a small grid on the companion stream walks the list
   // right behind the full-capacity solver stage (which then leaves the list alone: heavy_keep) -- the light envs'
   // position stage no longer waits for the slowest heavy solve.
   int skip_heavy, heavy_keep;
   // (skip_heavy tests this snapshot -- 1 = rp_order_kernel put the env on the list of the substep just solved -- not
-  // hdr[6], which the list's own position stage rewrites on the companion stream while the slice's launch reads it)
+  // hdr[HDR_CLASS], which the list's own position stage rewrites on the companion stream while the slice's launch reads it)
   const unsigned char* listed;
   // dm_control's legacy_step = False (physics.step() = mj_step = mj_step1; mj_step2: position-dependent data is NOT
   // refreshed after the last integration): the position stage that follows the LAST substep's solve keeps its outputs
@@ -277,17 +277,133 @@ template <typename S_, bool EXT> __device__ __forceinline__ S_& rp_smem(void* ex
   } while (0)
 #endif
 
-// Hand-over between the position/velocity kernel (MODE 0) and the solver kernel
-// (MODE 1): everything `mj_step1` leaves behind for `mj_step2`, per env.  Lives in
+namespace rpk {
+// ----------------------------------------------------------------- shared memory
+// LDS budget drives occupancy (fp64: 40.5 KB -> 4 workgroups per CU).  Scratch of the
+// position/velocity stage and scratch of the solver are never live together, so they
+// share storage; only what crosses from one stage into the other is persistent.
+template <typename T>
+struct SmemShared {  // used by both stages
+  union {
+    T vec[2][RPK_WAVE];
+    short work[RPK_WORK][2];  // position stage, collision only: candidate pairs
+  };
+  unsigned long long slotmask[16];
+  short slotkey[16];
+  short slotlink[16];
+  signed char keyslot[RPK_NKEYS];
+  unsigned prof[RPK_NPROF_STAGE];   // per-launch phase cycle counts of env 0 (debug aid)
+};
+template <typename T, int MODE, int MD = RPK_MAXD> struct Smem;
+
+// rows owned by one lane: friction-loss row of its hand dof, one limit row per dof
+// slot (hand, key, key+64), four pyramidal rows of its contact.
+template <typename T> struct Rows { T fr, lim[3], con[4]; };
+}  // namespace rpk
+
+// The lane constants of a stage body, decoded from its topology record `tp` and the key tables' raw reads `kdof_raw` /
+// `kact_raw` (the body requests them in ONE batch with whatever else its prologue reads, then expands this).
+#define RPK_LANE_CONSTANTS \
+  /* (not const: the position stage re-reads the record after the collision phase instead of carrying */ \
+  /* fourteen integers through it -- it is register-bound there) */ \
+  int parent = isl ? tp[0] : -1; \
+  int depth = isl ? tp[1] : -1; \
+  int jtype = isl ? tp[2] : 0; \
+  int sibrank = isl ? tp[3] : 0; \
+  int ltree = isl ? tp[4] : 0; \
+  int ldof = isl ? tp[5] : 0; \
+  /* chain structure (lanes are in preorder: trunk chain, then up to 5 leaf chains) */ \
+  int tbase = isl ? tp[6] : 0, TL = isl ? tp[7] : 0; \
+  int ndesc = isl ? tp[8] : 0; \
+  /* chain lanes: first depth past the end of my chain / chain index; bit c of chainmask: */ \
+  /* leaf chain c of my tree exists */ \
+  const int chain_end = isl ? tp[11] : 0, mychain = isl ? tp[12] : 0, chainmask = isl ? tp[13] : 0; \
+  /* lane of my ancestor at depth e (e <= depth) */ \
+  auto anc_at = [&](int e) -> int { return e < TL ? tbase + e : lane - (depth - e); }; \
+  int llimited = isl ? tp[9] : 0; \
+  int lact = isl ? tp[10] : -1; \
+  const T lactcoef = isl ? M.link_act_coef()[L] : (T)0; \
+  int hasdof[3]; \
+  hasdof[0] = isl && llimited; hasdof[1] = lane < nk; hasdof[2] = lane + 64 < nk; \
+  const bool isk[2] = {lane < nk, lane + 64 < nk}; \
+  const int kid[2] = {lane, lane + 64}; \
+  int kdof[2], kact[2]; \
+  _Pragma("unroll") \
+  for (int s = 0; s < 2; s++) { \
+    kdof[s] = isk[s] ? kdof_raw[s] : 0; \
+    kact[s] = isk[s] ? kact_raw[s] : -1; \
+  }
+
+// Hand-over between the position/velocity stage (rp_position_body) and the solver stages
+// (rp_lean_solver_body, rp_full_solver_body): everything `mj_step1` leaves behind for `mj_step2`, per env.  Lives in
 // HBM but is L2 / Infinity-Cache resident (<= 25 KB per env).
 #define RPK_NLF 29  // per-lane float fields
 #define RPK_NLI 12  // per-lane int fields
+// The layout of the hand-over record: the ONE definition every writer and reader goes by (the position stage writes it;
+// both solver stages, rp_order_kernel and the fused / clean-up kernels read it).
+namespace rpk {
+enum : int {
+  // ---- RpStage::hdr[env * HDR_N + .], one record per env
+  HDR_NCON = 0,       // contacts
+  HDR_NKT = 1,        // touched keys (= solver slots in use)
+  HDR_DIRTY_LO = 2,   // rows that need the dense block, lanes 0 .. 31
+  HDR_DIRTY_HI = 3,   // ... lanes 32 .. 63
+  HDR_NENT = 4,       // contact Jacobian entries
+  HDR_MAXM = 5,       // most entries of one contact
+  HDR_CLASS = 6,      // capacity class of the env's solve: 1 = light (fits rpk::LeanCaps), 0 = full capacity
+  HDR_RESUME = 7,     // fused substeps: the substep at which the env left the light class (the clean-up kernel resumes there)
+  HDR_N = 8,
+  // ---- RpStage::lanef[env][.][lane]
+  LF_QBIAS = 0,       // link lanes: bias force of the lane's dof
+  LF_ALEN = 1,        // actuator lanes (lane < nu): actuator length
+  LF_AVEL = 2,        // ... and velocity
+  LF_KSIN = 3,        // [2] sine of the angle of key `lane`, key `lane + 64`
+  LF_KCOS = 5,        // [2] ... and cosine
+  LF_FR_AREF = 7,     // friction-loss row: reference acceleration
+  LF_LIM_D = 8,       // [3] limit rows (hand dof, key, key + 64; written where the row is active): D
+  LF_LIM_AREF = 11,   // [3] ... reference acceleration
+  LF_CON_D = 14,      // contact lanes (lane < ncon), from here to the end: D of the contact's rows
+  LF_CON_MU = 15,     // friction coefficient
+  LF_CON_N = 16,      // [3] contact frame: normal
+  LF_CON_T1 = 19,     // [3] ... first tangent
+  LF_CON_T2 = 22,     // [3] ... second tangent
+  LF_CON_AREF = 25,   // [4] reference accelerations of the four pyramidal rows
+  LF_END = 29,
+  // ---- RpStage::lanei[env][.][lane]
+  LI_LIM_SIGN = 0,    // limit rows: (sign + 1) of the hand dof's row | of key `lane`'s << 2 | of key `lane + 64`'s << 4
+  LI_CON_A = 1,       // contact lanes, .. LI_MASKB_HI: link of side A
+  LI_CON_B = 2,       // link of side B, or RPK_KEYBASE + key
+  LI_CON_SLOT = 3,    // solver slot of the key of side B (-1: none)
+  LI_CON_CROSS = 4,   // 1: the contact couples two chains (its rows go through the dense block)
+  LI_MASKA_LO = 5,    // links on the root path of side A, lanes 0 .. 31
+  LI_MASKA_HI = 6,    // ... lanes 32 .. 63
+  LI_MASKB_LO = 7,    // the same for side B
+  LI_MASKB_HI = 8,
+  LI_SDEPTH = 9,      // solver-slot lanes (nlink + s): depth of the anchor link of the slot's key
+  LI_ENT_RANGE = 10,  // contact lanes: first Jacobian entry of the contact | its entries << 12 (RPK_EM_BASE / RPK_EM_CNT read both)
+  LI_SLOT_ANCHOR = 11,  // solver-slot lanes: anchor link | its trunk length << 8 | its trunk base lane << 16
+  LI_END = 12,
+  // ---- RpStage::slots[env * SLOT_N + .]: four sections of 16, one entry per solver slot
+  SLOT_KEY = 0,       // key of the slot
+  SLOT_LINK = 16,     // anchor link of that key
+  SLOT_MASK_LO = 32,  // links on the anchor's root path, lanes 0 .. 31
+  SLOT_MASK_HI = 48,  // ... lanes 32 .. 63
+  SLOT_N = 64,
+};
+static_assert(LF_CON_AREF + 4 == LF_END && LF_END == RPK_NLF, "lanef layout");
+static_assert(LI_SLOT_ANCHOR + 1 == LI_END && LI_END == RPK_NLI, "lanei layout");
+static_assert(SLOT_MASK_HI + 16 == SLOT_N, "slots layout");
+}  // namespace rpk
+// field i of this lane in the hand-over of `env` (a body that uses them defines
+//   const size_t lf = (size_t)env * RPK_NLF * 64 + lane, li = (size_t)env * RPK_NLI * 64 + lane;)
+#define LF(i) B.lanef[lf + (size_t)(i) * 64]
+#define LI(i) B.lanei[li + (size_t)(i) * 64]
 template <typename T>
 struct RpStage {
   T* RM;      // [E][RPK_NLX(MD)][MD+1] mass-matrix rows (MD = RPK_MAXD or RPK_MAXD_DEEP, the build in use)
-  T* lanef;   // [E][RPK_NLF][64]
-  int* lanei; // [E][RPK_NLI][64]
-  int* hdr;   // [E][8]: ncon, nkt, dirty mask lo/hi, nent, max entries per contact, capacity class (1 = light)
+  T* lanef;   // [E][RPK_NLF][64]   rpk::LF_*
+  int* lanei; // [E][RPK_NLI][64]   rpk::LI_*
+  int* hdr;   // [E][8]             rpk::HDR_*
   T* entJ;    // [E][RpCaps<T>::NE][3]  contact Jacobian entries: d(contact point velocity)/d(qvel of one dof)
   int* entM;  // [E][RpCaps<T>::NE][2]  lane | contact<<6 | column<<11 | cross<<15 ; base | count<<8 | rank<<16
   int* slots; // [E][64]: slotkey[16], slotlink[16], slotmask lo[16], hi[16]

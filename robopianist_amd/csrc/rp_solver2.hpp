@@ -1,6 +1,6 @@
 // rp_solver2.hpp — the LEAN solver stage (mj_step2: actuation, Newton solve, Euler) for envs whose
-// constraint system fits the "light" capacity class.  Same arithmetic as rp_stage_kernel<T, 1>
-// (rp_kernels.hpp: that build keeps the full capacities and takes the other envs), restructured so that
+// constraint system fits the "light" capacity class.  Same arithmetic as rp_full_solver_body
+// (rp_solver_full.hpp: that build keeps the full capacities and takes the other envs), restructured so that
 // the per-lane state is half as large: <= 256 registers and <= 20 KB of LDS per env, i.e. two waves per
 // SIMD in fp64 (the full-capacity build needs all 512 registers and 40 KB).
 //
@@ -22,9 +22,6 @@
 //     key values cross through 16 slot-indexed cells instead of a 128-key table;
 //   * state that the Newton loop does not touch (qpos, qvel, applied forces) is re-read at the end.
 #pragma once
-#ifdef RP_LEAN_TRACE
-#include <cstdio>
-#endif
 #include "rp_model.hpp"
 #include "rp_wave.hpp"
 #include "rp_dense.hpp"
@@ -70,13 +67,12 @@ __device__ __forceinline__ void rp_lean_solver_body(const RpModel<T>& M, const R
   constexpr int MD = RPK_MAXD, TC = 4;
   // (the env's header in two wide scalar loads; everything the prologue reads from the hand-over is requested further down
   // in ONE batch before the first value is used: fetched where they were used, these were some twenty dependent trips to L2)
-  const int4 hq0 = *(const int4*)(B.hdr + (size_t)env * 8), hq1 = *(const int4*)(B.hdr + (size_t)env * 8 + 4);
+  const int4 hq0 = *(const int4*)(B.hdr + (size_t)env * HDR_N), hq1 = *(const int4*)(B.hdr + (size_t)env * HDR_N + 4);
+  static_assert(HDR_NCON == 0 && HDR_NKT == 1 && HDR_DIRTY_LO == 2 && HDR_DIRTY_HI == 3 && HDR_NENT == 4 && HDR_MAXM == 5 &&
+                HDR_CLASS == 6, "hq0 / hq1 are read by component: .x .y .z .w = header slots 0 .. 3 / 4 .. 7");
   if (S.active && S.active[env] == 0) return;
-  if (hq1.z != 1) return;   // not a light env: the full-capacity build takes it
+  if (hq1.z != 1) return;   // (HDR_CLASS) not a light env: the full-capacity build takes it
   SmemLean<T>& sm = rp_smem<SmemLean<T>, EXT>(ext);
-#ifdef RP_LEAN_TRACE
-  if (lane == 0) printf("lean kernel: env %d ncon %d\n", env, B.hdr[env * 8]);
-#endif
 #ifdef RPK_POISON_LDS  // debug build: nothing may depend on what a previous workgroup left in LDS
   {
     unsigned* w_ = reinterpret_cast<unsigned*>(&sm);
@@ -104,8 +100,6 @@ __device__ __forceinline__ void rp_lean_solver_body(const RpModel<T>& M, const R
   const bool isk[2] = {lane < nk, lane + 64 < nk};
   const int kid[2] = {lane, lane + 64};
   const size_t lf = (size_t)env * RPK_NLF * 64 + lane, li = (size_t)env * RPK_NLI * 64 + lane;
-#define LF(i) B.lanef[lf + (size_t)(i) * 64]
-#define LI(i) B.lanei[li + (size_t)(i) * 64]
   // ---- the prologue's reads: topology record, key tables, the hand-over's per-lane fields, the first round of entries
   const int4* rec = (const int4*)(M.lane_topo() + 16 * L);
   const int4 tr0 = rec[0], tr1 = rec[1], tr2 = rec[2], tr3 = rec[3];
@@ -116,14 +110,17 @@ __device__ __forceinline__ void rp_lean_solver_body(const RpModel<T>& M, const R
     kdof[s] = M.key_dof()[K]; kact[s] = M.key_act()[K];
     kslot_raw[s] = (int)((const signed char*)(B.keyslot + (size_t)env * (RPK_NKEYS / 4)))[K];
   }
-  int pli[12];
+  int pli[LI_END];   // (indexed by the hand-over's own names; the contact's two links are not needed here)
 #pragma unroll
-  for (int i = 0; i < 12; i++) pli[i] = (i == 1 || i == 2) ? 0 : LI(i);
-  T plf[17];   // LF(8 .. 10), LF(14 .. 15), LF(16 .. 24): limit / contact D, friction, contact frame
+  for (int i = 0; i < LI_END; i++) pli[i] = (i == LI_CON_A || i == LI_CON_B) ? 0 : LI(i);
+  // limit D, then the contact lanes' fields up to the reference accelerations (D, friction, contact frame): plf[PLF_LIM_D + k]
+  // = LF(LF_LIM_D + k), plf[PLF_CON + (name - LF_CON_D)] = LF(name)
+  constexpr int PLF_LIM_D = 0, PLF_CON = 3, PLF_NCON = LF_CON_AREF - LF_CON_D;
+  T plf[PLF_CON + PLF_NCON];
 #pragma unroll
-  for (int i = 0; i < 3; i++) plf[i] = LF(8 + i);
+  for (int i = 0; i < 3; i++) plf[PLF_LIM_D + i] = LF(LF_LIM_D + i);
 #pragma unroll
-  for (int i = 0; i < 11; i++) plf[3 + i] = LF(14 + i);
+  for (int i = 0; i < PLF_NCON; i++) plf[PLF_CON + i] = LF(LF_CON_D + i);
   // this lane's first contact Jacobian entry (the list has room for RpCaps::NE entries per env: reading past its end is
   // reading this env's own, unused, slots)
   T pej[3]; int pem[2];
@@ -204,7 +201,7 @@ __device__ __forceinline__ void rp_lean_solver_body(const RpModel<T>& M, const R
 #pragma unroll
     for (int e = 0; e <= MD; e++) Mr[e] = isl ? row[e] : (T)0;
   };
-  spk = (pli[0] & 63) << 22;
+  spk = (pli[LI_LIM_SIGN] & 63) << 22;
   auto lim_sign = [&](int s) -> int {
     int t = spk;
     asm volatile("" : "+v"(t));
@@ -212,28 +209,28 @@ __device__ __forceinline__ void rp_lean_solver_body(const RpModel<T>& M, const R
   };
   T lim_D[3] = {0, 0, 0};
 #pragma unroll
-  for (int k = 0; k < 3; k++) if (lim_sign(k) != 0) lim_D[k] = plf[k];
+  for (int k = 0; k < 3; k++) if (lim_sign(k) != 0) lim_D[k] = plf[PLF_LIM_D + k];
   T con_D = 0, con_mu = 0;
   int cinfo = 0;   // my contact: first entry | entries << 8 | cross-chain << 16
   if (lane < ncon) {
-    con_D = plf[3]; con_mu = plf[4];
+    con_D = plf[PLF_CON]; con_mu = plf[PLF_CON + LF_CON_MU - LF_CON_D];
     {
-      const int bc = pli[10];   // (hand-over layout: first entry | entries << 12; a light env's fit in 8 bits each)
-      cinfo = (bc & 255) | (((bc >> 12) & 63) << 8) | ((pli[4] & 1) << 16);
+      const int bc = pli[LI_ENT_RANGE];   // (hand-over layout: first entry | entries << 12; a light env's fit in 8 bits each)
+      cinfo = (bc & 255) | (((bc >> 12) & 63) << 8) | ((pli[LI_CON_CROSS] & 1) << 16);
       unsigned long long sup = 0;
       if ((bc >> 12) & 63) {   // (a contact dropped for capacity keeps no entries)
-        sup = (((unsigned long long)(unsigned)pli[6] << 32) | (unsigned)pli[5]) | (((unsigned long long)(unsigned)pli[8] << 32) | (unsigned)pli[7]);
-        const int slot = pli[3];
+        sup = (((unsigned long long)(unsigned)pli[LI_MASKA_HI] << 32) | (unsigned)pli[LI_MASKA_LO]) | (((unsigned long long)(unsigned)pli[LI_MASKB_HI] << 32) | (unsigned)pli[LI_MASKB_LO]);
+        const int slot = pli[LI_CON_SLOT];
         if (slot >= 0) sup |= 1ull << (nl + slot);
       }
       sm.csup[lane] = sup; sm.cinf[lane] = cinfo;
     }
     // contact frame -> LDS (rows of sm.R are free until the first assembly), only to rotate the entries
 #pragma unroll
-    for (int k = 0; k < 9; k++) sm.R[lane][k] = plf[5 + k];
+    for (int k = 0; k < 9; k++) sm.R[lane][k] = plf[PLF_CON + LF_CON_N - LF_CON_D + k];   // (normal, tangent 1, tangent 2: contiguous)
   }
   {
-    const int sl_ = pli[11], sd_ = pli[9];
+    const int sl_ = pli[LI_SLOT_ANCHOR], sd_ = pli[LI_SDEPTH];
     spk |= (sl_ & 255) | (((sl_ >> 8) & 15) << 8) | (((sl_ >> 16) & 63) << 12) | (((sd_ + 1) & 15) << 18);
   }
   struct SlotI { int salink, sTL, sTB, sdepth; };
@@ -262,9 +259,9 @@ __device__ __forceinline__ void rp_lean_solver_body(const RpModel<T>& M, const R
   };
   // which touched keys hang under me (bit s: the anchor chain of slot s passes through this link)
   {
-    const int* sl = B.slots + (size_t)env * 64;
+    const int* sl = B.slots + (size_t)env * SLOT_N;
     for (int s = 0; s < nkt; s++) {
-      const unsigned long long am = ((unsigned long long)(unsigned)sl[48 + s] << 32) | (unsigned)sl[32 + s];
+      const unsigned long long am = ((unsigned long long)(unsigned)sl[SLOT_MASK_HI + s] << 32) | (unsigned)sl[SLOT_MASK_LO + s];
       if (isl && ((am >> lane) & 1)) kpk |= 1 << (10 + s);
     }
   }
@@ -372,9 +369,9 @@ __device__ __forceinline__ void rp_lean_solver_body(const RpModel<T>& M, const R
 #pragma unroll
     for (int s = 0; s < 2; s++) s_qappk[s] = S.qfrc_applied[eo + kdof[s]];
   }
-  T hf[7];
+  T hf[LF_FR_AREF];   // (the hand-over's first fields, LF_QBIAS .. LF_KCOS + 1, under their own names)
 #pragma unroll
-  for (int i = 0; i < 7; i++) hf[i] = LF(i);
+  for (int i = 0; i < LF_FR_AREF; i++) hf[i] = LF(i);
   T Rr_s[MD + 1];   // (my mass-matrix row for the qacc_smooth solve that follows this phase)
   fetch_Mlocal(Rr_s);
   __builtin_amdgcn_sched_barrier(0);
@@ -394,7 +391,7 @@ __device__ __forceinline__ void rp_lean_solver_body(const RpModel<T>& M, const R
       ctrl = (lane < nu && a_climited) ? cl_ : ctrl;
     }
     if (isa) {
-      const T alen = hf[1], avel = hf[2];
+      const T alen = hf[LF_ALEN], avel = hf[LF_AVEL];
       T aforce = a_gain * ctrl + a_b0 + a_b1 * alen +
                  a_b2 * avel;
       if (a_flimited)
@@ -403,7 +400,7 @@ __device__ __forceinline__ void rp_lean_solver_body(const RpModel<T>& M, const R
       S.act_force[(size_t)env * nu + lane] = aforce;
     }
     WSYNC();
-    const T qbias = hf[0];
+    const T qbias = hf[LF_QBIAS];
     const T q0 = isl ? s_q0 : (T)0, qd0 = isl ? s_qd0 : (T)0;
     const T qapp0 = isl ? s_qapp0 : (T)0;
     const T lstiff = isl ? ld_stiff : (T)0, lsref = isl ? ld_sref : (T)0;
@@ -411,7 +408,7 @@ __device__ __forceinline__ void rp_lean_solver_body(const RpModel<T>& M, const R
     const T qact = (isl && lact >= 0) ? lactcoef * sm.vec[lact >= 0 ? lact : 0] : (T)0;
     const T qpas = -lstiff * (q0 - lsref) - (isl ? ld_damp : (T)0) * qd0;
     qfs[0] = isl ? (qpas - qbias + qapp0 + qact) : (T)0;
-    const T ksin[2] = {hf[3], isk[1] ? hf[4] : (T)0}, kcos[2] = {hf[5], isk[1] ? hf[6] : (T)1};
+    const T ksin[2] = {hf[LF_KSIN], isk[1] ? hf[LF_KSIN + 1] : (T)0}, kcos[2] = {hf[LF_KCOS], isk[1] ? hf[LF_KCOS + 1] : (T)1};
 #pragma unroll
     for (int s = 0; s < 2; s++) {
       const T kstiff = isk[s] ? kd_stiff[s] : (T)0, ksref = isk[s] ? kd_sref[s] : (T)0;
@@ -471,9 +468,6 @@ __device__ __forceinline__ void rp_lean_solver_body(const RpModel<T>& M, const R
     // (slot lanes: Rr[e], e <= sdepth = my row over the anchor link's path, `sdiag` my diagonal)
     const int shift = (isl && pos >= 0) ? TL - TC : 0;
     const int kd = pos >= 0 ? TC + pos : depth;     // my diagonal (link lanes)
-#ifdef RPK_X_NOTS   // compile-only experiment: register floor without the tree solve
-    return rhs * Rr[0] + (T)(nslots + (int)dm);
-#endif
     const bool isslot = !isl && lane < nl + nslots;
     const bool dirty = (dm >> lane) & 1;
     T mydinv = 0;   // reciprocal pivot of my (clean) row
@@ -964,8 +958,12 @@ __device__ __forceinline__ void rp_lean_solver_body(const RpModel<T>& M, const R
   int anyrow = (isl && lfloss > 0) || lim_sign(0) || lim_sign(1) || lim_sign(2) || hascon;
   anyrow = __ballot(anyrow) != 0ull;
   int niter_last = 0;
-  // park qfrc_smooth (the hand-over slots it was built from are dead) and qacc_smooth
-  LF(0) = qfs[0]; LF(3) = qfs[1]; LF(4) = qfs[2];
+  // park qfrc_smooth (the hand-over slots it was built from are dead) and qacc_smooth.
+  // The parking slots overlay three fields of the hand-over.  That is safe: this lane has consumed them (hf[] above), no
+  // other lane or kernel reads this env's record before the next position stage, and that stage rewrites every field it
+  // hands over -- unconditionally these three's owners (LF_QBIAS, LF_KSIN; LF_KSIN + 1 on every lane that reads it back).
+  constexpr int LF_PARK_QFS0 = LF_QBIAS, LF_PARK_QFS1 = LF_KSIN, LF_PARK_QFS2 = LF_KSIN + 1;
+  LF(LF_PARK_QFS0) = qfs[0]; LF(LF_PARK_QFS1) = qfs[1]; LF(LF_PARK_QFS2) = qfs[2];
   T qw[3];
   qw[0] = isl ? S.warm[eo + ldof] : (T)0;
 #pragma unroll
@@ -982,13 +980,13 @@ __device__ __forceinline__ void rp_lean_solver_body(const RpModel<T>& M, const R
     T cost;
     {
       // reference accelerations of my rows
-      const T fr_aref = LF(7);
+      const T fr_aref = LF(LF_FR_AREF);
       T lim_aref[3] = {0, 0, 0}, con_aref[4] = {0, 0, 0, 0};
 #pragma unroll
-      for (int k = 0; k < 3; k++) if (lim_sign(k) != 0) lim_aref[k] = LF(11 + k);
+      for (int k = 0; k < 3; k++) if (lim_sign(k) != 0) lim_aref[k] = LF(LF_LIM_AREF + k);
       if (lane < ncon) {
 #pragma unroll
-        for (int k = 0; k < 4; k++) con_aref[k] = LF(25 + k);
+        for (int k = 0; k < 4; k++) con_aref[k] = LF(LF_CON_AREF + k);
       }
       auto sub_aref = [&](RowsL& r) {
         r.fr -= fr_aref;
@@ -1133,14 +1131,13 @@ __device__ __forceinline__ void rp_lean_solver_body(const RpModel<T>& M, const R
       // cross-chain contacts go to the packed dense block of the dirty rows (zeroed above; tree_solve adds the
       // Schur complement of the clean rows): entry lane a holds u = C_c J_a and walks the entries b <= a
       if (dmx) {
-        auto cidx = [&](int l) -> int { return __popcll(dmx & lanemask_lt(l)); };
         const HSplit hs = hand_split(dmx);   // (split block: the second hand's packed matrix starts at hs.off1)
         WSYNC();
         for (int e0 = 0; e0 < nent; e0 += 64) {
           const bool valid = e0 + lane < nent;
           const int e = valid ? e0 + lane : nent - 1;
           const int m0 = sm.entM[e][0], m1 = sm.entM[e][1];
-          const int ln = m0 & 63, c = (m0 >> 6) & 31;
+          const int c = (m0 >> 6) & 31;
           const int base = m1 & 255, rank = (m1 >> 16) & 255;
           const bool cross = ((m0 >> 15) & 1) != 0;
           if (__ballot(valid && cross) == 0ull) continue;
@@ -1150,11 +1147,7 @@ __device__ __forceinline__ void rp_lean_solver_body(const RpModel<T>& M, const R
           const T u0 = sn * ja0 + a1 * ja1 + a2 * ja2;
           const T u1 = a1 * ja0 + b1 * ja1;
           const T u2 = a2 * ja0 + b2 * ja2;
-#ifdef RPK_NO_T7
-          const int cia = cross ? cidx(ln) : 0;
-#else
           const int cia = cross ? ((m0 >> 16) & 63) : 0;
-#endif
           T* const Ha = sm.H + (((m0 >> 22) & 1) ? hs.off1 : 0);   // (the entries of a contact belong to one hand)
           for (int k0 = 0; k0 < maxm; k0 += 4) {
             int mb[4];
@@ -1170,11 +1163,7 @@ __device__ __forceinline__ void rp_lean_solver_body(const RpModel<T>& M, const R
             for (int u = 0; u < 4; u++) val[u] = u0 * jq[u][0] + u1 * jq[u][1] + u2 * jq[u][2];
 #pragma unroll
             for (int u = 0; u < 4; u++) {
-#ifdef RPK_NO_T7
-              if (valid && cross && k0 + u <= rank) lds_add(&sm.H[tri(cia, cidx(mb[u] & 63))], val[u]);
-#else
               if (valid && cross && k0 + u <= rank) lds_add(&Ha[tri(cia, (mb[u] >> 16) & 63)], val[u]);
-#endif
             }
           }
         }
@@ -1298,7 +1287,6 @@ __device__ __forceinline__ void rp_lean_solver_body(const RpModel<T>& M, const R
         LsPnt p1 = ls_point(-f0 / h0, true);
         if (p0.c < p1.c) p1 = p0;
         alpha = p1.a;
-#ifndef RPK_X_LS1   // compile-only experiment: the line search cut down to its first Newton point
         if (!(N::abs(p1.d0) < gtol)) {
           const T dir = p1.d0 < 0 ? (T)1 : (T)-1;
           LsPnt p2 = p1;
@@ -1348,7 +1336,6 @@ __device__ __forceinline__ void rp_lean_solver_body(const RpModel<T>& M, const R
             }
           }
         }
-#endif
       }
       PROF(7);
       if (!(alpha > 0)) break;
@@ -1394,8 +1381,8 @@ __device__ __forceinline__ void rp_lean_solver_body(const RpModel<T>& M, const R
     const int K = isk[s] ? kid[s] : 0;
     e_kd[s] = M.key_dof()[K]; e_kdamp[s] = M.key_damping()[K];
   }
-  e_fk[0] = LF(3); e_fk[1] = LF(4);
-  const T e_f0 = LF(0);
+  e_fk[0] = LF(LF_PARK_QFS1); e_fk[1] = LF(LF_PARK_QFS2);
+  const T e_f0 = LF(LF_PARK_QFS0);
   const T e_ldamp = M.link_damping()[L];
   T Rr_e[MD + 1];
   fetch_Mlocal(Rr_e);
@@ -1443,8 +1430,6 @@ __device__ __forceinline__ void rp_lean_solver_body(const RpModel<T>& M, const R
     atomicAdd((unsigned long long*)&S.prof[lane], (unsigned long long)sm.prof[lane]);
   }
   if (S.cost_sol && lane == 0) S.cost_sol[env] = (int)(((long long)__builtin_readcyclecounter() - kernel_t0) >> 8);
-#undef LF
-#undef LI
 }
 
 template <typename T>
