@@ -138,6 +138,19 @@ int rp_set_mpr_tolerance(rp_engine* e, double tolerance, double polytope_toleran
  * rp_field_ptr views: a caller that writes state through a view must call rp_forward (or rp_set)
  * before the next rp_step.  Default: off.  Results are bit-identical either way. */
 int rp_set_lazy_position_stage(rp_engine* e, int on);
+/* Reset snapshot (default: off, as the lazy mode; RP_RESET_SNAPSHOT=1 / 0 in the environment sets the default of new
+ * engines; the env layer, suite/physics.py, turns it on unless RP_RESET_SNAPSHOT=0).  physics.reset() writes
+ * the same state for every env, so the position / velocity stage of a just-reset env (its physics.forward(): site
+ * positions, contacts, actuator velocities, and what the next solver stage reads) gives the same bytes every time.  The
+ * engine computes them once with its own stage kernel for a one-env shadow of the batch and rp_reset / rp_step_masked
+ * copy them into every env they reset, which is then skipped by the leading stage of the next rp_step (no leading stage
+ * is launched at all when the lazy mode is on and every env's stage data is known valid).  The shadow is rebuilt after
+ * any rp_set_* option call; a reset recorded into a hipGraph while it is stale runs the ordinary way.  The snapshot is
+ * not used with rp_set_legacy_step(e, 0), and never again once rp_set(RP_TREE_OFFSET) has been called: per-env root
+ * offsets make reset states differ.  As for state: the engine cannot see tree offsets written through an rp_field_ptr
+ * view -- write them with rp_set.  Results are bit-identical either way; with 0 the engine enqueues exactly what it did
+ * without the snapshot.  No counterpart in the reference (dm_control recomputes mj_forward after every reset). */
+int rp_set_reset_snapshot(rp_engine* e, int on);
 /* dm_control's `legacy_step` (robopianist/suite/__init__.py:55,91 -> composer.Environment(legacy_step=...) ->
  * mjcf.Physics.step).  on (the default, and dm_control's): every physics.step() is `mj_step2; mj_step1`, i.e. after
  * rp_step the position-dependent outputs (RP_SITE_XPOS, RP_NCON / RP_CONTACT_GEOMS / RP_CONTACT_DIST, RP_ACT_VELOCITY)

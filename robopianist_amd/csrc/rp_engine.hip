@@ -24,10 +24,11 @@ namespace {
 // Bookkeeping of the lazy position stage (rp_set_lazy_position_stage): which envs' hand-over
 // (RpStage) still matches their state.
 // (lazy: skip the envs whose hand-over is still the one of their state; also: the envs rp_step_masked has just
-// reset, stepped or not -- their position / velocity stage is the physics.forward() of the new episode)
-__global__ void rp_lead_mask_kernel(int* lead, const int* active, const unsigned char* valid, int lazy, const unsigned char* also, int n) {
+// reset, stepped or not -- their position / velocity stage is the physics.forward() of the new episode;
+// also_lazy: ... unless the reset gave them the snapshot's hand-over and outputs, which it tells by valid[e])
+__global__ void rp_lead_mask_kernel(int* lead, const int* active, const unsigned char* valid, int lazy, const unsigned char* also, int also_lazy, int n) {
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
-  if (e < n) lead[e] = (((active ? active[e] != 0 : true) && !(lazy && valid[e])) || (also && also[e])) ? 1 : 0;
+  if (e < n) lead[e] = (((active ? active[e] != 0 : true) && !(lazy && valid[e])) || (also && also[e] && !(also_lazy && valid[e]))) ? 1 : 0;
 }
 __global__ void rp_mark_valid_kernel(unsigned char* valid, const int* active, const unsigned char* also, int n) {
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
@@ -321,6 +322,12 @@ struct EngineBase {
   virtual void mpr_tolerances(double tol, double poly_tol) = 0;
   bool lazy_position = false;
   bool legacy_step = true;   // rp_set_legacy_step: false = dm_control's legacy_step=False output semantics
+  // the reset snapshot's bookkeeping (rp_schedule.hpp); every setter that could change what the position stage computes
+  // goes through option_changed()
+  RpSnapshotState snap;
+  void option_changed() { rp_snapshot_on_option(snap); }
+  virtual int snapshot_flag_changed() = 0;   // (the device flag follows rp_snapshot_flag(snap))
+  virtual int reset_snapshot(int on) = 0;    // rp_set_reset_snapshot
   bool cost_order = false;   // rp_set_cost_ordered_launch
   int n_slices = 1;          // rp_set_stream_slices (0 = automatic)
   static const int kMaxSlices = kRpMaxSlices;
@@ -633,6 +640,66 @@ struct Engine : EngineBase {
     S.qpos_prev = nullptr; S.qvel_prev = nullptr;
     d_valid = dalloc<unsigned char>(E);  // (zero-filled: nothing is valid yet)
     S.max_newton = M.iterations; S.max_ls = M.ls_iterations;
+    alloc_snapshot();
+  }
+  // The pristine env of the reset snapshot (rp_model.hpp: RpSnapshot): a one-env state and hand-over of its own, beside
+  // the batch -- no env count, stride, slice bound or list of the batch knows of it.  Never stepped.
+  RpSnapshot<T> P{};
+  int* d_snap_ok = nullptr;
+  void alloc_snapshot() {
+    RpState<T>& s = P.S;
+    s = RpState<T>{};
+    s.nenv = 1;
+    s.qpos = dalloc<T>(nv); s.qvel = dalloc<T>(nv); s.warm = dalloc<T>(nv);
+    s.ctrl = dalloc<T>(nu); s.qfrc_applied = dalloc<T>(nv); s.time = dalloc<T>(1);
+    s.tree_offset = dalloc<T>((ntree ? ntree : 1) * 3);   // (zeros, not null: the stage adds them as it does for the batch)
+    s.act_force = dalloc<T>(nu); s.act_vel = dalloc<T>(nu);
+    s.site_xpos = dalloc<T>((nsite ? nsite : 1) * 3);
+    s.contact_dist = dalloc<T>(RPK_NCOUT);
+    s.ncon = dalloc<int>(1); s.contact_geoms = dalloc<int>(RPK_NCOUT * 2);
+    s.warn = dalloc<int>(1); s.solver_iter = dalloc<int>(1);
+    s.cost_pos = dalloc<int>(1); s.cost_sol = dalloc<int>(1);
+    RpStage<T>& b = P.B;
+    b = RpStage<T>{};
+    P.md = md();
+#define X(buf, per_env, live) b.buf = dalloc<std::remove_pointer_t<decltype(b.buf)>>(per_env);
+    { const int md = P.md; RPK_SNAPSHOT_HANDOVER(X) }
+#undef X
+    d_snap_valid = dalloc<unsigned char>(1);
+    d_snap_ok = dalloc<int>(1);   // (zero: no snapshot yet)
+    P.ok = d_snap_ok;
+  }
+  // Builds the snapshot on the engine's stream: physics.reset() of the pristine env, then the engine's own position /
+  // velocity stage for it -- the one-kernel stage, which is bit-identical to the split stage and needs no pooled lists.
+  // The options the stage reads travel with the launch (M, S.lean), so a build after a setter sees the new values.
+  void build_snapshot() {
+    RpState<T> s = P.S;
+    s.max_newton = S.max_newton; s.max_ls = S.max_ls; s.lean = S.lean;
+    RpSnapshot<T> none{};
+    hipLaunchKernelGGL(rp_reset_kernel<T>, dim3(1), dim3(64), 0, stream, s, d_qpos0, (const unsigned char*)nullptr, nv, nu, nsite, d_snap_valid, P.B, none);
+    launch_stage<T, 0>(variant, 1, stream, M, s, P.B, -1, 1);
+    snap_built = true;
+    rp_snapshot_on_built(snap);
+    snapshot_flag_changed();
+  }
+  unsigned char* d_snap_valid = nullptr;   // (the pristine env's own stage_valid byte: written by its reset, read by nothing)
+  bool snap_built = false;                 // the pristine env holds a snapshot, fresh or not
+  int reset_snapshot(int on) override {
+    HIP_OK(hipSetDevice(device));
+    snap.enabled = on != 0;
+    option_changed();
+    if (!on) {
+      // off means "as if the snapshot had never existed": the hand-overs earlier resets copied are recomputed too
+      HIP_OK(hipMemsetAsync(d_valid, 0, (size_t)nenv, stream));
+      rp_snapshot_on_state_write(snap, false, stream_capturing());
+    }
+    return snapshot_flag_changed();
+  }
+  int snapshot_flag_changed() override {
+    if (!d_snap_ok || !snap_built) return 0;   // (never built: the flag is still the zero it was allocated with)
+    HIP_OK(hipSetDevice(device));
+    HIP_OK(hipMemsetAsync(d_snap_ok, (rp_snapshot_flag(snap) && snap_built) ? 1 : 0, 1, stream));
+    return 0;
   }
   // RP_SPLIT_POS, RP_LEAN, RP_DENSE_HANDS (RP_FORCE_DEEP: upload_tables; RP_FUSED, RP_FUSED_SPLIT, RP_HEAVY_GRID: their members)
   void read_switches() {
@@ -643,6 +710,12 @@ struct Engine : EngineBase {
       split_mode = !split_capable ? 0 : (sp ? (sp[0] == '0' ? 0 : (sp[0] == '1' ? 1 : 2)) : 2);
       // (the buffers -- 78 KB per env: 320 MB at 4096 envs -- are allocated by the first rp_step that runs the split stage:
       // ensure_split_buffers; an engine that never does, small batches and RP_SPLIT_POS=0 among them, never pays for them)
+    }
+    {
+      // The reset snapshot is off in a new engine, as the lazy mode is: rp_set_reset_snapshot turns it on (the env layer,
+      // suite/physics.py, does).  RP_RESET_SNAPSHOT=1 / =0 sets the engine's own default.  Off: every launch as before it existed.
+      const char* rs = getenv("RP_RESET_SNAPSHOT");
+      snap.enabled = rs && rs[0] != '0';
     }
     {
       const char* le = getenv("RP_LEAN");
@@ -821,8 +894,23 @@ struct Engine : EngineBase {
   }
 
   // physics.reset() of the envs a device mask flags (null: all) -- rp_reset and rp_step_masked
-  void launch_reset(const unsigned char* dmask) {
-    hipLaunchKernelGGL(rp_reset_kernel<T>, dim3(nenv), dim3(64), 0, stream, reset_state(), d_qpos0, dmask, nv, nu, nsite, d_valid);
+  // Returns true when the envs got the reset snapshot with it (their hand-over is valid: no leading stage for them).
+  // lead_follows: rp_step_masked -- the leading stage of the same call takes the envs that did not get it.
+  bool launch_reset(const unsigned char* dmask, bool capturing, bool lead_follows) {
+    const RpSnapshotUse use = rp_snapshot_use(snap, capturing);
+    if (use == kRpSnapBuild) build_snapshot();
+    const bool used = use != kRpSnapNone;
+    RpSnapshot<T> p = P;
+    if (!used) p.ok = nullptr;
+    // (four waves per env when there is a snapshot to copy: ~22 KB per reset env, a dependent load -> store trip per KB and wave)
+    hipLaunchKernelGGL(rp_reset_kernel<T>, dim3(nenv), dim3(used ? 256 : 64), 0, stream, reset_state(), d_qpos0, dmask, nv, nu, nsite, d_valid, B, p);
+    rp_snapshot_on_reset(snap, used, dmask == nullptr, lead_follows, capturing);
+    return used;
+  }
+  bool stream_capturing() const {
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    (void)hipStreamIsCapturing(stream, &cap);
+    return cap != hipStreamCaptureStatusNone;
   }
   int reset(const uint8_t* mask) override {
     HIP_OK(hipSetDevice(device));
@@ -836,7 +924,7 @@ struct Engine : EngineBase {
         dmask = d_mask;
       }
     }
-    launch_reset(dmask);
+    launch_reset(dmask, stream_capturing(), false);
     HIP_OK(hipGetLastError());
     return 0;
   }
@@ -890,7 +978,12 @@ struct Engine : EngineBase {
     }
     if (f == RP_ACTIVE) S.active = d_active;
     // state the position stage depends on changed: every env's hand-over is stale
-    if (f == RP_QPOS || f == RP_QVEL || f == RP_TREE_OFFSET) HIP_OK(hipMemsetAsync(d_valid, 0, (size_t)nenv, stream));
+    if (f == RP_QPOS || f == RP_QVEL || f == RP_TREE_OFFSET) {
+      HIP_OK(hipMemsetAsync(d_valid, 0, (size_t)nenv, stream));
+      rp_snapshot_on_state_write(snap, f == RP_TREE_OFFSET, stream_capturing());
+      // (tree offsets: a reset state is no longer the same for every env -- the snapshot is off for this engine)
+      if (f == RP_TREE_OFFSET) RP_TRY(snapshot_flag_changed());
+    }
     return 0;
   }
   int get(rp_field f, void* dst) override {
@@ -1128,11 +1221,13 @@ struct Engine : EngineBase {
   int step(int nsub, uint32_t* trace, int mode, const uint8_t* reset_mask = nullptr) override {
     HIP_OK(hipSetDevice(device));
     if (mode == 0 && nsub <= 0) return fail("rp_step: n_substeps must be positive");
+    bool snap_used = false;
     if (reset_mask) {
       // rp_step_masked: physics.reset() of the flagged envs first (same launch as rp_reset with a device mask); their
       // physics.forward() is the leading position / velocity stage below
+      // -- unless the reset itself hands them the stage's results for the reset state (the reset snapshot)
       if (!is_device_ptr(reset_mask)) return fail("rp_step_masked: the reset mask must be device memory");
-      launch_reset(reset_mask);
+      snap_used = launch_reset(reset_mask, stream_capturing(), true);
     }
     StepCtx c;
     c.nsub = nsub; c.mode = mode; c.reset_mask = reset_mask;
@@ -1154,24 +1249,29 @@ struct Engine : EngineBase {
     const bool lazy_now = lazy_position && legacy_step;
     c.s.stale_outputs = (!legacy_step && mode == 0) ? 1 : 0;
     c.lead_masked = (lazy_now || reset_mask) && mode == 0;
-    if (c.lead_masked)
-      hipLaunchKernelGGL(rp_lead_mask_kernel, dim3((nenv + 255) / 256), dim3(256), 0, stream, d_lead, c.s.active, d_valid, lazy_now ? 1 : 0, reset_mask, nenv);
+    // (the lazy mode with every hand-over known valid, the envs just reset included: no leading stage at all)
+    const bool no_lead = rp_lead_skippable(snap, mode, lazy_now, c.capturing, reset_mask != nullptr, snap_used);
+    if (c.lead_masked && !no_lead)
+      hipLaunchKernelGGL(rp_lead_mask_kernel, dim3((nenv + 255) / 256), dim3(256), 0, stream, d_lead, c.s.active, d_valid, lazy_now ? 1 : 0, reset_mask, snap_used ? 1 : 0, nenv);
     RP_TRY(fork_slices(c));
     for (int sl = 0; sl < c.nsl; sl++) {
       Slice x = slice_of(c, sl);
-      // mj_step1 for the current state, in index order: d_order may date from a step with another slice
-      // count (a permutation of other ranges), and every slice must write the hand-over of exactly ITS envs
-      // before its solver stage reads it (the solver stage consumes the hand-over: it parks values in it)
-      RpState<T> lead = x.ss;
-      lead.order = nullptr;
-      if (c.lead_masked) lead.active = d_lead;   // skipped for envs whose hand-over is still the one of their state
-      emit_pos(c, x, lead, -1);
+      if (!no_lead) {
+        // mj_step1 for the current state, in index order: d_order may date from a step with another slice
+        // count (a permutation of other ranges), and every slice must write the hand-over of exactly ITS envs
+        // before its solver stage reads it (the solver stage consumes the hand-over: it parks values in it)
+        RpState<T> lead = x.ss;
+        lead.order = nullptr;
+        if (c.lead_masked) lead.active = d_lead;   // skipped for envs whose hand-over is still the one of their state
+        emit_pos(c, x, lead, -1);
+      }
       if (mode != 0) continue;
       // ... then n_sub x (mj_step2; mj_step1), in one launch per slice or stage by stage
       if (c.plan.fused_now && sizeof(T) == 8) { RP_TRY(emit_fused_slice(c, x)); continue; }
       for (int k = 0; k < nsub; k++) RP_TRY(emit_substep(c, x, k));
     }
     RP_TRY(join_slices(c));
+    rp_snapshot_on_step_done(snap, c.s.active != nullptr, c.capturing);
     return finish(c, trace, need);
   }
 };
@@ -1238,6 +1338,7 @@ int rp_step_masked(rp_engine* e, int n_substeps, uint32_t* key_trace, const uint
 int rp_set_solver_limits(rp_engine* e, int max_newton_iter, int max_ls_iter) {
   if (!e) return fail("null engine");
   E(e)->limits(max_newton_iter, max_ls_iter);
+  E(e)->option_changed();
   return 0;
 }
 int rp_profile(rp_engine* e, long long* out, int n, int enable) {
@@ -1246,38 +1347,49 @@ int rp_profile(rp_engine* e, long long* out, int n, int enable) {
 int rp_set_mpr_tolerance(rp_engine* e, double tolerance, double polytope_tolerance) {
   if (!e) return fail("null engine");
   E(e)->mpr_tolerances(tolerance, polytope_tolerance);
+  E(e)->option_changed();
   return 0;
 }
 int rp_set_solver_tolerance(rp_engine* e, double tolerance, double ls_tolerance) {
   if (!e) return fail("null engine");
   E(e)->tolerances(tolerance, ls_tolerance);
+  E(e)->option_changed();
   return 0;
 }
 int rp_set_lazy_position_stage(rp_engine* e, int on) {
   if (!e) return fail("null engine");
   E(e)->lazy_position = on != 0;
+  E(e)->option_changed();
   return 0;
+}
+int rp_set_reset_snapshot(rp_engine* e, int on) {
+  if (!e) return fail("null engine");
+  return E(e)->reset_snapshot(on);
 }
 int rp_set_legacy_step(rp_engine* e, int on) {
   if (!e) return fail("null engine");
   E(e)->legacy_step = on != 0;
-  return 0;
+  E(e)->option_changed();
+  E(e)->snap.legacy_step = on != 0;   // (off: the leading stage publishes every env's outputs -- no snapshot)
+  return E(e)->snapshot_flag_changed();
 }
-int rp_set_acc_sensors(rp_engine* e, int on) { return e ? E(e)->acc_sensors(on) : fail("null engine"); }
-int rp_set_lean_solver(rp_engine* e, int on) { return e ? E(e)->lean_solver(on) : fail("null engine"); }
-int rp_set_fused_substeps(rp_engine* e, int on) { return e ? E(e)->fused_substeps(on) : fail("null engine"); }
+int rp_set_acc_sensors(rp_engine* e, int on) { if (e) E(e)->option_changed(); return e ? E(e)->acc_sensors(on) : fail("null engine"); }
+int rp_set_lean_solver(rp_engine* e, int on) { if (e) E(e)->option_changed(); return e ? E(e)->lean_solver(on) : fail("null engine"); }
+int rp_set_fused_substeps(rp_engine* e, int on) { if (e) E(e)->option_changed(); return e ? E(e)->fused_substeps(on) : fail("null engine"); }
 int rp_get_fused_substeps(rp_engine* e) { return e ? E(e)->fused_substeps_on() : fail("null engine"); }
-int rp_set_split_position_stage(rp_engine* e, int on) { return e ? E(e)->split_position(on) : fail("null engine"); }
+int rp_set_split_position_stage(rp_engine* e, int on) { if (e) E(e)->option_changed(); return e ? E(e)->split_position(on) : fail("null engine"); }
 int rp_get_split_position_stage(rp_engine* e) { return e ? E(e)->split_position_on() : fail("null engine"); }
 int rp_set_stream_slices(rp_engine* e, int n) {
   if (!e) return fail("null engine");
   if (n != 0 && n != 1 && n != 2 && n != 3 && n != 4) return fail("rp_set_stream_slices: 0 (automatic), 1, 2, 3 or 4");
   E(e)->n_slices = n;
+  E(e)->option_changed();
   return 0;
 }
 int rp_set_cost_ordered_launch(rp_engine* e, int on) {
   if (!e) return fail("null engine");
   E(e)->cost_order = on != 0;
+  E(e)->option_changed();
   return 0;
 }
 int rp_sync(rp_engine* e) {

@@ -97,12 +97,25 @@ struct Smem<T, 2, MD> : Smem<T, 0, MD> {
 }  // namespace rpk
 
 // physics.reset() for the envs selected by a device-side mask (null = all).
+// With a reset snapshot (P.ok set and 1; rp_model.hpp: RpSnapshot) the env also gets the hand-over and the outputs of
+// the position / velocity stage of its new state, copied from the pristine env, and its hand-over is valid at once.
 template <typename T>
 __global__ void rp_reset_kernel(RpState<T> S, const T* qpos0, const unsigned char* mask, int nv, int nu, int nsite,
-                                unsigned char* stage_valid) {
+                                unsigned char* stage_valid, RpStage<T> B, RpSnapshot<T> P) {
   const int env = blockIdx.x;
   if (mask && !mask[env]) return;
-  if (threadIdx.x == 0) stage_valid[env] = 0;  // the hand-over of this env no longer matches its state
+  const bool snap = P.ok && *P.ok == 1;
+  if (snap) {
+    const int md = P.md;
+    const int* h = P.B.hdr;
+#define X(buf, per_env, live) rp_copy_wide(B.buf + (size_t)env * (per_env), P.B.buf, (live));
+    RPK_SNAPSHOT_HANDOVER(X)
+#undef X
+#define X(arr, per_env) if (S.arr) for (int i = threadIdx.x; i < (per_env); i += blockDim.x) S.arr[(size_t)env * (per_env) + i] = P.S.arr[i];
+    RPK_SNAPSHOT_OUTPUTS(X)
+#undef X
+  }
+  if (threadIdx.x == 0) stage_valid[env] = snap ? 1 : 0;  // without: the hand-over of this env no longer matches its state
   for (int i = threadIdx.x; i < nv; i += blockDim.x) {
     S.qpos[(size_t)env * nv + i] = qpos0[i];
     S.qvel[(size_t)env * nv + i] = 0;
@@ -110,7 +123,7 @@ __global__ void rp_reset_kernel(RpState<T> S, const T* qpos0, const unsigned cha
     S.qfrc_applied[(size_t)env * nv + i] = 0;
   }
   for (int i = threadIdx.x; i < nu; i += blockDim.x) S.ctrl[(size_t)env * nu + i] = 0;
-  if (threadIdx.x == 0) { S.time[env] = 0; S.warn[env] = 0; }
+  if (threadIdx.x == 0) { S.time[env] = 0; if (!snap) S.warn[env] = 0; }
   // acceleration-stage sensors: no reading of the previous episode survives a reset (the first observation of the
   // new episode reports zero until the first step has run the sensor stage)
   if (S.sens_torque) for (int i = threadIdx.x; i < nv; i += blockDim.x) S.sens_torque[(size_t)env * nv + i] = 0;

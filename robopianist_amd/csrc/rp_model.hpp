@@ -427,3 +427,53 @@ struct RpStage {
   size_t tstride; // ceil(E / 8) * RPK_NCAND: one stripe of one type (a slice's entries start at (env_base / 8) * RPK_NCAND)
   int* split_dropped;   // may be null: counts the envs whose candidate / record lists overflowed (RP_WARN_SPLIT_FULL)
 };
+
+// ---- The reset snapshot: what the position / velocity stage leaves for an env that rp_reset_kernel has just written.
+// That state is the same for every env (qpos0, everything else zero), so with all-zero tree offsets the stage's results
+// are the same bytes every time: the engine computes them once for a one-env shadow ("pristine env", RpSnapshot) with
+// its own stage kernel, and rp_reset_kernel copies them instead of the env going through the leading stage.
+// THE ONE LIST of what is copied -- a new hand-over buffer or a new output of the stage for substep -1 goes here:
+//   X(buffer, elements per env, elements of them that are live)       (`h` = the pristine env's hdr record, `md` = the
+//   kernel build's tree depth; hdr itself: HDR_NCON .. HDR_CLASS -- HDR_RESUME belongs to the fused kernels)
+// Not on it: the split stage's intermediates (frames, cand, ncand, cres, cres_n, tlist), which no later launch reads.
+#define RPK_SNAPSHOT_HANDOVER(X)                                                                          \
+  X(RM, RPK_NLX(md) * (md + 1), RPK_NLX(md) * (md + 1))                                                   \
+  X(lanef, RPK_NLF * 64, RPK_NLF * 64)                                                                    \
+  X(lanei, RPK_NLI * 64, RPK_NLI * 64)                                                                    \
+  X(hdr, rpk::HDR_N, rpk::HDR_RESUME)                                                                     \
+  X(entJ, RpCaps<T>::NE * 3, rp_clampi(h[rpk::HDR_NENT], 0, RpCaps<T>::NE) * 3)                           \
+  X(entM, RpCaps<T>::NE * 2, rp_clampi(h[rpk::HDR_NENT], 0, RpCaps<T>::NE) * 2)                           \
+  X(slots, rpk::SLOT_N, rpk::SLOT_N)                                                                      \
+  X(keyslot, RPK_NKEYS / 4, RPK_NKEYS / 4)                                                                \
+  X(covf, (RPK_NC - RPK_NCL) * 12, rp_clampi(h[rpk::HDR_NCON] - RPK_NCL, 0, RPK_NC - RPK_NCL) * 12)        \
+  X(covi, (RPK_NC - RPK_NCL) * 4, rp_clampi(h[rpk::HDR_NCON] - RPK_NCL, 0, RPK_NC - RPK_NCL) * 4)
+//   X(array, elements per env)       the outputs the stage publishes into RpState (its "outputs" block; site_xpos from
+//   the kinematics); warn is OR-ed by the stage into the zero rp_reset_kernel has just written: a plain copy here
+#define RPK_SNAPSHOT_OUTPUTS(X)                                                                           \
+  X(act_vel, nu) X(site_xpos, nsite * 3) X(contact_geoms, RPK_NCOUT * 2) X(contact_dist, RPK_NCOUT)        \
+  X(ncon, 1) X(cost_pos, 1) X(warn, 1)
+__host__ __device__ __forceinline__ int rp_clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+template <typename T>
+struct RpSnapshot {
+  RpState<T> S;    // one env: the reset state and the stage's outputs for it
+  RpStage<T> B;    // ... and its hand-over (a copy SOURCE only: a solver stage parks values in the hand-over it consumes)
+  // device flag, null = no snapshot (rp_reset_kernel as it always was): 1 while the snapshot may stand in for the
+  // leading stage of a reset env; the host clears it when tree offsets are set or the switch goes off, so that a reset
+  // recorded in a hipGraph falls back to the leading stage when it is replayed afterwards
+  const int* ok;
+  int md;          // tree depth of the kernel build in use (RPK_MAXD / RPK_MAXD_DEEP): RM's shape
+};
+// `n` elements from `src` to `dst` by the threads of a workgroup: 16 bytes per thread and trip where both sides allow
+template <typename U>
+__device__ __forceinline__ void rp_copy_wide(U* __restrict__ dst, const U* __restrict__ src, int n) {
+  static_assert(16 % sizeof(U) == 0, "element size");
+  constexpr int W = 16 / sizeof(U);
+  const int t = (int)threadIdx.x, nt = (int)blockDim.x;
+  if ((((size_t)dst | (size_t)src) & 15) == 0) {
+    const int nw = n / W;
+    for (int i = t; i < nw; i += nt) ((int4*)dst)[i] = ((const int4*)src)[i];
+    for (int i = nw * W + t; i < n; i += nt) dst[i] = src[i];
+  } else {
+    for (int i = t; i < n; i += nt) dst[i] = src[i];
+  }
+}

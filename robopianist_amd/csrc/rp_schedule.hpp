@@ -114,6 +114,56 @@ inline bool rp_heavy_pos_alongside(const RpStepInput& in, bool on_companion_stre
   return on_companion_stream && !in.deep && !in.graph && fp64 && est >= kRpHeavyOn;
 }
 
+// ---- The reset snapshot (rp_model.hpp: RpSnapshot): the host's bookkeeping, as pure functions of this record.
+// Engine<T> calls the rp_snapshot_on_* functions where the events happen and asks the two questions below.
+struct RpSnapshotState {
+  bool enabled = true;           // RP_RESET_SNAPSHOT / rp_set_reset_snapshot
+  bool fresh = false;            // built, and nothing that could change what the position stage computes has been set since
+  bool tree_offset_set = false;  // rp_set(RP_TREE_OFFSET) has been called: the reset state is no longer the same for every env -- off for good
+  bool legacy_step = true;       // rp_set_legacy_step(0): the leading stage publishes the incoming state's outputs for all envs -- off
+  // What the host knows of the device's stage_valid flags: true only while EVERY env's hand-over is known to match its
+  // state (then a lazy rp_step needs no leading stage at all).  Conservative: false whenever the host cannot tell.
+  bool all_valid = false;
+  bool poisoned = false;         // a reset or a state write was recorded into a hipGraph: its replays change stage_valid unseen -- all_valid stays false
+};
+enum RpSnapshotUse { kRpSnapNone = 0, kRpSnapUse = 1, kRpSnapBuild = 2 };   // (Build: build it now, then use it)
+// May the reset of this call copy the snapshot?  A stale snapshot is rebuilt, except inside a stream capture (the build
+// is not part of the caller's graph): that call resets the ordinary way and its envs go through the leading stage.
+inline RpSnapshotUse rp_snapshot_use(const RpSnapshotState& s, bool capturing) {
+  if (!s.enabled || s.tree_offset_set || !s.legacy_step) return kRpSnapNone;
+  if (s.fresh) return kRpSnapUse;
+  return capturing ? kRpSnapNone : kRpSnapBuild;
+}
+// Does the device flag RpSnapshot::ok stand?  (Staleness is not in it: a stale snapshot is only kept from NEW resets.)
+inline bool rp_snapshot_flag(const RpSnapshotState& s) { return s.enabled && !s.tree_offset_set && s.legacy_step; }
+// ... a model-table upload or any option setter (tolerances, impratio, capacity classes, sensors, ...): err on the side of stale
+inline void rp_snapshot_on_option(RpSnapshotState& s) { s.fresh = false; }
+inline void rp_snapshot_on_built(RpSnapshotState& s) { s.fresh = true; }
+// ... rp_set(RP_QPOS | RP_QVEL | RP_TREE_OFFSET): every stage_valid flag is cleared
+inline void rp_snapshot_on_state_write(RpSnapshotState& s, bool tree_offset, bool capturing) {
+  s.all_valid = false;
+  if (tree_offset) s.tree_offset_set = true;
+  if (capturing) s.poisoned = true;
+}
+// ... a reset: `used` = its envs got the snapshot (stage_valid 1), else their flags are cleared; `whole_batch` = no mask;
+// `lead_follows` = rp_step_masked without the snapshot: the leading stage of the same call makes the envs valid again
+inline void rp_snapshot_on_reset(RpSnapshotState& s, bool used, bool whole_batch, bool lead_follows, bool capturing) {
+  if (capturing) { s.poisoned = true; s.all_valid = false; return; }
+  if (used) s.all_valid = s.all_valid || whole_batch;
+  else if (!lead_follows) s.all_valid = false;
+}
+// ... the end of an rp_step / rp_forward: it marks every env it touched valid; without an RP_ACTIVE mask that is all of them
+inline void rp_snapshot_on_step_done(RpSnapshotState& s, bool active_mask, bool capturing) {
+  if (!capturing && !active_mask && !s.poisoned) s.all_valid = true;
+}
+// May an rp_step leave out its leading position / velocity stage (mask kernel and every slice's launch)?  Only the lazy
+// mode may (otherwise the stage runs for every active env), outside a capture (a graph must work for any later state),
+// when no env can need it: all valid, and the envs this call resets got the snapshot.
+inline bool rp_lead_skippable(const RpSnapshotState& s, int mode, bool lazy_now, bool capturing, bool has_reset, bool snap_used) {
+  // (s.enabled: with the switch off the engine enqueues exactly what it did before the snapshot existed)
+  return s.enabled && mode == 0 && lazy_now && !capturing && !s.poisoned && s.all_valid && (!has_reset || snap_used);
+}
+
 // slice sl of nsl covers the envs [bound(sl), bound(sl + 1)); bounds are multiples of 8 (XCD classes of the order)
 inline int rp_slice_bound(int nenv, int nsl, int sl) { return sl >= nsl ? nenv : (int)(((long long)nenv * sl / nsl + 7) / 8 * 8); }
 

@@ -39,7 +39,7 @@ WARN_DENSE_FULL = 32
 
 EXPORTED_SYMBOLS = (
     "rp_create", "rp_destroy", "rp_reset", "rp_set", "rp_get", "rp_step", "rp_forward", "rp_step_masked",
-    "rp_set_solver_limits", "rp_set_solver_tolerance", "rp_set_mpr_tolerance", "rp_set_lazy_position_stage", "rp_set_legacy_step", "rp_set_cost_ordered_launch", "rp_set_stream_slices", "rp_set_lean_solver", "rp_set_fused_substeps", "rp_get_fused_substeps", "rp_set_split_position_stage", "rp_get_split_position_stage", "rp_set_acc_sensors", "rp_sync", "rp_get_stream", "rp_set_stream", "rp_field_ptr",
+    "rp_set_solver_limits", "rp_set_solver_tolerance", "rp_set_mpr_tolerance", "rp_set_lazy_position_stage", "rp_set_reset_snapshot", "rp_set_legacy_step", "rp_set_cost_ordered_launch", "rp_set_stream_slices", "rp_set_lean_solver", "rp_set_fused_substeps", "rp_get_fused_substeps", "rp_set_split_position_stage", "rp_get_split_position_stage", "rp_set_acc_sensors", "rp_sync", "rp_get_stream", "rp_set_stream", "rp_field_ptr",
     "rp_n_envs", "rp_dim",
     "rp_kernel_time", "rp_solver_kernel_time", "rp_solver_kernel_envs", "rp_solver_kernel_fused", "rp_profile", "rp_last_error",
 )
@@ -72,6 +72,7 @@ def load_library(path: str = LIB_PATH):
     L.rp_set_solver_tolerance.argtypes = [ctypes.c_void_p, ctypes.c_double, ctypes.c_double]
     L.rp_set_mpr_tolerance.argtypes = [ctypes.c_void_p, ctypes.c_double, ctypes.c_double]
     L.rp_set_lazy_position_stage.argtypes = [ctypes.c_void_p, ctypes.c_int]
+    L.rp_set_reset_snapshot.argtypes = [ctypes.c_void_p, ctypes.c_int]
     L.rp_set_cost_ordered_launch.argtypes = [ctypes.c_void_p, ctypes.c_int]
     L.rp_set_acc_sensors.argtypes = [ctypes.c_void_p, ctypes.c_int]
     L.rp_set_stream_slices.argtypes = [ctypes.c_void_p, ctypes.c_int]
@@ -250,6 +251,12 @@ class BatchedPhysics:
         """rp_step skips its leading position/velocity stage for envs whose stage data is still
         valid (see include/rp_engine.h); state written through views then needs forward()."""
         self._check(self._L.rp_set_lazy_position_stage(self._h, int(bool(on))))
+
+    def set_reset_snapshot(self, on: bool = True):
+        """Resets copy the position / velocity stage's results for the reset state from a one-env shadow instead of
+        recomputing them per env (include/rp_engine.h: rp_set_reset_snapshot); bit-identical results.  Tree offsets
+        written through a view are invisible to it: write them with set(TREE_OFFSET, ...)."""
+        self._check(self._L.rp_set_reset_snapshot(self._h, int(bool(on))))
 
     def set_acc_sensors(self, on: bool = True):
         """Torque / touch sensors (SENSOR_TORQUE, SENSOR_TOUCH) after every step(): one extra launch per

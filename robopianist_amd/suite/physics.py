@@ -49,6 +49,10 @@ class TorchPhysics:
         # followed by forward(): rp_step may skip its leading position stage for untouched envs.
         # Code that writes `physics.qpos` / `qvel` through the views must call forward() itself.
         e.set_lazy_position_stage(True)
+        # a reset copies the position stage's results for the reset state instead of the env going through the leading
+        # stage of the next step (include/rp_engine.h: rp_set_reset_snapshot); tree offsets go through set_tree_offset
+        if os.environ.get("RP_RESET_SNAPSHOT", "1") != "0":
+            e.set_reset_snapshot(True)
         # heterogeneous batches (random policies, envs at their own episode times): heaviest envs first
         e.set_cost_ordered_launch(os.environ.get("RP_COST_ORDER", "1") != "0")
         # two halves of the batch on two streams (one half's launch tail overlaps the other half's next
@@ -163,7 +167,11 @@ class TorchPhysics:
                                  .expand(self.n_envs, self.model.nv))
 
     def set_tree_offset(self, off):
-        self._tree_offset.copy_(torch.as_tensor(off, dtype=self.dtype, device=self.device))
+        # (through rp_set, not the view: the engine must see that the reset state is no longer the same for every env --
+        # include/rp_engine.h: rp_set_reset_snapshot)
+        off = torch.as_tensor(off, dtype=self.dtype, device=self.device).expand(self._tree_offset.shape).contiguous()
+        self._tree_offset_src = off   # keep alive until the copy has run
+        self.engine.set(eng.TREE_OFFSET, off)
 
     @property
     def active_mask(self):
@@ -195,12 +203,23 @@ class TorchPhysics:
         """The LIVE tensors `state_dict` would clone, `{name: tensor [n_envs, ...]}`: zero-copy views of engine memory.
         Writing them is writing the engine's state; as after `load_state_dict`, follow it with `active <- 1` and
         forward().  (The planner's fork reads the real env's views and writes the planning env's: planning.py.)"""
-        return dict(self._state_views())
+        views = dict(self._state_views())
+        if "tree_offset" in views:
+            # (the caller may write tree offsets the engine cannot see: no reset snapshot for this engine)
+            self.engine.set_reset_snapshot(False)
+        return views
 
     def load_state_dict(self, sd):
         views = self._state_views()
         for k, v in views.items():
-            v.copy_(sd[k].to(device=self.device, dtype=v.dtype))
+            src = sd[k].to(device=self.device, dtype=v.dtype)
+            if k == "tree_offset":
+                # (offsets that change go through rp_set, as in set_tree_offset; a checkpoint of a task without them
+                # leaves the engine's reset snapshot alone -- one read-back, a resume is rare)
+                if not torch.equal(src.reshape(v.shape), v):
+                    self.set_tree_offset(src.reshape(v.shape))
+                continue
+            v.copy_(src)
         self._active.fill_(1)
         self.engine.forward()
 
