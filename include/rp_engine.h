@@ -228,6 +228,11 @@ int rp_set_stream(rp_engine* e, void* hip_stream);
 int rp_field_ptr(rp_engine* e, rp_field f, void** ptr, size_t* bytes);
 int rp_n_envs(const rp_engine* e);
 int rp_dim(const rp_engine* e, const char* name); /* "nv","nu","nsite","ntree","nkey","nlink","maxdepth","precision"; "rm_rows","rm_cols" = per-env shape of RP_DEBUG_MASS_ROWS */
+/* ... and the per-env capacities of the engine's build: "max_contacts" (fp64 64, fp32 32), "max_entries" (contact Jacobian
+ * entries: 640 / 240), "max_dense_rows" (rows the solver's dense cross-chain block has room for: 60 / 56).  Beyond the first
+ * two the position stage keeps the deepest contacts and sets RP_WARN_CONTACT_FULL: a step without that flag lost nothing.
+ * RP_MAX_CONTACTS stays the width of RP_CONTACT_DIST / RP_CONTACT_GEOMS in both builds; slots from NCON on hold
+ * dist = 0 and geoms = (-1, -1). */
 /* Average device time (ms) of one rp_step launch sequence (1 + 2*n_substeps kernels)
  * since the last call, measured with HIP events on the engine stream; also returns
  * the number of sequences timed. */

@@ -30,6 +30,15 @@ extern "C" {
 typedef struct rpo_model rpo_model;
 typedef struct rpo_data rpo_data;
 
+/* The scalar type of every stored value and of every array behind rpo_get_ptr.  The default build (librp_oracle.so) is
+ * the fp64 reference.  -DRPO_FLOAT32 (librp_oracle_f32.so) restates the same formulae in float32: the yardstick for
+ * the fp32 engine's rounding error, never a reference of its own (rp_oracle.c states how mixed that build is). */
+#ifdef RPO_FLOAT32
+typedef float rpo_real;
+#else
+typedef double rpo_real;
+#endif
+
 /* fields for rpo_get_ptr */
 enum {
   RPO_QPOS = 0, RPO_QVEL, RPO_QACC, RPO_QACC_WARMSTART, RPO_CTRL, RPO_QFRC_APPLIED,
@@ -60,7 +69,7 @@ void rpo_forward(const rpo_model* m, rpo_data* d);
 /* One physics.step() in dm_control legacy order: mj_step2 then mj_step1. */
 void rpo_step(const rpo_model* m, rpo_data* d);
 
-double* rpo_get_ptr(const rpo_model* m, rpo_data* d, int field);
+rpo_real* rpo_get_ptr(const rpo_model* m, rpo_data* d, int field);
 int rpo_ncon(const rpo_data* d);
 int rpo_nefc(const rpo_data* d);
 int rpo_solver_iter(const rpo_data* d);
@@ -69,11 +78,11 @@ int rpo_warnings(const rpo_data* d);
 /* Batched CPU baseline: steps `nenv` independent copies `nstep` times with the
  * given per-env ctrl [nenv][nu] (held constant), OpenMP over envs. Returns
  * seconds of wall time. */
-double rpo_bench(const rpo_model* m, int nenv, int nstep, const double* ctrl,
-                 int nthreads, double* qpos_out /* [nenv][nq] or NULL */);
+double rpo_bench(const rpo_model* m, int nenv, int nstep, const rpo_real* ctrl,
+                 int nthreads, rpo_real* qpos_out /* [nenv][nq] or NULL */);
 /* every env replays ctrl_seq [T][nu]: row (start[e] + s / hold) mod T at mj_step s */
-double rpo_bench_seq(const rpo_model* m, int nenv, int nstep, const double* ctrl_seq, int T, int hold,
-                     const int* start, int nthreads, double* qpos_out);
+double rpo_bench_seq(const rpo_model* m, int nenv, int nstep, const rpo_real* ctrl_seq, int T, int hold,
+                     const int* start, int nthreads, rpo_real* qpos_out);
 
 /* Test hook: the line search of the Newton solver (PrimalSearch as restated in rp_oracle.c) on a
  * hand-made one-dimensional problem  phi(alpha) = q0 + q1 alpha + q2 alpha^2 + sum_i row_i(jar_i + alpha jv_i)
@@ -86,9 +95,9 @@ void rpo_debug_set_boxbox_max(int n);
 void rpo_debug_set_mpr(double tol, int discrete);   /* uniform stopping tolerance (<= 0: MuJoCo's 1e-6); resets the polytope tolerance */
 void rpo_debug_set_mpr_poly(double tol_poly);         /* >= 0: polytope pairs (box / hull on both sides) refine to this instead; < 0: off */
 void rpo_debug_newton_stats(long* out, int reset);     /* out[0] Newton directions computed, out[1] of them with the Hessian of the direction before (single-env runs only) */
-double rpo_debug_line_search(int n, const int* type, const double* jar, const double* jv, const double* D,
-                             const double* floss, const double* R, const double quad[3], double gtol,
-                             int ls_iterations, int* evals);
+rpo_real rpo_debug_line_search(int n, const int* type, const rpo_real* jar, const rpo_real* jv, const rpo_real* D,
+                               const rpo_real* floss, const rpo_real* R, const rpo_real quad[3], rpo_real gtol,
+                               int ls_iterations, int* evals);
 
 #ifdef __cplusplus
 }

@@ -14,6 +14,10 @@ import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_PATH = os.path.join(_HERE, "librp_oracle.so")
+# the float32 restatement (rp_oracle.c, -DRPO_FLOAT32): Oracle(model, blob, precision=32).  A yardstick for the fp32
+# engine's rounding error in the tests; smoke() and bench.py's baseline use the fp64 library only.
+_LIB_PATHS = {64: _LIB_PATH, 32: os.path.join(_HERE, "librp_oracle_f32.so")}
+_REAL = {64: (ctypes.c_double, np.float64), 32: (ctypes.c_float, np.float32)}
 
 FIELDS = dict(
     qpos=0, qvel=1, qacc=2, qacc_warmstart=3, ctrl=4, qfrc_applied=5,
@@ -26,22 +30,26 @@ FIELDS = dict(
 
 
 def build(force: bool = False) -> str:
-    src = os.path.join(_HERE, "rp_oracle.c")
-    if (force or not os.path.exists(_LIB_PATH)
-            or os.path.getmtime(_LIB_PATH) < os.path.getmtime(src)):
-        subprocess.check_call(["make", "-C", _HERE, "-s", "-B", "librp_oracle.so"])
+    """Builds both libraries (the fp64 reference and its float32 restatement); returns the fp64 library's path."""
+    srcs = [os.path.join(_HERE, f) for f in ("rp_oracle.c", "rp_oracle.h")]
+    for path in _LIB_PATHS.values():
+        if (force or not os.path.exists(path)
+                or os.path.getmtime(path) < max(os.path.getmtime(s) for s in srcs)):
+            subprocess.check_call(["make", "-C", _HERE, "-s", "-B", os.path.basename(path)])
     return _LIB_PATH
 
 
-_lib = None
+_libs = {}
 
 
-def lib():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(_LIB_PATH):
+def lib(precision: int = 64):
+    if precision not in _LIB_PATHS:
+        raise ValueError("precision must be 64 or 32")
+    if precision not in _libs:
+        if not os.path.exists(_LIB_PATHS[precision]):
             build()
-        L = ctypes.CDLL(_LIB_PATH)
+        c_real = _REAL[precision][0]
+        L = ctypes.CDLL(_LIB_PATHS[precision])
         L.rpo_model_load.restype = ctypes.c_void_p
         L.rpo_model_load.argtypes = [ctypes.c_char_p, ctypes.c_size_t]
         L.rpo_model_free.argtypes = [ctypes.c_void_p]
@@ -50,7 +58,7 @@ def lib():
         L.rpo_data_free.argtypes = [ctypes.c_void_p]
         for f in ("rpo_reset", "rpo_forward", "rpo_step", "rpo_step1"):
             getattr(L, f).argtypes = [ctypes.c_void_p, ctypes.c_void_p]
-        L.rpo_get_ptr.restype = ctypes.POINTER(ctypes.c_double)
+        L.rpo_get_ptr.restype = ctypes.POINTER(c_real)
         L.rpo_get_ptr.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
         for f in ("rpo_ncon", "rpo_nefc", "rpo_solver_iter", "rpo_warnings"):
             getattr(L, f).argtypes = [ctypes.c_void_p]
@@ -65,8 +73,8 @@ def lib():
         L.rpo_debug_set_mpr_poly.argtypes = [ctypes.c_double]
         L.rpo_debug_set_capsule_box.argtypes = [ctypes.c_int]
         L.rpo_debug_set_boxbox_max.argtypes = [ctypes.c_int]
-        _lib = L
-    return _lib
+        _libs[precision] = L
+    return _libs[precision]
 
 
 MPR_POLY_REFINED = 1e-10   # the polytope-pair tolerance of the step-by-step comparisons (engine: rp_set_mpr_tolerance)
@@ -77,8 +85,9 @@ def set_mpr_experiment(tolerance: float = 1e-6, discrete: bool = False, poly_tol
     every pair), which is the oracle's default.  `poly_tolerance`: polytope pairs (box / hull on both sides) refine to
     that instead -- converged, two implementations cannot stop on different portals (rp_oracle.c: g_mpr_tol_poly);
     `discrete` = polytope pairs stop when the support vertex already is a portal vertex (a tolerance-free rule)."""
-    lib().rpo_debug_set_mpr(float(tolerance), int(bool(discrete)))
-    lib().rpo_debug_set_mpr_poly(-1.0 if poly_tolerance is None else float(poly_tolerance))
+    for precision in sorted(set(_libs) | {64}):   # (each library has its own copy of the knobs; the float32 one clamps at 1e-6)
+        lib(precision).rpo_debug_set_mpr(float(tolerance), int(bool(discrete)))
+        lib(precision).rpo_debug_set_mpr_poly(-1.0 if poly_tolerance is None else float(poly_tolerance))
 
 
 # The narrow-phase choices this restatement could not pin from memory (DESIGN section 8), as process-wide switches, so
@@ -97,9 +106,9 @@ def set_narrow_phase_variant(capsule_box: int = 0, boxbox_max: int = 8, mpr: str
     """Selects one combination of NARROW_PHASE_VARIANTS (no arguments = the defaults)."""
     if capsule_box not in NARROW_PHASE_VARIANTS["capsule_box"] or mpr not in NARROW_PHASE_VARIANTS["mpr"] or not 1 <= boxbox_max <= 8:
         raise ValueError("unknown narrow-phase variant")
-    L = lib()
-    L.rpo_debug_set_capsule_box(int(capsule_box))
-    L.rpo_debug_set_boxbox_max(int(boxbox_max))
+    for precision in sorted(set(_libs) | {64}):
+        lib(precision).rpo_debug_set_capsule_box(int(capsule_box))
+        lib(precision).rpo_debug_set_boxbox_max(int(boxbox_max))
     set_mpr_experiment(1e-10 if mpr == "tight" else 1e-6, mpr == "discrete", MPR_POLY_REFINED if mpr == "refined" else None)
 
 
@@ -149,11 +158,14 @@ def chaos_control(model, blob, ctrl_seq, nstep=1000, hold=10, seeds=(0, 1, 2), e
 
 
 class Oracle:
-    """One fp64 environment stepped by the CPU oracle."""
+    """One environment stepped by the CPU oracle: the fp64 reference, or with precision=32 its float32 restatement
+    (same interface; the views are float32 arrays, and the bench entry points are the fp64 library's only)."""
 
-    def __init__(self, model, blob: bytes):
+    def __init__(self, model, blob: bytes, precision: int = 64):
         self.m = model
-        self._L = lib()
+        self.precision = precision
+        self._L = lib(precision)
+        self._dtype = _REAL[precision][1]
         self._blob = blob
         self._model = self._L.rpo_model_load(blob, len(blob))
         if not self._model:
@@ -188,7 +200,7 @@ class Oracle:
         n = self._size(name)
         p = self._L.rpo_get_ptr(self._model, self._data, FIELDS[name])
         if n == 0:
-            return np.zeros(0)
+            return np.zeros(0, self._dtype)
         return np.ctypeslib.as_array(p, shape=(n,))
 
     def __getattr__(self, name):
@@ -231,6 +243,7 @@ class Oracle:
     def bench_seq(self, nenv, nstep, ctrl_seq, start, hold=10, nthreads=0):
         """Every env replays `ctrl_seq` [T, nu] from its own row start[e], one row per `hold` mj_steps.
         Returns (seconds, qpos[nenv, nv])."""
+        assert self.precision == 64, "the CPU baseline is the fp64 library's"
         out = np.zeros((nenv, self.m.nv))
         c = np.ascontiguousarray(ctrl_seq, np.float64)
         st = np.ascontiguousarray(start, np.int32)
@@ -241,6 +254,7 @@ class Oracle:
 
     def bench(self, nenv, nstep, ctrl=None, nthreads=0):
         """Returns (seconds, qpos[nenv, nv])."""
+        assert self.precision == 64, "the CPU baseline is the fp64 library's"
         out = np.zeros((nenv, self.m.nv))
         c = None
         if ctrl is not None:

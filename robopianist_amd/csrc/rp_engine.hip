@@ -1432,6 +1432,12 @@ int rp_dim(const rp_engine* e, const char* name) {
   if (!strcmp(name, "precision")) return b->precision;
   if (!strcmp(name, "rm_rows")) return b->rm_rows;
   if (!strcmp(name, "rm_cols")) return b->rm_cols;
+  // the capacities of this engine's build (RpCaps<T>): beyond them the position stage keeps the deepest contacts and
+  // raises RP_WARN_CONTACT_FULL; max_dense_rows is the size of the solver's dense cross-chain block (RP_WARN_DENSE_FULL)
+  const bool f32 = b->precision == 32;
+  if (!strcmp(name, "max_contacts")) return f32 ? RpCaps<float>::NC : RpCaps<double>::NC;
+  if (!strcmp(name, "max_entries")) return f32 ? RpCaps<float>::NE : RpCaps<double>::NE;
+  if (!strcmp(name, "max_dense_rows")) return f32 ? RpCaps<float>::HMAX : RpCaps<double>::HMAX;
   return -1;
 }
 int rp_kernel_time(rp_engine* e, double* avg_ms, int* n_launches) {

@@ -138,6 +138,11 @@ class BatchedPhysics:
             raise EngineError(self._L.rp_last_error().decode())
         self.nv = self.dim("nv"); self.nu = self.dim("nu"); self.nsite = self.dim("nsite")
         self.ntree = self.dim("ntree")
+        # this build's per-env capacities (fp64 64 / 640 / 60, fp32 32 / 240 / 56): contacts, contact Jacobian entries, rows of
+        # the solver's dense block.  Beyond the first two WARN_CONTACT_FULL is raised and the deepest contacts are kept;
+        # MAX_CONTACTS stays the width of CONTACT_DIST / CONTACT_GEOMS (slots from NCON on: 0 and (-1, -1))
+        self.max_contacts = self.dim("max_contacts"); self.max_entries = self.dim("max_entries")
+        self.max_dense_rows = self.dim("max_dense_rows")
         self._shapes = {
             QPOS: (self.nv,), QVEL: (self.nv,), QACC_WARMSTART: (self.nv,), CTRL: (self.nu,),
             QFRC_APPLIED: (self.nv,), ACT_FORCE: (self.nu,), ACT_VELOCITY: (self.nu,),

@@ -946,12 +946,22 @@ def test_capacity_overflow_ends_the_episode():
     the episode with reward 0 / discount 0 like a diverged state, on the fused path and on the torch hooks alike;
     by default the env steps on, as the reference's would (piano_with_shadow_hands.py:212-220 names the only
     termination causes), and the episode is counted in `overflow_episodes` when it ends."""
+    _capacity_overflow_ends_the_episode(64)
+
+
+def test_capacity_overflow_ends_the_episode_fp32():
+    """The same consequence on the fp32 build, whose capacities are the smaller ones (32 contacts / 240 entries:
+    tests/test_gpu_parity_fp32.py states when its position stage raises the flag)."""
+    _capacity_overflow_ends_the_episode(32)
+
+
+def _capacity_overflow_ends_the_episode(precision):
     from robopianist_amd import engine
-    fused, ref = _load_pair(4, 64, overflow_termination=True)
-    loose, _ = _load_pair(4, 64)
+    fused, ref = _load_pair(4, precision, overflow_termination=True)
+    loose, _ = _load_pair(4, precision)
     dev = fused.physics.device
     A = fused.action_spec().shape[0]
-    a = torch.zeros((4, A), device=dev, dtype=torch.float64)
+    a = torch.zeros((4, A), device=dev, dtype=fused.physics.dtype)
     for env in (fused, ref, loose):
         env.reset()
         env.step(a)

@@ -8,7 +8,12 @@ Two kinds of comparison:
   * teacher-forced: every physics step starts from the oracle's state, so the
     number is the per-step discrepancy of the implementation, free of the
     trajectory's own sensitivity.  Tolerances: fp64 1e-9, fp32 5e-3 relative to
-    the step's largest velocity change.
+    the step's largest velocity change.  The scenario functions here
+    (teacher_forced, pile_up, palm_flat, box_box_drive) take the engine's
+    precision; with an Fp32Record they also step the float32 restatement of
+    the oracle from the same states, and tests/test_gpu_parity_fp32.py holds
+    the fp32 engine's median and p90 to 8 x that restatement's error on
+    every kind of scene, and states the fp32 build's capacity rules.
   * free-running: the north-star statement "state matches within 1e-4 relative
     over 1000 steps on identical actions" (relative = |dq| / max(|q|, 1e-2)).
     Asserted for the fp64 engine on the scripted key-press scenario; the fp32
@@ -83,33 +88,136 @@ def wrist_press_sequence(si, nsteps):
 
 
 def make_pair(si, precision, nenv=2):
+    """(engine, fp64 oracle).  precision 64 / 32 picks the engine's build; None = no engine at all (the host tests of the
+    float32 restatement walk the same windows without a GPU): (None, oracle)."""
     from robopianist_amd import engine
     from oracle.rp_oracle import Oracle
+    if precision is None:
+        return None, Oracle(si.model, engine.make_blob(si.model, si.key_joint_ids))
     phys = engine.BatchedPhysics(si.model, si.key_joint_ids, n_envs=nenv, precision=precision)
     return phys, Oracle(si.model, phys.blob)
 
 
-def teacher_forced(si, precision, ctrl):
+# The fp32 engine's own floor of both MPR tolerances (rp_set_mpr_tolerance), and hence how far from the dist = 0 threshold
+# a contact may sit and still be seen by one side only; the fp64 comparisons allow rounding order alone.
+NEAR_THRESHOLD = {64: 1e-11, 32: 1e-6, None: 1e-6}
+FP32_WORST = 5e-3     # the fp32 contract: every step within 5e-3 of the step's largest velocity change
+FP32_MARGIN = 8.0     # ... and median / p90 within 8 x the float32 restatement's (the learner tests' margin)
+
+
+class Fp32Record:
+    """The float32 RESTATEMENT of the oracle (Oracle(precision=32): same formulae, every value and product a float32)
+    stepped beside an fp32 comparison: before every step it is given the fp64 oracle's state, and its result is compared
+    with the fp64 oracle's like the engine's.  Its error is what float32 costs a careful sequential implementation on the
+    same inputs, so the fp32 engine's bars are multiples of it -- no engine-measured number is a bar.  Holds, per compared
+    step, `eng` and `ref` (relative to the step's largest velocity change), and the conditions on the restatement itself
+    that tests/test_oracle_f32.py checks without a GPU: its warnings, Newton iterations and contact counts."""
+
+    def __init__(self, si):
+        from robopianist_amd import engine
+        from oracle.rp_oracle import Oracle
+        self.o32 = Oracle(si.model, engine.make_blob(si.model, si.key_joint_ids), precision=32)
+        self.bp0 = self.o32.body_pos.copy()
+        self.eng, self.ref, self.ref_all = [], [], []
+        self.iter_diff, self.ncon_diff, self.warnings, self.steps, self.flagged, self.maxcon = 0, 0, 0, 0, 0, 0
+        self.last = None
+
+    def restate(self, orc, q, v, w, c, body_pos=None):
+        """One step of the restatement from the state (q, v, warm start w, controls c) the fp64 oracle `orc` is about to
+        step from; call it BEFORE orc.step(1), then `compare` after."""
+        o = self.o32
+        o.body_pos[:] = self.bp0 if body_pos is None else body_pos
+        o.reset()                       # (clears its sticky warnings; the state is written next)
+        o.qpos[:] = q; o.qvel[:] = v; o.qacc_warmstart[:] = w; o.ctrl[:] = c
+        o.step1()
+        self._ncon0 = (o.ncon, orc.ncon)
+        o.step(1)
+
+    def compare(self, orc, v0):
+        o = self.o32
+        self.steps += 1
+        self.warnings |= int(o.warnings)
+        self.iter_diff = max(self.iter_diff, abs(int(o.solver_iter) - int(orc.solver_iter)))
+        self.ncon_diff += int(self._ncon0[0] != self._ncon0[1] or o.ncon != orc.ncon)
+        self.maxcon = max(self.maxcon, self._ncon0[1])
+        self.last = float(np.abs(o.qvel.astype(np.float64) - orc.qvel).max() / max(np.abs(orc.qvel - v0).max(), 1e-9))
+        self.ref_all.append(self.last)
+        return self.last
+
+    def engine_step(self, err):
+        """The engine's error on the step `compare` was last called for (steps left out as borderline are not passed)."""
+        self.eng.append(float(err)); self.ref.append(self.last)
+
+    def figures(self):
+        e, r = np.asarray(self.eng), np.asarray(self.ref)
+        return {"steps": len(e), "engine": (float(e.max()), float(np.median(e)), float(np.percentile(e, 90))),
+                "restatement": (float(r.max()), float(np.median(r)), float(np.percentile(r, 90)))}
+
+    def assert_bars(self, name):
+        """Section-2 bars: worst < 5e-3 (the documented contract), median and 90th percentile <= 8 x the restatement's on
+        the same steps.  Prints both sides first."""
+        f = self.figures()
+        print("fp32 %-34s %4d steps  engine worst/median/p90 %.2e %.2e %.2e | restatement %.2e %.2e %.2e | ratio median %.2f p90 %.2f"
+              % ((name, f["steps"]) + f["engine"] + f["restatement"] +
+                 (f["engine"][1] / max(f["restatement"][1], 1e-30), f["engine"][2] / max(f["restatement"][2], 1e-30))))
+        assert f["steps"] >= 10, (name, f["steps"])
+        assert f["engine"][0] < FP32_WORST, (name, f)
+        assert f["engine"][1] <= FP32_MARGIN * f["restatement"][1], (name, "median", f)
+        assert f["engine"][2] <= FP32_MARGIN * f["restatement"][2], (name, "p90", f)
+        return f
+
+    def assert_restatement_is_sound(self, name):
+        """The conditions on the reference alone (checked on the host for every window the GPU tests use)."""
+        assert self.warnings == 0, (name, "restatement warnings", self.warnings)
+        assert self.iter_diff <= 2, (name, "Newton iterations differ by", self.iter_diff)
+        assert self.ncon_diff <= 2, (name, "steps with another contact count", self.ncon_diff)
+
+
+def _geom_pairs_engine(phys, n):
     from robopianist_amd import engine
-    phys, orc = make_pair(si, precision)
+    return sorted((min(int(a), int(b)), max(int(a), int(b))) for a, b in phys.get(engine.CONTACT_GEOMS)[0][:n])   # (a key's pair is (hand geom, key))
+
+
+def _geom_pairs_oracle(orc):
+    return sorted((min(int(c[13]), int(c[14])), max(int(c[13]), int(c[14]))) for c in orc.contact.reshape(-1, 16))
+
+
+def teacher_forced(si, precision, ctrl, record=None):
+    """Every step restarts from the fp64 oracle's state.  `precision`: the engine build (64 / 32), or None for no engine.
+    `record` (Fp32Record): the float32 restatement steps along and the per-step figures of both are kept in it; with it
+    the geom pairs of the contacts are compared too, not only their number.  Returns (worst rel dv, max contacts)."""
+    from robopianist_amd import engine
+    phys, orc = make_pair(si, precision, 2 if record is None else 1)
+    near = NEAR_THRESHOLD[precision]
     worst, maxcon, borderline = 0.0, 0, 0
     for c in ctrl:
-        phys.set(engine.QPOS, orc.qpos[None, :])
-        phys.set(engine.QVEL, orc.qvel[None, :])
-        phys.set(engine.QACC_WARMSTART, orc.qacc_warmstart[None, :])
-        phys.set(engine.CTRL, c[None, :])
+        if phys is not None:
+            phys.set(engine.QPOS, orc.qpos[None, :])
+            phys.set(engine.QVEL, orc.qvel[None, :])
+            phys.set(engine.QACC_WARMSTART, orc.qacc_warmstart[None, :])
+            phys.set(engine.CTRL, c[None, :])
+        if record is not None:
+            record.restate(orc, orc.qpos, orc.qvel, orc.qacc_warmstart, c)
         orc.ctrl[:] = c
         v0 = orc.qvel.copy()
-        phys.step(1)
+        if phys is not None:
+            phys.step(1)
         orc.step(1)
+        maxcon = max(maxcon, orc.ncon)
+        if record is not None:
+            record.compare(orc, v0)
+        if phys is None:
+            continue
         ne = int(phys.get(engine.NCON)[0])
         assert phys.warn_flags.max() == 0, f"engine capacity / state flag {int(phys.warn_flags.max())} raised"
+        if record is not None and ne == orc.ncon:
+            assert _geom_pairs_engine(phys, ne) == _geom_pairs_oracle(orc), "same number of contacts on other geom pairs"
         if ne != orc.ncon:
             # a contact sitting exactly on the dist = 0 threshold may be seen by one side only
-            # (rounding order); anything else is a real narrow-phase disagreement
+            # (rounding order; fp32: the MPR floor); anything else is a real narrow-phase disagreement
             d_e = np.abs(phys.get(engine.CONTACT_DIST)[0][:ne].astype(np.float64))
             d_o = np.abs(orc.contact.reshape(-1, 16)[:, 0])
-            on_threshold = int((d_e < 1e-11).sum() + (d_o < 1e-11).sum())
+            on_threshold = int((d_e < near).sum() + (d_o < near).sum())
             if on_threshold < abs(ne - orc.ncon):
                 gm = si.model.names["geom"]
                 ce = phys.get(engine.CONTACT_GEOMS)[0][:ne]
@@ -120,13 +228,13 @@ def teacher_forced(si, precision, ctrl):
                 raise AssertionError(f"contact sets differ: engine-only {sorted(set(pe) - set(po))}, "
                                      f"oracle-only {sorted(set(po) - set(pe))}")
             borderline += 1
-            maxcon = max(maxcon, orc.ncon)
             continue
         dv = np.abs(phys.qvel[0].astype(np.float64) - orc.qvel).max()
         worst = max(worst, dv / max(np.abs(orc.qvel - v0).max(), 1e-9))
-        maxcon = max(maxcon, orc.ncon)
+        if record is not None:
+            record.engine_step(dv / max(np.abs(orc.qvel - v0).max(), 1e-9))
     assert borderline <= 2, borderline
-    assert phys.warn_flags.max() == 0 and orc.warnings == 0
+    assert (phys is None or phys.warn_flags.max() == 0) and orc.warnings == 0
     return worst, maxcon
 
 
@@ -840,12 +948,11 @@ def test_joints_torque_and_fingertip_force_observables():
     assert force > 0.0, "curled fingers must press on the keys"
 
 
-def test_teacher_forced_fp64_with_box_box_contacts(two_hand_scene):
-    """Box-box narrow phase (forearm box on the own palm's boxes, palm on palm when the hands are
-    driven into each other) in the engine against the oracle: same contact counts, 1e-9 per step."""
+def box_box_drive(si, precision, record=None, nsteps=360):
+    """The hands driven against their own forearms and into each other: box-box pairs (forearm box on the own palm's boxes,
+    palm on palm), teacher forced.  Returns (worst rel dv, box-box contacts seen, max contacts, warn flags)."""
     from robopianist_amd import engine
     from robopianist_amd.model import spec
-    si = two_hand_scene
     m = si.model
     names = m.names["actuator"]
     lo, hi = m.actuator_ctrlrange[:, 0], m.actuator_ctrlrange[:, 1]
@@ -862,24 +969,47 @@ def test_teacher_forced_fp64_with_box_box_contacts(two_hand_scene):
             elif s.endswith("WRJ2") or s.endswith("WRJ1"):
                 c[a] = np.clip(wr * (1 if n.startswith("rh") else -1), lo[a], hi[a])
         return c
-    phases = [ctrl_for(-0.3, 0.0, 0.0)] * 120 + [ctrl_for(-0.15, 0.15, 0.4)] * 120 + [ctrl_for(-0.05, 0.25, -0.3)] * 120
-    phys, orc = make_pair(si, 64)
+    third = nsteps // 3
+    phases = [ctrl_for(-0.3, 0.0, 0.0)] * third + [ctrl_for(-0.15, 0.15, 0.4)] * third + [ctrl_for(-0.05, 0.25, -0.3)] * third
+    phys, orc = make_pair(si, precision, 2 if record is None else 1)
     worst, boxbox, maxcon = 0.0, 0, 0
     for c in phases:
         c = np.clip(c + rng.normal(0, 0.02, m.nu) * (hi - lo), lo, hi)
-        phys.set(engine.QPOS, orc.qpos[None, :]); phys.set(engine.QVEL, orc.qvel[None, :])
-        phys.set(engine.QACC_WARMSTART, orc.qacc_warmstart[None, :])
-        phys.set(engine.CTRL, c[None, :]); orc.ctrl[:] = c
+        if phys is not None:
+            phys.set(engine.QPOS, orc.qpos[None, :]); phys.set(engine.QVEL, orc.qvel[None, :])
+            phys.set(engine.QACC_WARMSTART, orc.qacc_warmstart[None, :])
+            phys.set(engine.CTRL, c[None, :])
+        if record is not None:
+            record.restate(orc, orc.qpos, orc.qvel, orc.qacc_warmstart, c)
+        orc.ctrl[:] = c
         v0 = orc.qvel.copy()
-        phys.step(1); orc.step(1)
-        dv = np.abs(phys.qvel[0].astype(np.float64) - orc.qvel).max()
-        worst = max(worst, dv / max(np.abs(orc.qvel - v0).max(), 1e-9))
-        assert phys.get(engine.NCON)[0] == orc.ncon
+        if phys is not None:
+            phys.step(1)
+        orc.step(1)
         con = orc.contact.reshape(-1, 16)
         boxbox += sum(1 for cc in con if m.geom_type[int(cc[13])] == spec.GEOM_BOX and m.geom_type[int(cc[14])] == spec.GEOM_BOX)
         maxcon = max(maxcon, orc.ncon)
-    print(f"box-box: {boxbox} box-box contacts over {len(phases)} steps, max contacts {maxcon}, worst rel dv {worst:.2e}")
-    assert boxbox >= 50 and (phys.warn_flags.max() & ~engine.WARN_CONTACT_FULL) == 0
+        if record is not None:
+            record.compare(orc, v0)
+        if phys is None:
+            continue
+        dv = np.abs(phys.qvel[0].astype(np.float64) - orc.qvel).max()
+        worst = max(worst, dv / max(np.abs(orc.qvel - v0).max(), 1e-9))
+        ne = int(phys.get(engine.NCON)[0])
+        assert ne == orc.ncon
+        if record is not None:
+            assert _geom_pairs_engine(phys, ne) == _geom_pairs_oracle(orc)
+            record.engine_step(dv / max(np.abs(orc.qvel - v0).max(), 1e-9))
+    return worst, boxbox, maxcon, 0 if phys is None else int(phys.warn_flags.max())
+
+
+def test_teacher_forced_fp64_with_box_box_contacts(two_hand_scene):
+    """Box-box narrow phase (forearm box on the own palm's boxes, palm on palm when the hands are
+    driven into each other) in the engine against the oracle: same contact counts, 1e-9 per step."""
+    from robopianist_amd import engine
+    worst, boxbox, maxcon, flags = box_box_drive(two_hand_scene, 64)
+    print(f"box-box: {boxbox} box-box contacts over 360 steps, max contacts {maxcon}, worst rel dv {worst:.2e}")
+    assert boxbox >= 50 and (flags & ~engine.WARN_CONTACT_FULL) == 0
     assert worst < 1e-9
 
 
@@ -901,7 +1031,7 @@ def test_teacher_forced_fp64_large_hull_colliders():
     assert worst < 1e-9
 
 
-def pile_up(si, nsteps=120, seed=3, lo_dx=0.083, hi_dx=0.098, stable_only=False, stats=None):
+def pile_up(si, nsteps=120, seed=3, lo_dx=0.083, hi_dx=0.098, stable_only=False, stats=None, precision=64, record=None):
     """Teacher-forced steps from hand-IN-hand poses: both forearms shifted towards each other until the hands
     interpenetrate (30 ... 64 contacts, most of them hand-hand, i.e. ~14 Jacobian entries each and one large dense
     block), fingers at random postures.  Returns (worst rel dv, max contacts, max entries, steps beyond 32 contacts).
@@ -910,13 +1040,26 @@ def pile_up(si, nsteps=120, seed=3, lo_dx=0.083, hi_dx=0.098, stable_only=False,
     the plane of its caps [MJ: mjc_support: sign(dir_z) * half height], so the portal refinement of a thin disc deep
     inside a hull has rounding-decided branches: the oracle started 1e-13 away returns depths up to 4e-5 apart on ~12 %
     of these poses -- as does the engine.  That is MuJoCo's algorithm, not a difference between implementations.
-    `stats` (dict): filled with the contact counts by geom-type pair and the number of poses skipped as unstable."""
+    `stats` (dict): filled with the contact counts by geom-type pair and the number of poses skipped as unstable.
+    `precision` 32 with a `record` (Fp32Record) states the fp32 build's CAPACITY RULES instead of skipping by a predicted
+    capacity: a pose whose two position stages stay within dim("max_contacts") contacts in the oracle and whose entry
+    upper bound stays within dim("max_entries") raises no flag; a pose that raises no flag is compared like any other step
+    (capacity is never lost silently); a flagged pose must be RP_WARN_CONTACT_FULL alone, beyond one of the two
+    capacities, and finite.  stats["unflagged_over_8"] / stats["flagged"] count the two sides.  precision None: no engine."""
     from robopianist_amd import engine
     from robopianist_amd.model import spec
     m = si.model
     jn = m.names["joint"]
     rng = np.random.default_rng(seed)
-    phys, orc = make_pair(si, 64)
+    phys, orc = make_pair(si, precision, 2 if record is None else 1)
+    if precision == 64:
+        cap_con, cap_ent = engine.MAX_CONTACTS, 600   # (entries: an upper bound is compared, so a little under the 640)
+    elif phys is not None:
+        cap_con, cap_ent = phys.dim("max_contacts"), phys.dim("max_entries")
+    else:   # (the host walk of an fp32 window: the fp32 build's capacities, as include/rp_engine.h states them)
+        cap_con, cap_ent = 32, 240
+    # stable_only: the size of the perturbation a second implementation's rounding makes, and the depth it may move
+    eps_q, eps_d = (1e-13, 1e-9) if precision == 64 else (1e-7, 1e-6)
     lo, hi = m.actuator_ctrlrange[:, 0], m.actuator_ctrlrange[:, 1]
     nanc = np.zeros(m.nbody, int)
     for b in range(1, m.nbody):
@@ -956,30 +1099,72 @@ def pile_up(si, nsteps=120, seed=3, lo_dx=0.083, hi_dx=0.098, stable_only=False,
         if stable_only:
             if "orc2" not in locals():
                 from oracle.rp_oracle import Oracle
-                orc2 = Oracle(m, phys.blob)
+                orc2 = Oracle(m, engine.make_blob(m, si.key_joint_ids))
             d0 = sorted((int(x[13]), int(x[14]), float(x[0])) for x in orc.contact.reshape(-1, 16))
             for _ in range(10):   # (a rounding-decided branch goes either way about half of the time)
                 orc2.reset()
-                orc2.qpos[:] = q + 1e-13 * rng.standard_normal(m.nv); orc2.qvel[:] = v; orc2.qacc_warmstart[:] = 0; orc2.ctrl[:] = c
+                orc2.qpos[:] = q + eps_q * rng.standard_normal(m.nv); orc2.qvel[:] = v; orc2.qacc_warmstart[:] = 0; orc2.ctrl[:] = c
                 orc2.forward()
                 d1 = sorted((int(x[13]), int(x[14]), float(x[0])) for x in orc2.contact.reshape(-1, 16))
-                if len(d0) != len(d1) or any(a[:2] != b[:2] or abs(a[2] - b[2]) > 1e-9 for a, b in zip(d0, d1)):
+                if len(d0) != len(d1) or any(a[:2] != b[:2] or abs(a[2] - b[2]) > eps_d for a, b in zip(d0, d1)):
                     if stats is not None:
                         stats["unstable"] = stats.get("unstable", 0) + 1
                     degenerate = True
                     break
-        phys.reset()   # (clears the sticky warn flags of an iteration that was beyond the capacity)
-        phys.set(engine.QPOS, q[None, :]); phys.set(engine.QVEL, v[None, :])
-        phys.set(engine.QACC_WARMSTART, w[None, :]); phys.set(engine.CTRL, c[None, :])
+        if phys is not None:
+            phys.reset()   # (clears the sticky warn flags of an iteration that was beyond the capacity)
+            phys.set(engine.QPOS, q[None, :]); phys.set(engine.QVEL, v[None, :])
+            phys.set(engine.QACC_WARMSTART, w[None, :]); phys.set(engine.CTRL, c[None, :])
+        if record is not None:
+            record.restate(orc, q, v, w, c)
         v0 = orc.qvel.copy()
-        phys.step(1); orc.step(1)
+        if phys is not None:
+            phys.step(1)
+        orc.step(1)
         con = orc.contact.reshape(-1, 16)
         ne = entries()
-        if max(ncon0, orc.ncon) > engine.MAX_CONTACTS or max(ne0, ne) > 600:
+        within = max(ncon0, orc.ncon) <= cap_con and max(ne0, ne) <= cap_ent
+        if record is not None:   # (what the oracle alone promises about this pose: see the capacity rules above)
+            stats["within_over_8"] = stats.get("within_over_8", 0) + int(within and max(ncon0, orc.ncon) > 8 and not degenerate and not axis_in_box())
+            stats["beyond_contacts"] = stats.get("beyond_contacts", 0) + int(max(ncon0, orc.ncon) > cap_con)
+        if record is not None and phys is not None:
+            flag = int(phys.warn_flags.max())
+            assert flag or max(ncon0, orc.ncon) <= cap_con, f"{max(ncon0, orc.ncon)} contacts in the oracle and no flag"
+            if flag:
+                assert flag == engine.WARN_CONTACT_FULL, flag
+                assert not within, f"flag within the capacity: contacts {ncon0} -> {orc.ncon}, entries <= {max(ne0, ne)}"
+                assert np.isfinite(phys.qpos).all() and np.isfinite(phys.qvel).all()
+                assert int(phys.get(engine.NCON)[0]) <= cap_con
+                stats["flagged"] = stats.get("flagged", 0) + 1
+                continue
+        elif not within:
             continue   # (beyond the engine's capacity: covered by the overflow tests)
         if degenerate or axis_in_box():
             continue
+        if record is not None and (phys is None or within):
+            # (the restatement is held to its soundness conditions on the poses the capacity rule promises to be
+            # compared; an unflagged pose beyond the predicted capacity is compared as well, for the engine's bars)
+            record.compare(orc, v0)
+        if phys is None:
+            maxcon = max(maxcon, ncon0, orc.ncon); maxent = max(maxent, ne0, ne)
+            if stats is not None:
+                stats["compared"] = stats.get("compared", 0) + 1
+                for x in con:
+                    k = (int(m.geom_type[int(x[13])]), int(m.geom_type[int(x[14])]))
+                    stats[k] = stats.get(k, 0) + 1
+            continue
+        if record is not None and not within:
+            record.last = float(np.abs(record.o32.qvel.astype(np.float64) - orc.qvel).max() / max(np.abs(orc.qvel - v0).max(), 1e-9))
         ne_ = int(phys.get(engine.NCON)[0])
+        if ne_ != orc.ncon and record is not None:
+            # fp32: a contact within the MPR floor of the dist = 0 threshold may be seen by one side only (teacher_forced's
+            # allowance, at most two poses)
+            d_e = np.abs(phys.get(engine.CONTACT_DIST)[0][:ne_].astype(np.float64))
+            if int((d_e < NEAR_THRESHOLD[32]).sum() + (np.abs(con[:, 0]) < NEAR_THRESHOLD[32]).sum()) >= abs(ne_ - orc.ncon):
+                assert phys.warn_flags.max() == 0
+                stats["borderline"] = stats.get("borderline", 0) + 1
+                assert stats["borderline"] <= 2
+                continue
         if ne_ != orc.ncon:
             gm = m.names["geom"]
             ce = phys.get(engine.CONTACT_GEOMS)[0][:ne_]
@@ -991,6 +1176,11 @@ def pile_up(si, nsteps=120, seed=3, lo_dx=0.083, hi_dx=0.098, stable_only=False,
         assert phys.warn_flags.max() == 0, int(phys.warn_flags.max())
         dv = np.abs(phys.qvel[0].astype(np.float64) - orc.qvel).max()
         worst = max(worst, dv / max(np.abs(orc.qvel - v0).max(), 1e-9))
+        if record is not None:
+            assert _geom_pairs_engine(phys, ne_) == _geom_pairs_oracle(orc)
+            record.engine_step(dv / max(np.abs(orc.qvel - v0).max(), 1e-9))
+            if max(ncon0, orc.ncon) > 8:
+                stats["unflagged_over_8"] = stats.get("unflagged_over_8", 0) + 1
         if os.environ.get("RP_PILEUP_VERBOSE"):
             print(f"  pile-up step {it}: contacts {ncon0} -> {orc.ncon}, entries <= {ne0}, solver_iter {orc.solver_iter} / "
                   f"{int(phys.get(engine.SOLVER_ITER)[0]) & 255}, rel dv {dv / max(np.abs(orc.qvel - v0).max(), 1e-9):.2e}")
@@ -1013,7 +1203,7 @@ def test_teacher_forced_fp64_pile_up_beyond_32_contacts(two_hand_scene):
     assert worst < 1e-9
 
 
-def palm_flat(si, nsteps=30, seed=5):
+def palm_flat(si, nsteps=30, seed=5, precision=64, record=None, dz_range=(0.0965, 0.1005)):
     """Teacher-forced steps with the right hand lowered until its palm boxes lie on the keys (rp_set(RP_TREE_OFFSET)
     / the oracle's body_pos): box-box pairs resting face to face -- four to eight points per pair -- with the wrist
     yawed and tilted a little so that the incident face is clipped by the reference rectangle.  Returns (worst rel
@@ -1024,15 +1214,16 @@ def palm_flat(si, nsteps=30, seed=5):
     m = si.model
     jn, bn = m.names["joint"], m.names["body"]
     rng = np.random.default_rng(seed)
-    phys, orc = make_pair(si, 64)
+    phys, orc = make_pair(si, precision, 2 if record is None else 1)
+    cap_con = engine.MAX_CONTACTS if precision == 64 else (32 if phys is None else phys.dim("max_contacts"))
     root = [i for i, n in enumerate(bn) if m.body_parentid[i] == 0 and n.startswith("rh_shadow_hand")][0]
     bp0 = orc.body_pos.copy()
     lo, hi = m.actuator_ctrlrange[:, 0], m.actuator_ctrlrange[:, 1]
-    ntree = phys.dim("ntree")
+    ntree = 1 if phys is None else phys.dim("ntree")
     worst, maxcon, pairs, most = 0.0, 0, 0, 0
     try:
         for it in range(nsteps):
-            dz = rng.uniform(0.0965, 0.1005)
+            dz = rng.uniform(*dz_range)
             orc.body_pos[:] = bp0; orc.body_pos[3 * root + 2] -= dz
             orc.reset()
             q = orc.qpos.copy()
@@ -1052,18 +1243,29 @@ def palm_flat(si, nsteps=30, seed=5):
             con0 = orc.contact.reshape(-1, 16).copy()
             off = np.zeros((1, ntree, 3))
             off[0, 0, 2] = -dz   # (tree 0 = the right hand: the first hand of the scene)
-            phys.reset()
-            phys.set(engine.TREE_OFFSET, off)
-            phys.set(engine.QPOS, q[None, :]); phys.set(engine.QVEL, v[None, :])
-            phys.set(engine.QACC_WARMSTART, w[None, :]); phys.set(engine.CTRL, c[None, :])
+            if phys is not None:
+                phys.reset()
+                phys.set(engine.TREE_OFFSET, off)
+                phys.set(engine.QPOS, q[None, :]); phys.set(engine.QVEL, v[None, :])
+                phys.set(engine.QACC_WARMSTART, w[None, :]); phys.set(engine.CTRL, c[None, :])
+            if record is not None:
+                record.restate(orc, q, v, w, c, body_pos=orc.body_pos)
             v0 = orc.qvel.copy()
-            phys.step(1); orc.step(1)
-            if max(len(con0), orc.ncon) > engine.MAX_CONTACTS:
+            if phys is not None:
+                phys.step(1)
+            orc.step(1)
+            if max(len(con0), orc.ncon) > cap_con:
                 continue
-            assert int(phys.get(engine.NCON)[0]) == orc.ncon, (int(phys.get(engine.NCON)[0]), orc.ncon)
-            assert phys.warn_flags.max() == 0, int(phys.warn_flags.max())
-            dv = np.abs(phys.qvel[0].astype(np.float64) - orc.qvel).max()
-            worst = max(worst, dv / max(np.abs(orc.qvel - v0).max(), 1e-9))
+            if record is not None:
+                record.compare(orc, v0)
+            if phys is not None:
+                assert int(phys.get(engine.NCON)[0]) == orc.ncon, (int(phys.get(engine.NCON)[0]), orc.ncon)
+                assert phys.warn_flags.max() == 0, int(phys.warn_flags.max())
+                dv = np.abs(phys.qvel[0].astype(np.float64) - orc.qvel).max()
+                worst = max(worst, dv / max(np.abs(orc.qvel - v0).max(), 1e-9))
+                if record is not None:
+                    assert _geom_pairs_engine(phys, orc.ncon) == _geom_pairs_oracle(orc)
+                    record.engine_step(dv / max(np.abs(orc.qvel - v0).max(), 1e-9))
             bb = Counter((int(x[13]), int(x[14])) for x in con0
                          if m.geom_type[int(x[13])] == spec.GEOM_BOX and m.geom_type[int(x[14])] == spec.GEOM_BOX)
             pairs += sum(1 for n_ in bb.values() if n_ > 3); most = max([most] + list(bb.values()))

@@ -163,6 +163,26 @@ def test_impratio_and_cylinder_colliders_on_the_wave_emulator(wavesim_lib):
     assert compared >= 10 and cyl >= 8 and worst < 1e-9, (worst, compared, cyl)
 
 
+@pytest.mark.parametrize("kind,n,scene", [
+    ("replay", 40, dict(primitive_fingertip_collisions=False)),                                            # hulls: MESH = 1
+    ("cylinder", 40, dict(primitive_fingertip_collisions=False, cylinder_colliders=True, impratio=10.0)),  # MESH = 2
+    ("palm", 24, None),                                                                                    # box-box, 4-8 points
+    ("capacity", 36, None),                                                                                # 32 contacts / 240 entries
+])
+def test_fp32_scenes_on_the_wave_emulator(wavesim_lib, kind, n, scene):
+    """The fp32 build (Engine<float>: its own position stage, capacities and WIDE dense step) without a GPU: short windows of
+    the scenes of tests/test_gpu_parity_fp32.py, each held to that module's bars inside the scenario function -- worst
+    step < 5e-3, median and p90 within 8 x the float32 restatement of the oracle, equal geom pairs, and the capacity rules
+    (no flag within the capacity, parity without a flag, RP_WARN_CONTACT_FULL alone beyond it)."""
+    r = _run_parity_fn(wavesim_lib, "short_window", kind, n, module="test_gpu_parity_fp32", scene=scene)
+    steps, maxcon, flagged, unflagged = int(r[0]), int(r[1]), int(r[8]), int(r[9])
+    assert steps >= 10, r
+    if kind == "replay":
+        assert maxcon >= 4, r
+    if kind == "capacity":
+        assert flagged >= 4 and unflagged >= 4, r
+
+
 LAUNCH_TRACE_GROUPS = ("prim64", "hull64", "graph64", "deep64", "prim32", "short64", "sizes", "executed")
 
 
