@@ -30,19 +30,37 @@ from robopianist_amd.wrappers import (AudioObservationWrapper, CanonicalSpecWrap
                                       MidiEvaluationWrapper, PianoSoundVideoWrapper, PianoSoundWrapper, PixelWrapper)
 
 
+def _task_kwargs(args):
+    return dict(
+        change_color_on_activation=True, trim_silence=args.trim_silence,
+        control_timestep=args.control_timestep, gravity_compensation=args.gravity_compensation,
+        primitive_fingertip_collisions=args.primitive_fingertip_collisions,
+        reduced_action_space=args.reduced_action_space, n_steps_lookahead=args.n_steps_lookahead,
+        disable_fingering_reward=args.disable_fingering_reward,
+        disable_forearm_reward=args.disable_forearm_reward,
+        disable_colorization=args.disable_colorization,
+        disable_hand_collisions=args.disable_hand_collisions, attachment_yaw=args.attachment_yaw)
+
+
 def _load(args, n_envs):
     return suite.load(
         environment_name=args.env_name, midi_file=args.midi_file, stretch=args.stretch, shift=args.shift,
         seed=args.seed, n_envs=n_envs, precision=args.precision, record_key_trace=args.record or args.hear,
-        task_kwargs=dict(
-            change_color_on_activation=True, trim_silence=args.trim_silence,
-            control_timestep=args.control_timestep, gravity_compensation=args.gravity_compensation,
-            primitive_fingertip_collisions=args.primitive_fingertip_collisions,
-            reduced_action_space=args.reduced_action_space, n_steps_lookahead=args.n_steps_lookahead,
-            disable_fingering_reward=args.disable_fingering_reward,
-            disable_forearm_reward=args.disable_forearm_reward,
-            disable_colorization=args.disable_colorization,
-            disable_hand_collisions=args.disable_hand_collisions, attachment_yaw=args.attachment_yaw))
+        task_kwargs=_task_kwargs(args))
+
+
+def _load_members(args, n_envs, names):
+    """As `_load` with the task's `midi=[one song per name]`: env e plays song e % len(names)."""
+    from robopianist_amd import music
+    from robopianist_amd.suite import environment
+    from robopianist_amd.suite.tasks import piano_with_shadow_hands
+    songs = dict(zip(suite.ALL, list(music.PIG_MIDIS) + list(music.ETUDE_MIDIS) + list(music.DEBUG_MIDIS)))
+    for name in names:
+        if name not in songs:
+            raise ValueError(f"Unknown environment {name}. Available environments: {suite.ALL}")
+    midis = [music.load(songs[name], stretch=args.stretch, shift=args.shift) for name in names]
+    task = piano_with_shadow_hands.PianoWithShadowHands(midi=midis, **_task_kwargs(args))
+    return environment.Environment(task, n_envs=n_envs, random_state=args.seed, precision=args.precision)
 
 
 def main() -> None:
@@ -99,8 +117,15 @@ def main() -> None:
     ap.add_argument("--train-droq", type=int, default=0, metavar="ROUNDS",
                     help="train a policy with droq.DroQ for that many rounds (16 control steps and one actor step of 20 "
                          "critic steps each) instead; prints the same lines and the F1 of the trained policy at the end")
+    ap.add_argument("--train-population", type=int, default=0, metavar="ROUNDS",
+                    help="train --members independent DroQ learners (population.DroQPopulation; member p owns the envs "
+                         "e %% members == p) for that many rounds instead; prints the same lines and the F1, per member")
+    ap.add_argument("--members", type=int, default=8, help="--train-population: the number of members (divides --n_envs)")
+    ap.add_argument("--member-envs", dest="member_envs", default=None, metavar="NAME[,NAME...]",
+                    help="--train-population: environment names of suite.ALL, one (every member learns that song) or "
+                         "--members of them (member p learns song p); default: --env_name")
     ap.add_argument("--time-limit", type=float, default=None,
-                    help="--train-ppo, --train-sac, --train-droq: stop after that many seconds")
+                    help="--train-ppo, --train-sac, --train-droq, --train-population: stop after that many seconds")
     args = ap.parse_args()
     if args.video and not args.record:
         ap.error("--video needs --record")
@@ -116,8 +141,22 @@ def main() -> None:
             warnings.simplefilter("ignore")
             return _load(args, n_envs)
 
-    if (args.train_ppo > 0) + (args.train_sac > 0) + (args.train_droq > 0) > 1:
-        ap.error("--train-ppo, --train-sac and --train-droq are three learners: choose one")
+    if (args.train_ppo > 0) + (args.train_sac > 0) + (args.train_droq > 0) + (args.train_population > 0) > 1:
+        ap.error("--train-ppo, --train-sac, --train-droq and --train-population are four learners: choose one")
+    if args.train_population > 0:
+        if (args.fingertip_pianist or args.plan or args.action_sequence or args.pixels or args.hear or args.record
+                or args.canonicalize):
+            ap.error("--train-population trains on the plain environment: it goes with the task flags only")
+        names = [n for n in (args.member_envs or args.env_name).split(",") if n]
+        if len(names) not in (1, args.members):
+            ap.error(f"--member-envs takes one name or --members = {args.members} names, got {len(names)}")
+        from robopianist_amd import population
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            env = _load_members(args, args.n_envs, names)
+        population.train_and_evaluate(env, args.train_population, args.members, time_limit=args.time_limit, seed=args.seed,
+                                      batch_size=max(1, min(4096, 16 * args.n_envs) // args.members))
+        return
     if args.train_droq > 0:
         if (args.fingertip_pianist or args.plan or args.action_sequence or args.pixels or args.hear or args.record
                 or args.canonicalize):

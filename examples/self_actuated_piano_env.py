@@ -31,13 +31,17 @@ def main() -> None:
     ap.add_argument("--train-droq", type=int, default=0, metavar="ROUNDS",
                     help="train a policy with droq.DroQ for that many rounds (16 control steps and one actor step of 20 "
                          "critic steps each) instead; prints the same lines and the F1 of the trained policy at the end")
+    ap.add_argument("--train-population", type=int, default=0, metavar="ROUNDS",
+                    help="train --members independent DroQ learners (population.DroQPopulation; member p owns the envs "
+                         "e %% members == p) for that many rounds instead; prints the same lines and the F1, per member")
+    ap.add_argument("--members", type=int, default=8, help="--train-population: the number of members (divides --n_envs)")
     ap.add_argument("--time-limit", type=float, default=None,
-                    help="--train-ppo, --train-sac, --train-droq: stop after that many seconds")
+                    help="--train-ppo, --train-sac, --train-droq, --train-population: stop after that many seconds")
     args = ap.parse_args()
-    if (args.train_ppo > 0) + (args.train_sac > 0) + (args.train_droq > 0) > 1:
-        ap.error("--train-ppo, --train-sac and --train-droq are three learners: choose one")
-    if args.train_ppo > 0 or args.train_sac > 0 or args.train_droq > 0:
-        from robopianist_amd import droq, learning, offpolicy
+    if (args.train_ppo > 0) + (args.train_sac > 0) + (args.train_droq > 0) + (args.train_population > 0) > 1:
+        ap.error("--train-ppo, --train-sac, --train-droq and --train-population are four learners: choose one")
+    if args.train_ppo > 0 or args.train_sac > 0 or args.train_droq > 0 or args.train_population > 0:
+        from robopianist_amd import droq, learning, offpolicy, population
         with warnings.catch_warnings():
             warnings.simplefilter("ignore")
             task = SelfActuatedPiano(midi=music.load(args.midi), n_steps_lookahead=1,
@@ -49,6 +53,9 @@ def main() -> None:
         elif args.train_droq > 0:
             droq.train_and_evaluate(env, args.train_droq, time_limit=args.time_limit,
                                     batch_size=min(4096, 16 * args.n_envs))
+        elif args.train_population > 0:
+            population.train_and_evaluate(env, args.train_population, args.members, time_limit=args.time_limit,
+                                          batch_size=max(1, min(4096, 16 * args.n_envs) // args.members))
         else:
             learning.train_and_evaluate(env, args.train_ppo, time_limit=args.time_limit)
         return

@@ -1,5 +1,5 @@
-"""What the ctypes bindings of the HIP libraries share: the library opener (all ten bindings) and the entry table of the
-libraries whose entry points take one argument block each (planning, learning, offpolicy, droq)."""
+"""What the ctypes bindings of the HIP libraries share: the library opener (all eleven bindings) and the entry table of the
+libraries whose entry points take one argument block each (planning, learning, offpolicy, droq, population)."""
 
 from __future__ import annotations
 

@@ -20,6 +20,7 @@
 //   rp_learn_gae_kernel      one thread per env, backwards over the slots, float64.
 //   rp_learn_moments_kernel  grid (column block of 16): 16 columns x 16 partial sums per workgroup, two passes (sum, then
 //                            squared deviations), lanes reduced through LDS in ascending order, merged by Chan's formula.
+//                            Its body is rpl_moments_block of rp_learn.hpp, which librp_pop.so runs per member too.
 #include <hip/hip_runtime.h>
 
 #include <math.h>
@@ -240,54 +241,10 @@ __global__ __launch_bounds__(RPL_BLOCK) void rp_learn_gae_kernel(const rp_learn_
 }
 
 // ---- moments ---------------------------------------------------------------------------------------------------------
-__device__ inline double rpl_lane_sum(double mine, double (*part)[RPL_MOMENT_COLS], int col, int l) {
-  __syncthreads();   // (the previous reduction's reads)
-  part[l][col] = mine;
-  __syncthreads();
-  double s = part[0][col];
-  for (int i = 1; i < RPL_MOMENT_LANES; i++) s = s + part[i][col];
-  return s;
-}
-
+// The body is rp_learn.hpp's, on the identity map.
 __global__ __launch_bounds__(RPL_MOMENT_COLS * RPL_MOMENT_LANES) void rp_learn_moments_kernel(const rp_learn_moments_args a) {
   __shared__ double part[RPL_MOMENT_LANES][RPL_MOMENT_COLS];
-  const int col = (int)threadIdx.x & (RPL_MOMENT_COLS - 1), l = (int)threadIdx.x / RPL_MOMENT_COLS;
-  const int j = (int)blockIdx.x * RPL_MOMENT_COLS + col;
-  const bool live = j < a.D;
-  const float* x = a.obs + (live ? j : 0);
-  const double nb = (double)a.n_rows;
-  double S = 0.0;
-  if (live)
-    for (long long i = l; i < a.n_rows; i += RPL_MOMENT_LANES) S = S + (double)x[i * a.D];
-  S = rpl_lane_sum(S, part, col, l);
-  const double mb = S / nb;
-  double M = 0.0;
-  if (live)
-    for (long long i = l; i < a.n_rows; i += RPL_MOMENT_LANES) {
-      const double d = (double)x[i * a.D] - mb;
-      const double q = d * d;
-      M = M + q;
-    }
-  M = rpl_lane_sum(M, part, col, l);
-  if (!live || l != 0) return;
-  const double n = a.count + nb;
-  const double dl = mb - a.mean[j];
-  const double w = nb / n;
-  const double step = dl * w;
-  const double mean = a.mean[j] + step;
-  const double dd = dl * dl;
-  const double dc = dd * a.count;
-  const double cross = dc * w;
-  const double m2ab = a.M2[j] + M;
-  const double m2 = m2ab + cross;
-  a.mean[j] = mean;
-  a.M2[j] = m2;
-  a.mean_f32[j] = (float)mean;
-  const double var = m2 / n;
-  const double ve = var + a.eps;
-  const double sd = sqrt(ve);
-  const double inv = 1.0 / sd;
-  a.inv_std_f32[j] = (float)inv;
+  rpl_moments_block(a, RplRowIdentity{}, part);
 }
 
 }  // namespace

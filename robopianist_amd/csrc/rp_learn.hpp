@@ -108,4 +108,66 @@ inline std::string rpl_check_moments(const rp_learn_moments_args* a) {
   return "";
 }
 
+// ---- the device text of moments, shared with librp_pop.so (rp_pop.hip) --------------------------------------------------
+// Parametrised by a row map resolved at compile time: the kernel of librp_learn.so passes the identity.
+namespace {
+
+struct RplRowIdentity {   // row l of the caller's range is array row l
+  __device__ long long operator()(long long l) const { return l; }
+};
+
+__device__ inline double rpl_lane_sum(double mine, double (*part)[RPL_MOMENT_COLS], int col, int l) {
+  __syncthreads();   // (the previous reduction's reads)
+  part[l][col] = mine;
+  __syncthreads();
+  double s = part[0][col];
+  for (int i = 1; i < RPL_MOMENT_LANES; i++) s = s + part[i][col];
+  return s;
+}
+
+// The merge of the caller's n_rows rows, `rows` giving the array row of each, into the moments `a` points to; `part`:
+// the caller's LDS.  All 256 threads call it together.
+template <typename Rows>
+__device__ inline void rpl_moments_block(const rp_learn_moments_args& a, const Rows rows, double (*part)[RPL_MOMENT_COLS]) {
+  const int col = (int)threadIdx.x & (RPL_MOMENT_COLS - 1), l = (int)threadIdx.x / RPL_MOMENT_COLS;
+  const int j = (int)blockIdx.x * RPL_MOMENT_COLS + col;
+  const bool live = j < a.D;
+  const float* x = a.obs + (live ? j : 0);
+  const double nb = (double)a.n_rows;
+  double S = 0.0;
+  if (live)
+    for (long long i = l; i < a.n_rows; i += RPL_MOMENT_LANES) S = S + (double)x[rows(i) * a.D];
+  S = rpl_lane_sum(S, part, col, l);
+  const double mb = S / nb;
+  double M = 0.0;
+  if (live)
+    for (long long i = l; i < a.n_rows; i += RPL_MOMENT_LANES) {
+      const double d = (double)x[rows(i) * a.D] - mb;
+      const double q = d * d;
+      M = M + q;
+    }
+  M = rpl_lane_sum(M, part, col, l);
+  if (!live || l != 0) return;
+  const double n = a.count + nb;
+  const double dl = mb - a.mean[j];
+  const double w = nb / n;
+  const double step = dl * w;
+  const double mean = a.mean[j] + step;
+  const double dd = dl * dl;
+  const double dc = dd * a.count;
+  const double cross = dc * w;
+  const double m2ab = a.M2[j] + M;
+  const double m2 = m2ab + cross;
+  a.mean[j] = mean;
+  a.M2[j] = m2;
+  a.mean_f32[j] = (float)mean;
+  const double var = m2 / n;
+  const double ve = var + a.eps;
+  const double sd = sqrt(ve);
+  const double inv = 1.0 / sd;
+  a.inv_std_f32[j] = (float)inv;
+}
+
+}  // namespace
+
 #endif  // RP_LEARN_HPP_

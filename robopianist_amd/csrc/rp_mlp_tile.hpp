@@ -1,6 +1,7 @@
 // rp_mlp_tile.hpp -- the 16-row MFMA multilayer-perceptron tile in LDS, shared by the kernels of librp_learn.so
-// (rp_learn.hip: the PPO policy) and of librp_sac.so (rp_sac.hip: the SAC policy and TD target), and the one-wave row
-// copy: rp_sac_sample_kernel's rows through rpl_copy_row, rp_learn_pack_kernel's float32 fields through its parts.
+// (rp_learn.hip: the PPO policy), of librp_sac.so (rp_sac.hip: the SAC policy and TD target), of librp_droq.so and of
+// librp_pop.so (the same bodies, through rp_sac.hpp and rp_droq.hpp), and the one-wave row copy: the sampler's rows
+// through rpl_copy_row, rp_learn_pack_kernel's float32 fields through its parts.
 //
 // A workgroup of RPL_BLOCK = 256 threads (four waves) owns RPL_TILE_R = 16 rows.  A layer runs on
 // v_mfma_f32_16x16x4_f32; both operands go through LDS RPL_TK = 32 k at a time (the caller's `sa` [16][RPL_S_PITCH] and

@@ -10,6 +10,8 @@
 //   rp_sac_target_kernel   grid (row tile), four waves: the same tile on each target critic in turn, the first layer
 //                          reading cat([normalised next obs, action]); the running minimum of the tile's 16 rows stays
 //                          in LDS, so the ensemble needs neither atomics nor a second launch.
+// The bodies of sample and act are device functions of rp_sac.hpp (rps_sample_row, rps_act_tile), which librp_pop.so runs
+// on a member's rows too; the kernels here call them with the identity map.
 // Resources (gfx950, -O3 -ffp-contract=on, the compiler's kernel-resource-usage remark): sample 14 VGPRs, no LDS; act
 // 178 VGPRs + 16 AGPRs, 0 scratch, 53,632 bytes of LDS (rp_learn_act_kernel's figures: two workgroups per CU); target 256
 // VGPRs + 72 AGPRs, 0 scratch, 53,696 bytes (the learner's three arrays and 64 bytes of minima): one workgroup per CU,
@@ -28,136 +30,17 @@
 
 namespace {
 
-// ---- sample ----------------------------------------------------------------------------------------------------------
-__device__ inline void rps_zero_row(float* d, int width) {
-  for (int i = (int)threadIdx.x; i < width; i += RPL_WAVE) d[i] = 0.f;
-}
-
+// ---- sample and act: the bodies are rp_sac.hpp's, on the identity map ------------------------------------------------
 __global__ __launch_bounds__(RPL_WAVE) void rp_sac_sample_kernel(const rp_sac_sample_args a) {
-  const long long b = (long long)a.row_first + blockIdx.x;
-  const long long C = a.C, E = a.E;
-  const long long F = a.n_written < C ? a.n_written : C;
-  const uint64_t N = (uint64_t)((F - 1) * E);   // (< 2^32, checked)
-  long long slot = -1, next = -1, e = 0;
-  for (uint32_t j = 0; j < RP_SAC_SAMPLE_TRIES; ++j) {
-    const uint32_t w = rppl_philox(a.round, (uint32_t)b, 0u, 16u + j, a.seed_lo, a.seed_hi).w[0];
-    const uint64_t i = ((uint64_t)w * N) >> 32;   // (< N)
-    const long long t = (long long)(i / (uint64_t)E);
-    const long long ee = (long long)(i % (uint64_t)E);
-    const long long m = a.n_written - F + t;      // (<= n_written - 2)
-    const long long s0 = m % C, s1 = (m + 1) % C;
-    const int st0 = a.ring_step_type[s0 * E + ee], st1 = a.ring_step_type[s1 * E + ee];
-    if (st0 != RP_LEARN_STEP_LAST && st1 != RP_LEARN_STEP_FIRST) {   // (wave-uniform)
-      slot = s0; next = s1; e = ee;
-      break;
-    }
-  }
-  float* obs = a.obs + b * a.D;
-  float* nobs = a.next_obs + b * a.D;
-  float* act = a.action + b * a.A;
-  if (slot < 0) {
-    rps_zero_row(obs, a.D);
-    rps_zero_row(nobs, a.D);
-    rps_zero_row(act, a.A);
-    if (threadIdx.x == 0) {
-      a.reward[b] = 0.f;
-      a.discount[b] = 0.f;
-      a.mask[b] = 0.f;
-      if (a.index) a.index[b] = -1;
-    }
-    return;
-  }
-  const long long r0 = slot * E + e, r1 = next * E + e;
-  rpl_copy_row(a.ring_obs + r0 * a.D, obs, a.D);
-  rpl_copy_row(a.ring_obs + r1 * a.D, nobs, a.D);
-  rpl_copy_row(a.ring_action + r0 * a.A, act, a.A);
-  if (threadIdx.x == 0) {
-    a.reward[b] = a.ring_reward[r1];
-    a.discount[b] = a.ring_discount[r1];
-    a.mask[b] = 1.f;
-    if (a.index) a.index[b] = (int32_t)r0;
-  }
+  rps_sample_row(a, (long long)a.row_first + blockIdx.x, RpsEnvsAll{a.E});
 }
-
-// ---- act -------------------------------------------------------------------------------------------------------------
-struct RpsActor {
-  rp_learn_mlp net;
-  float logp_const;   // (float)(0.5 A ln 2 pi)
-  float ln2;          // (float)ln 2
-};
 
 __global__ __launch_bounds__(RPL_BLOCK) void rp_sac_act_kernel(const rp_sac_act_args a, const RpsActor actor) {
   __shared__ float sa[RPL_TILE_R * RPL_S_PITCH];        // the staged input: [row][k]
   __shared__ float sw[RP_LEARN_MAX_H * RPL_S_PITCH];    // the staged weights: [out][k]; the epilogue's log-probability terms
   __shared__ float sh[RPL_TILE_R * RPL_H_PITCH];        // the tile's activations: [row][unit]
-  const int tid = (int)threadIdx.x;
-  const rp_learn_mlp net = actor.net;
-  const int A = a.A, N3 = 2 * a.A;
-  const long long e0 = (long long)a.row_first + (long long)blockIdx.x * RPL_TILE_R;
-  const long long e_end = (long long)a.row_first + a.row_count;
-  f32x4 acc[RPL_ACC];
-  const float clip = a.obs_clip, nclip = -a.obs_clip;
-  rpl_layer(
-      [&](int r, int k) {
-        const long long e = e0 + r;
-        if (e >= e_end) return 0.f;
-        const float x = a.obs[(size_t)e * a.D + k];
-        const float d = x - a.mean[k];
-        const float p = d * a.inv_std[k];
-        const float lo = fmaxf(p, nclip);
-        return fminf(lo, clip);
-      },
-      a.D, net.w1, a.H1, sa, sw, acc);
-  rpl_store_layer<true>(acc, net.b1, a.H1, sh);
-  rpl_layer([&](int r, int k) { return sh[r * RPL_H_PITCH + k]; }, a.H1, net.w2, a.H2, sa, sw, acc);
-  rpl_store_layer<true>(acc, net.b2, a.H2, sh);
-  rpl_layer([&](int r, int k) { return sh[r * RPL_H_PITCH + k]; }, a.H2, net.w3, N3, sa, sw, acc);
-  rpl_store_layer<false>(acc, net.b3, N3, sh);
-  float* sg = sw;   // [row][RP_LEARN_MAX_A]: the terms of the log-probability (the weight stage is dead)
-  for (int idx = tid; idx < RPL_TILE_R * A; idx += RPL_BLOCK) {
-    const int r = idx / A, u = idx - r * A;
-    const long long e = e0 + r;
-    if (e >= e_end) continue;
-    const float m = sh[r * RPL_H_PITCH + u];
-    float p = m;
-    if (!a.deterministic) {
-      const float l = sh[r * RPL_H_PITCH + A + u];
-      const float lc = fmaxf(l, a.log_std_min);
-      const float ls = fminf(lc, a.log_std_max);
-      const float zf = (float)rppl_z(a.seed_lo, a.seed_hi, a.round, (uint32_t)e, (uint32_t)u);
-      const float sd = expf(ls);
-      const float t = sd * zf;
-      p = m + t;
-      const float w = -2.f * p;
-      const float aw = fabsf(w);
-      const float ex = expf(-aw);
-      const float l1 = log1pf(ex);
-      const float wp = fmaxf(w, 0.f);
-      const float sp = wp + l1;
-      const float c1 = actor.ln2 - p;
-      const float c2 = c1 - sp;
-      const float lg = 2.f * c2;
-      const float q = zf * zf;
-      const float h = -0.5f * q;
-      const float g0 = h - ls;
-      sg[r * RP_LEARN_MAX_A + u] = g0 - lg;
-    }
-    const float act = tanhf(p);
-    const size_t o = (size_t)e * A + u;
-    a.action[o] = act;
-    if (a.pre) a.pre[o] = p;
-    if (a.env_action) {
-      if (a.precision == 32) static_cast<float*>(a.env_action)[o] = act;
-      else static_cast<double*>(a.env_action)[o] = (double)act;
-    }
-  }
-  if (a.deterministic) return;   // (block-uniform)
-  __syncthreads();
-  if (tid < RPL_TILE_R && e0 + tid < e_end) {
-    float s = 0.f;
-    for (int u = 0; u < A; u++) s = s + sg[tid * RP_LEARN_MAX_A + u];
-    a.logp[e0 + tid] = s - actor.logp_const;
-  }
+  rps_act_tile(a, actor, RplRowIdentity{}, (long long)a.row_first + (long long)blockIdx.x * RPL_TILE_R,
+               (long long)a.row_first + a.row_count, sa, sw, sh);
 }
 
 // ---- target ----------------------------------------------------------------------------------------------------------

@@ -1,0 +1,688 @@
+"""ctypes binding of the population kernels' C ABI (include/learn/rp_pop.h, librp_pop.so) and `DroQPopulation`, P
+independent DroQ learners (droq.DroQ) that share one environment batch: member p owns the envs e with e % P == p -- the
+task's own song rule, so with `midi=[P songs]` member p is the specialist of song p, and with one song the members are
+P seeds or a sweep over `gamma`, `init_alpha` and `target_entropy`.
+
+The four entry points are module functions taking raw device addresses (`sample`, `act`, `target`, `moments`); each
+enqueues one kernel on the caller's HIP stream and reads nothing back.  They are the single-learner kernels' device text
+(rp_sac_sample, rp_sac_act, rp_droq_target, rp_learn_moments) run on a member's rows with that member's slices of the
+stacked parameters.  The ring is SAC's [C][E]..., written by the learner's unchanged `pack`.  The gradient step is plain
+torch on stacked parameters [P][out][in] (`torch.baddbmm`): a loss is the sum over the members of the per-member masked
+means, so member p's gradient depends on member p's rows alone, and Adam, being element-wise, keeps the members
+independent.  Like the engine, the library has no CPU fallback: a missing library is an error.
+"""
+
+from __future__ import annotations
+
+import copy
+import ctypes
+import math
+import os
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+from torch import nn
+
+from robopianist_amd import _abi, droq
+from robopianist_amd.droq import Critic, drop_threshold
+from robopianist_amd.learning import STEP_FIRST, STEP_LAST, DeviceLearner, LearnError, Mlp
+from robopianist_amd.offpolicy import MAX_CRITICS, squashed_gaussian
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+LIB_PATH = os.environ.get("RP_POP_LIB") or os.path.join(_HERE, "csrc", "librp_pop.so")
+
+EXPORTED_SYMBOLS = ("rp_pop_act", "rp_pop_sample", "rp_pop_target", "rp_pop_moments", "rp_pop_dim", "rp_pop_last_error")
+
+INTERLEAVED, BLOCKED = 0, 1          # row j of member p is array row p + P j / p rows + j
+TILE_MAJOR, MEMBER_MAJOR = 0, 1      # the workgroup order of act and target (speed only)
+
+_lib = None
+
+_p, _i, _u32, _f, _d = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_float, ctypes.c_double
+
+
+class ActArgs(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_size_t), ("obs", _p), ("mean", _p), ("inv_std", _p), ("obs_clip", _f),
+                ("log_std_min", _f), ("log_std_max", _f), ("actor", ctypes.POINTER(Mlp)), ("action", _p), ("logp", _p),
+                ("pre", _p), ("env_action", _p), ("precision", _i), ("deterministic", _i), ("seed_lo", _u32),
+                ("seed_hi", _u32), ("round", _u32), ("D", _i), ("H1", _i), ("H2", _i), ("A", _i), ("P", _i), ("rows", _i),
+                ("layout", _i), ("grid_order", _i), ("member_first", _i), ("member_count", _i), ("row_first", _i),
+                ("row_count", _i), ("hip_stream", _p)]
+
+
+class SampleArgs(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_size_t), ("ring_obs", _p), ("ring_action", _p), ("ring_reward", _p),
+                ("ring_discount", _p), ("ring_step_type", _p), ("obs", _p), ("next_obs", _p), ("action", _p),
+                ("reward", _p), ("discount", _p), ("mask", _p), ("index", _p), ("n_written", ctypes.c_longlong),
+                ("seed_lo", _u32), ("seed_hi", _u32), ("round", _u32), ("C", _i), ("E", _i), ("D", _i), ("A", _i),
+                ("P", _i), ("n", _i), ("member_first", _i), ("member_count", _i), ("row_first", _i), ("row_count", _i),
+                ("hip_stream", _p)]
+
+
+class TargetArgs(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_size_t), ("next_obs", _p), ("action", _p), ("logp", _p), ("reward", _p),
+                ("discount", _p), ("mean", _p), ("inv_std", _p), ("obs_clip", _f), ("gamma", _p), ("log_alpha", _p),
+                ("critics", ctypes.POINTER(Critic)), ("n_critics", _i), ("y", _p), ("q_min", _p), ("q", _p),
+                ("drop_threshold", _u32), ("keep_scale", _f), ("ln_eps", _f), ("seed_lo", _u32), ("seed_hi", _u32),
+                ("round", _u32), ("D", _i), ("H1", _i), ("H2", _i), ("A", _i), ("P", _i), ("n", _i), ("grid_order", _i),
+                ("member_first", _i), ("member_count", _i), ("row_first", _i), ("row_count", _i), ("hip_stream", _p)]
+
+
+class MomentsArgs(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_size_t), ("obs", _p), ("mean", _p), ("M2", _p), ("mean_f32", _p),
+                ("inv_std_f32", _p), ("count", _d), ("eps", _d), ("k", _i), ("E", _i), ("D", _i), ("P", _i),
+                ("member_first", _i), ("member_count", _i), ("hip_stream", _p)]
+
+
+_ARGS = {"act": ActArgs, "sample": SampleArgs, "target": TargetArgs, "moments": MomentsArgs}
+
+
+def load_library(path: str = LIB_PATH):
+    """Loads librp_pop.so; raises LearnError if it has not been built."""
+    global _lib
+    if _lib is None:
+        _lib = declare(_abi.open_library(path, "population", LearnError))
+    return _lib
+
+
+_entries = _abi.EntryTable("rp_pop_", _ARGS, LearnError, load_library)
+make_args, call_raw, last_error, dim, _call = (_entries.make_args, _entries.call_raw, _entries.last_error, _entries.dim,
+                                               _entries.call)
+
+
+def declare(L, prefix: str = "rp_pop_"):
+    """Declares the ABI's prototypes on a loaded library whose symbols start with `prefix`."""
+    return _entries.declare(L, prefix)
+
+
+def _order(grid_order):
+    return dim("default_grid_order") if grid_order is None else int(grid_order)
+
+
+def _ranges(P, rows, member_first, member_count, row_first, row_count):
+    return dict(member_first=member_first, member_count=P - member_first if member_count is None else member_count,
+                row_first=row_first, row_count=rows - row_first if row_count is None else row_count)
+
+
+def act(obs, mean, inv_std, obs_clip, actor, D, H1, H2, A, P, rows, layout, log_std_bounds=(-5.0, 2.0), action=None,
+        logp=None, pre=None, env_action=None, precision=64, deterministic=False, seed=0, round_=0, member_first=0,
+        member_count=None, row_first=0, row_count=None, grid_order=None, hip_stream=None):
+    """`actor`: an `Mlp` of the bases of the stacked tensors; `rows`: per member; `layout`: INTERLEAVED / BLOCKED."""
+    _call("act", obs=obs, mean=mean, inv_std=inv_std, obs_clip=float(obs_clip), log_std_min=float(log_std_bounds[0]),
+          log_std_max=float(log_std_bounds[1]), actor=ctypes.pointer(actor) if actor is not None else None,
+          action=action, logp=logp, pre=pre, env_action=env_action, precision=precision,
+          deterministic=int(bool(deterministic)), D=D, H1=H1, H2=H2, A=A, P=P, rows=rows, layout=int(layout),
+          grid_order=_order(grid_order), hip_stream=hip_stream, **_abi.seed_args(seed, round_),
+          **_ranges(P, rows, member_first, member_count, row_first, row_count))
+
+
+def sample(ring_obs, ring_action, ring_reward, ring_discount, ring_step_type, obs, next_obs, action, reward, discount,
+           mask, n_written, C, E, D, A, P, n, index=None, seed=0, round_=0, member_first=0, member_count=None,
+           row_first=0, row_count=None, hip_stream=None):
+    """`n`: minibatch rows per member; the outputs hold P n rows, member p's at [p n, (p + 1) n)."""
+    _call("sample", ring_obs=ring_obs, ring_action=ring_action, ring_reward=ring_reward, ring_discount=ring_discount,
+          ring_step_type=ring_step_type, obs=obs, next_obs=next_obs, action=action, reward=reward, discount=discount,
+          mask=mask, index=index, n_written=int(n_written), C=C, E=E, D=D, A=A, P=P, n=n, hip_stream=hip_stream,
+          **_abi.seed_args(seed, round_), **_ranges(P, n, member_first, member_count, row_first, row_count))
+
+
+def target(next_obs, action, logp, reward, discount, mean, inv_std, obs_clip, gamma, log_alpha, critics, y, D, H1, H2, A,
+           P, n, q_min=None, q=None, threshold=0, keep_scale=1.0, ln_eps=1e-5, seed=0, round_=0, member_first=0,
+           member_count=None, row_first=0, row_count=None, grid_order=None, hip_stream=None):
+    """`critics`: a sequence of `Critic` of the bases of the stacked target networks; `gamma`, `log_alpha`: device
+    addresses of [P] float32."""
+    tab = droq.critic_table(critics)
+    _call("target", next_obs=next_obs, action=action, logp=logp, reward=reward, discount=discount, mean=mean,
+          inv_std=inv_std, obs_clip=float(obs_clip), gamma=gamma, log_alpha=log_alpha, critics=tab, n_critics=len(tab),
+          y=y, q_min=q_min, q=q, drop_threshold=int(threshold), keep_scale=float(keep_scale), ln_eps=float(ln_eps),
+          D=D, H1=H1, H2=H2, A=A, P=P, n=n, grid_order=_order(grid_order), hip_stream=hip_stream,
+          **_abi.seed_args(seed, round_), **_ranges(P, n, member_first, member_count, row_first, row_count))
+
+
+def moments(obs, mean, M2, mean_f32, inv_std_f32, count, eps, k, E, D, P, member_first=0, member_count=None,
+            hip_stream=None):
+    """`obs`: the first of k consecutive ring slots [k][E][D]; the four outputs are [P][D]."""
+    _call("moments", obs=obs, mean=mean, M2=M2, mean_f32=mean_f32, inv_std_f32=inv_std_f32, count=float(count),
+          eps=float(eps), k=int(k), E=E, D=D, P=P, member_first=member_first,
+          member_count=P - member_first if member_count is None else member_count, hip_stream=hip_stream)
+
+
+# ---- the batched modules -------------------------------------------------------------------------------------------------
+class BatchedLinear(nn.Module):
+    """P `nn.Linear`s as one: weight [P][out][in], bias [P][out]; [P, n, in] -> [P, n, out]."""
+
+    def __init__(self, linears):
+        super().__init__()
+        self.weight = nn.Parameter(torch.stack([m.weight.detach() for m in linears]).contiguous())
+        self.bias = nn.Parameter(torch.stack([m.bias.detach() for m in linears]).contiguous())
+
+    def forward(self, x):
+        return torch.baddbmm(self.bias.unsqueeze(1), x, self.weight.transpose(1, 2))
+
+
+class BatchedLayerNorm(nn.Module):
+    """P `nn.LayerNorm`s over the last dimension as one: weight, bias [P][H]."""
+
+    def __init__(self, norms):
+        super().__init__()
+        self.eps = float(norms[0].eps)
+        self.weight = nn.Parameter(torch.stack([m.weight.detach() for m in norms]).contiguous())
+        self.bias = nn.Parameter(torch.stack([m.bias.detach() for m in norms]).contiguous())
+
+    def forward(self, x):
+        h = F.layer_norm(x, (x.shape[-1],), None, None, self.eps)
+        return h * self.weight.unsqueeze(1) + self.bias.unsqueeze(1)
+
+
+def stack_networks(nets):
+    """P `nn.Sequential`s of the same architecture (Linear, LayerNorm, Dropout, Tanh, ReLU) as one batched
+    `nn.Sequential` with the same indices, on [P, n, .]."""
+    BL, BLN = BatchedLinear, BatchedLayerNorm
+    layers = []
+    for group in zip(*nets):
+        m = group[0]
+        if isinstance(m, nn.Linear):
+            layers.append(BL(group))
+        elif isinstance(m, nn.LayerNorm):
+            layers.append(BLN(group))
+        elif isinstance(m, nn.Dropout):
+            layers.append(nn.Dropout(m.p))
+        else:
+            layers.append(type(m)())
+    return nn.Sequential(*layers)
+
+
+def member_network(net, p):
+    """Member p of a batched network as a plain `nn.Sequential` (a copy)."""
+    BL, BLN = BatchedLinear, BatchedLayerNorm
+    layers = []
+    for m in net:
+        if isinstance(m, BL):
+            lin = nn.Linear(m.weight.shape[2], m.weight.shape[1]).to(m.weight.device, m.weight.dtype)
+            with torch.no_grad():
+                lin.weight.copy_(m.weight[p]); lin.bias.copy_(m.bias[p])
+            layers.append(lin)
+        elif isinstance(m, BLN):
+            ln = nn.LayerNorm(m.weight.shape[1], m.eps).to(m.weight.device, m.weight.dtype)
+            with torch.no_grad():
+                ln.weight.copy_(m.weight[p]); ln.bias.copy_(m.bias[p])
+            layers.append(ln)
+        elif isinstance(m, nn.Dropout):
+            layers.append(nn.Dropout(m.p))
+        else:
+            layers.append(type(m)())
+    return nn.Sequential(*layers)
+
+
+# ---- the losses: offpolicy's, per member, summed over the members ----------------------------------------------------------
+def member_means(x, mask):
+    """offpolicy._masked_mean of every member: x, mask [P, n] -> [P]."""
+    return (x * mask).sum(1) / mask.sum(1).clamp(min=1.0)
+
+
+def critic_losses(qs, y, mask):
+    """offpolicy.critic_loss of every member on its own rows: [P].  `qs`: a list of [P, n]."""
+    return sum(member_means(0.5 * (q - y) ** 2, mask) for q in qs)
+
+
+def actor_losses(log_alpha, logp_new, q_new, mask):
+    """offpolicy.actor_loss of every member: [P]; `log_alpha` [P]."""
+    return member_means(log_alpha.detach().exp().unsqueeze(1) * logp_new - q_new, mask)
+
+
+def alpha_losses(log_alpha, logp_new, target_entropy, mask):
+    """offpolicy.alpha_loss of every member: [P]; `log_alpha`, `target_entropy` [P]."""
+    return member_means(-log_alpha.unsqueeze(1) * (logp_new.detach() + target_entropy.unsqueeze(1)), mask)
+
+
+def critic_loss(qs, y, mask):
+    """What the critics' optimizer minimises: the sum over the members, so that member p's gradient is its own loss's."""
+    return critic_losses(qs, y, mask).sum()
+
+
+def actor_loss(log_alpha, logp_new, q_new, mask):
+    return actor_losses(log_alpha, logp_new, q_new, mask).sum()
+
+
+def alpha_loss(log_alpha, logp_new, target_entropy, mask):
+    return alpha_losses(log_alpha, logp_new, target_entropy, mask).sum()
+
+
+def _per_member(value, P, name):
+    """A scalar or a length-P sequence as a list of P floats."""
+    if np.ndim(value) == 0:
+        return [float(value)] * P
+    out = [float(v) for v in value]
+    if len(out) != P:
+        raise ValueError(f"{name} must be a scalar or a sequence of {P} values (one per member), got {len(out)}")
+    return out
+
+
+class DroQPopulation(DeviceLearner):
+    """`members` = P independent `droq.DroQ` learners over one env batch of E = P Em envs: member p collects with, and
+    learns from, the envs p, p + P, p + 2 P, ... alone, and has its own actor, critics, targets, temperature, observation
+    normaliser and minibatches of `batch_size` rows (per member).  `gamma`, `init_alpha` and `target_entropy` take a
+    scalar or a sequence of P values; everything else is shared.  With `members=1` this is DroQ.
+
+    `collect(n)` launches, per control step, one `rp_pop_act` over all envs (each env by its member's actor), the env's
+    step and `pack`, then one `rp_pop_moments` per contiguous run of new slots; nothing is read back.  `update(g)` is
+    DroQ's schedule with one `rp_pop_sample`, one `rp_pop_act` and, per range, one `rp_pop_target` for all members."""
+
+    _reads = "the population kernels read"
+
+    def __init__(self, env, members: int, hidden=(256, 256), n_critics: int = 2, capacity: int = 64,
+                 batch_size: int = 256, gamma=0.99, tau: float = 0.005, lr: float = 3e-4, init_alpha=1.0,
+                 target_entropy=None, log_std_bounds=(-5.0, 2.0), learning_starts: int = 0, obs_clip: float = 10.0,
+                 seed: int = 0, norm_eps: float = 1e-8, dropout: float = 0.01, utd: int = 20, ln_eps: float = 1e-5):
+        super().__init__(env)
+        self.P = int(members)
+        if self.P < 1:
+            raise ValueError(f"members must be >= 1, got {members}")
+        if self.E % self.P:
+            raise ValueError(f"members = {self.P} does not divide n_envs = {self.E}: member p owns the envs e % members == p")
+        self.Em = self.E // self.P
+        self.C, self.B = int(capacity), int(batch_size)
+        if self.C < 2:
+            raise ValueError("capacity must be >= 2 slots")
+        if self.B < 1:
+            raise ValueError("batch_size must be >= 1")
+        if (self.C - 1) * self.Em >= 2 ** 32:
+            raise ValueError("(capacity - 1) x n_envs / members must stay below 2^32")
+        self.dropout, self.utd, self.ln_eps = float(dropout), int(utd), float(ln_eps)
+        if not 0.0 <= self.dropout < 1.0:
+            raise ValueError(f"dropout must lie in [0, 1), got {dropout}")
+        if self.utd < 1:
+            raise ValueError(f"utd must be >= 1, got {utd}")
+        if not self.ln_eps > 0.0:
+            raise ValueError(f"ln_eps must be > 0, got {ln_eps}")
+        if self.P * self.utd * self.B > 2 ** 31 - 1:
+            raise ValueError("members x utd x batch_size must stay below 2^31")
+        self._threshold = drop_threshold(self.dropout)
+        self._keep_scale = 1.0 / (1.0 - self.dropout)
+        self._init_specs(hidden, obs_clip, seed, norm_eps)
+        self.n_critics = int(n_critics)
+        if not 1 <= self.n_critics <= MAX_CRITICS:
+            raise ValueError(f"n_critics must be 1 .. {MAX_CRITICS}, got {n_critics}")
+        P, D, A = self.P, self.D, self.A
+        f32 = lambda v: torch.tensor(v, dtype=torch.float32, device=self._dev)
+        self.gamma = f32(_per_member(gamma, P, "gamma"))
+        self.target_entropy = f32(_per_member(-float(A) if target_entropy is None else target_entropy, P, "target_entropy"))
+        alpha0 = _per_member(init_alpha, P, "init_alpha")
+        self.tau = float(tau)
+        self.log_std_bounds = (float(log_std_bounds[0]), float(log_std_bounds[1]))
+        if not self.log_std_bounds[0] <= self.log_std_bounds[1]:
+            raise ValueError("log_std_bounds must be (min, max) with min <= max")
+        self.learning_starts = int(learning_starts)
+        self.n_written = 0
+        with torch.random.fork_rng(devices=[]):   # (the global generator is left as it was)
+            torch.manual_seed(self.seed)
+            drawn = [(self._net(D, 2 * A), [self._critic_net(D + A) for _ in range(self.n_critics)]) for _ in range(P)]
+        self.actor = stack_networks([a for a, _ in drawn]).to(self._dev)
+        self.critics = [stack_networks([cs[i] for _, cs in drawn]).to(self._dev) for i in range(self.n_critics)]
+        self.targets = [copy.deepcopy(c) for c in self.critics]
+        for t in self.targets:
+            t.requires_grad_(False)
+        self.log_alpha = nn.Parameter(f32([math.log(a) for a in alpha0]))
+        adam = lambda params: torch.optim.Adam(params, lr=float(lr))
+        self.actor_optimizer = adam(list(self.actor.parameters()))
+        self.critic_optimizer = adam([p for c in self.critics for p in c.parameters()])
+        self.alpha_optimizer = adam([self.log_alpha])
+        self._gen = torch.Generator(device=self._dev).manual_seed(self.seed)
+        C, E, z = self.C, self.E, self._zeros
+        # the normaliser, per member (DeviceLearner allocated one row)
+        self._mean, self._M2 = z(P, D, dtype=torch.float64), z(P, D, dtype=torch.float64)
+        self._mean_f32, self._inv_std_f32 = z(P, D), torch.ones(P, D, dtype=torch.float32, device=self._dev)
+        # the ring: SAC's
+        self._obs, self._reward, self._discount = z(C, E, D), z(C, E), z(C, E)
+        self._step_type, self._action = z(C, E, dtype=torch.int32), z(C, E, A)
+        self._logp, self._env_action = z(E), z(E, A, dtype=self._dtype)
+        # the minibatches: member p's utd ranges of B rows at [p n, (p + 1) n), n = utd B
+        n = self.utd * self.B
+        self._u_obs, self._u_next, self._u_action = z(P * n, D), z(P * n, D), z(P * n, A)
+        self._u_reward, self._u_discount, self._u_mask = z(P * n), z(P * n), z(P * n)
+        self._u_next_action, self._u_next_logp, self._u_y = z(P * n, A), z(P * n), z(P * n)
+        self._range = self.utd - 1
+
+    def _critic_net(self, n_in):
+        """One member's critic, drawn as droq.DroQ draws it."""
+        p, eps = self.dropout, self.ln_eps
+        return nn.Sequential(nn.Linear(n_in, self.H1), nn.Dropout(p), nn.LayerNorm(self.H1, eps), nn.ReLU(),
+                             nn.Linear(self.H1, self.H2), nn.Dropout(p), nn.LayerNorm(self.H2, eps), nn.ReLU(),
+                             nn.Linear(self.H2, 1))
+
+    # -- accessors ---------------------------------------------------------------------------------------------------
+    @property
+    def members(self):
+        return self.P
+
+    @property
+    def alpha(self):
+        """[P] floats."""
+        return self.log_alpha.detach().exp().cpu().numpy().astype(np.float64)
+
+    def ring(self):
+        """The replay ring as a dict of views (live); TimeStep m lives in slot m mod capacity, env e belongs to member
+        e % members."""
+        return {"obs": self._obs, "reward": self._reward, "discount": self._discount, "step_type": self._step_type,
+                "action": self._action}
+
+    def rows(self):
+        """The utd x batch_size rows per member that the last actor step drew, [P, utd B, ...] views (live)."""
+        v = lambda t: t.view(self.P, self.utd * self.B, *t.shape[1:])
+        return {"obs": v(self._u_obs), "next_obs": v(self._u_next), "action": v(self._u_action),
+                "reward": v(self._u_reward), "discount": v(self._u_discount), "mask": v(self._u_mask),
+                "next_action": v(self._u_next_action), "next_logp": v(self._u_next_logp), "y": v(self._u_y)}
+
+    def minibatch(self):
+        """The range of `rows()` the last launches worked on: [P, B, ...] views (live)."""
+        r = slice(self._range * self.B, (self._range + 1) * self.B)
+        return {k: v[:, r] for k, v in self.rows().items()}
+
+    def _checked(self, tensors):
+        for t in tensors:
+            if not t.is_contiguous() or t.dtype != torch.float32:
+                raise LearnError(f"{self._reads} contiguous float32 parameters")
+        return tensors
+
+    def _actor_table(self):
+        """The stacked actor as rp_learn_mlp: the bases of its tensors as they are now."""
+        net = self.actor
+        m = Mlp()
+        for (name, _), t in zip(Mlp._fields_, self._checked([t for i in (0, 2, 4) for t in (net[i].weight, net[i].bias)])):
+            setattr(m, name, t.data_ptr())
+        return m
+
+    def _critic_table(self, net):
+        """A stacked critic as rp_droq_critic."""
+        tensors = [t for i in (0, 4, 8) for t in (net[i].weight, net[i].bias)]
+        tensors += [t for i in (2, 6) for t in (net[i].weight, net[i].bias)]
+        return droq.critic_entry(self._checked(tensors))
+
+    def _act(self, obs, rows, layout, st, **out):
+        act(obs.data_ptr(), self._mean_f32.data_ptr(), self._inv_std_f32.data_ptr(), self.obs_clip, self._actor_table(),
+            self.D, self.H1, self.H2, self.A, self.P, rows, layout, log_std_bounds=self.log_std_bounds, seed=self.seed,
+            round_=self._round, hip_stream=st, **out)
+
+    # -- collection ----------------------------------------------------------------------------------------------------
+    def collect(self, n: int):
+        """The next n control steps of every env into the ring (the first call resets the env and writes TimeStep 0
+        first), then the new slots into the members' normalisers.  Returns `ring()`."""
+        C, n = self.C, int(n)
+        with torch.cuda.device(self._dev):
+            st = self._stream()
+            kept = []
+            first_new = self.n_written
+            if self.n_written == 0:
+                ts = self._env.reset()
+                self._pack(ts, 0, st)
+                kept.append(ts)
+                self.n_written = 1
+            for _ in range(n):
+                newest = (self.n_written - 1) % C
+                self._act(self._obs[newest], self.Em, INTERLEAVED, st, action=self._action[newest].data_ptr(),
+                          logp=self._logp.data_ptr(), env_action=self._env_action.data_ptr(), precision=self._precision)
+                self._round += 1
+                ts = self._env.step_canonical(self._env_action, self._bounds, False)
+                self._pack(ts, self.n_written % C, st)
+                self.n_written += 1
+                kept.append(ts)
+            self._merge(first_new, self.n_written, st)
+            self._keep = kept   # alive until the kernels have run
+        return self.ring()
+
+    def _merge(self, first, end, st):
+        """The TimeSteps first .. end - 1 that the ring still holds into the running moments of every member: one launch
+        per contiguous run of slots (two where the slots wrap)."""
+        C = self.C
+        first = max(first, end - C)
+        while first < end:
+            s = first % C
+            k = min(end - first, C - s)
+            moments(self._obs[s].data_ptr(), self._mean.data_ptr(), self._M2.data_ptr(), self._mean_f32.data_ptr(),
+                    self._inv_std_f32.data_ptr(), self._count, self.norm_eps, k, self.E, self.D, self.P, hip_stream=st)
+            self._count += float(k * self.Em)
+            first += k
+
+    def normalize(self, obs):
+        """What the kernels feed the first layer (torch): obs [P, n, D] by the member's moments."""
+        return torch.clamp((obs - self._mean_f32.unsqueeze(1)) * self._inv_std_f32.unsqueeze(1), -self.obs_clip,
+                           self.obs_clip)
+
+    # -- the gradient steps ----------------------------------------------------------------------------------------------
+    def draw_and_act(self):
+        """The two launches of an actor step that cover all members and all utd ranges: the utd x B rows of every
+        member, and every member's policy at their next observations."""
+        n = self.utd * self.B
+        with torch.cuda.device(self._dev):
+            st = self._stream()
+            sample(self._obs.data_ptr(), self._action.data_ptr(), self._reward.data_ptr(), self._discount.data_ptr(),
+                   self._step_type.data_ptr(), self._u_obs.data_ptr(), self._u_next.data_ptr(), self._u_action.data_ptr(),
+                   self._u_reward.data_ptr(), self._u_discount.data_ptr(), self._u_mask.data_ptr(), self.n_written,
+                   self.C, self.E, self.D, self.A, self.P, n, seed=self.seed, round_=self._round, hip_stream=st)
+            self._act(self._u_next, n, BLOCKED, st, action=self._u_next_action.data_ptr(),
+                      logp=self._u_next_logp.data_ptr())
+
+    def target_range(self, u):
+        """The TD target of range u of every member from the target critics as they are now (one launch); returns
+        `minibatch()` on it."""
+        with torch.cuda.device(self._dev):
+            target(self._u_next.data_ptr(), self._u_next_action.data_ptr(), self._u_next_logp.data_ptr(),
+                   self._u_reward.data_ptr(), self._u_discount.data_ptr(), self._mean_f32.data_ptr(),
+                   self._inv_std_f32.data_ptr(), self.obs_clip, self.gamma.data_ptr(), self.log_alpha.data_ptr(),
+                   [self._critic_table(t) for t in self.targets], self._u_y.data_ptr(), self.D, self.H1, self.H2, self.A,
+                   self.P, self.utd * self.B, threshold=self._threshold, keep_scale=self._keep_scale, ln_eps=self.ln_eps,
+                   seed=self.seed, round_=self._round, row_first=u * self.B, row_count=self.B, hip_stream=self._stream())
+        self._range = u
+        return self.minibatch()
+
+    def critic_step(self, batch):
+        """The critics' Adam step on `batch` ([P, n, ...]; torch's own dropout) and the targets' Polyak step over the
+        stacked tensors.  Returns the per-member losses [P] (a tensor)."""
+        xa = torch.cat([self.normalize(batch["obs"]), batch["action"]], dim=2)
+        per = critic_losses([c(xa).squeeze(-1) for c in self.critics], batch["y"], batch["mask"])
+        self.critic_optimizer.zero_grad(set_to_none=True)
+        per.sum().backward()
+        self.critic_optimizer.step()
+        with torch.no_grad():
+            torch._foreach_lerp_([p for t in self.targets for p in t.parameters()],
+                                 [p for c in self.critics for p in c.parameters()], self.tau)
+        return per.detach()
+
+    def actor_step(self, batch):
+        """The actors' and the temperatures' Adam steps on `batch`; the critics stay in train() mode, as in the paper.
+        Returns per-member statistics, [P] tensors."""
+        mask = batch["mask"]
+        xn = self.normalize(batch["obs"])
+        eps = torch.randn(xn.shape[0], xn.shape[1], self.A, generator=self._gen, device=xn.device, dtype=xn.dtype)
+        a_new, logp_new, _ = squashed_gaussian(self.actor(xn), eps, self.log_std_bounds)
+        xa_new = torch.cat([xn, a_new], dim=2)
+        q_new = torch.stack([c(xa_new).squeeze(-1) for c in self.critics]).min(0).values
+        la = actor_losses(self.log_alpha, logp_new, q_new, mask)
+        self.actor_optimizer.zero_grad(set_to_none=True)
+        la.sum().backward()   # (the critics' gradients of this pass are dropped by their next zero_grad)
+        self.actor_optimizer.step()
+        lt = alpha_losses(self.log_alpha, logp_new, self.target_entropy, mask)
+        self.alpha_optimizer.zero_grad(set_to_none=True)
+        lt.sum().backward()
+        self.alpha_optimizer.step()
+        return {"actor_loss": la.detach(), "alpha_loss": lt.detach(), "alpha": self.log_alpha.detach().exp(),
+                "entropy": -member_means(logp_new.detach(), mask), "masked": 1.0 - mask.mean(1)}
+
+    def update(self, g: int = 1):
+        """g actor steps of utd critic steps each; returns the statistics of the last one: float64 arrays [P]."""
+        if self.n_written < 2:
+            raise LearnError("update() needs at least two TimeSteps in the ring: call collect() first")
+        stats = {}
+        for _ in range(int(g)):
+            self.draw_and_act()
+            for u in range(self.utd):
+                batch = self.target_range(u)
+                lc = self.critic_step(batch)
+            stats = dict({"critic_loss": lc}, **self.actor_step(batch))
+            self._round += 1
+        if not stats:
+            return {}
+        host = torch.stack([v.to(torch.float64) for v in stats.values()]).cpu().numpy()   # (one read-back)
+        return dict(zip(stats, host))
+
+    def episode_stats(self):
+        """{"episodes" [P] int, "mean_return" [P], "mean_length" [P]} of the episodes that ended since the last call, per
+        member (one read-back); the counters start again from zero."""
+        by_member = lambda t: t.view(self.Em, self.P).sum(0).to(torch.float64)
+        host = torch.stack([by_member(self._done_count), by_member(self._done_return), by_member(self._done_len)]).cpu().numpy()
+        n = host[0]
+        with np.errstate(invalid="ignore", divide="ignore"):
+            out = {"episodes": n.astype(np.int64), "mean_return": np.where(n > 0, host[1] / n, np.nan),
+                   "mean_length": np.where(n > 0, host[2] / n, np.nan)}
+        self._done_return.zero_(); self._done_len.zero_(); self._done_count.zero_()
+        return out
+
+    def train(self, n: int, steps_per_round: int = 1, grad_steps: int = 1, callback=None):
+        """n rounds of collect(steps_per_round) and, once `learning_starts` control steps have been collected,
+        update(grad_steps); returns the list of per-round statistics, every one an array of length P (the update's, plus
+        "mean_reward": the mean reward of the member's new TimeSteps that are not FIRST, and `episode_stats()`)."""
+        log = []
+        for i in range(int(n)):
+            first = max(self.n_written, 1)
+            self.collect(steps_per_round)
+            s = self.update(grad_steps) if self.n_written - 1 >= max(self.learning_starts, 1) and grad_steps > 0 else {}
+            slots = torch.arange(max(first, self.n_written - self.C), self.n_written, device=self._dev) % self.C
+            live = (self._step_type[slots] != STEP_FIRST).to(torch.float64).view(-1, self.Em, self.P)
+            reward = self._reward[slots].to(torch.float64).view(-1, self.Em, self.P)
+            sums = torch.stack([(reward * live).sum((0, 1)), live.sum((0, 1))]).cpu().numpy()
+            with np.errstate(invalid="ignore", divide="ignore"):
+                s["mean_reward"] = np.where(sums[1] > 0, sums[0] / sums[1], np.nan)
+            s.update(self.episode_stats())
+            log.append(s)
+            if callback is not None:
+                callback(i, s)
+        return log
+
+    # -- evaluation ----------------------------------------------------------------------------------------------------
+    def act(self, observation, deterministic: bool = True):
+        """The action for an observation dict of E rows, each env by its member's policy: [E, A] of the engine's dtype in
+        [-1, 1] (what a CanonicalSpecWrapper's step takes).  Live: the next call overwrites it."""
+        with torch.cuda.device(self._dev):
+            st = self._stream()
+            self._pack_observation(observation, st)
+            self._act(self._e_obs, self.Em, INTERLEAVED, st, action=self._e_action.data_ptr(),
+                      logp=self._e_logp.data_ptr(), env_action=self._e_env_action.data_ptr(), precision=self._precision,
+                      deterministic=deterministic)
+            if not deterministic:
+                self._round += 1
+        return self._e_env_action
+
+    def actor_of(self, p: int):
+        """Member p's actor as a plain `nn.Sequential` (a copy): what `droq.DroQ.actor` or `offpolicy.SAC.actor` of a
+        single-learner env batch loads with `load_state_dict(actor_of(p).state_dict())`."""
+        if not 0 <= int(p) < self.P:
+            raise ValueError(f"member {p} of {self.P}")
+        return member_network(self.actor, int(p))
+
+    def normalizer_of(self, p: int):
+        """(count, mean [D] f64, M2 [D] f64, mean_f32 [D], inv_std_f32 [D]) of member p -- live views."""
+        return self._count, self._mean[p], self._M2[p], self._mean_f32[p], self._inv_std_f32[p]
+
+    # -- checkpoint / resume -------------------------------------------------------------------------------------------
+    def state_dict(self, include_replay: bool = False):
+        """SAC's contract on the stacked tensors, plus "members" and DroQ's "droq" block; the whole ring only with
+        `include_replay`.  With the env's own `state_dict()` the next `collect()` is resumed bit for bit."""
+        c = lambda t: t.detach().clone()
+        nets = lambda ms: [{k: c(v) for k, v in m.state_dict().items()} for m in ms]
+        newest = (self.n_written - 1) % self.C if self.n_written else 0
+        sd = {"members": self.P, "droq": {"dropout": self.dropout, "utd": self.utd, "ln_eps": self.ln_eps},
+              "actor": nets([self.actor])[0], "critics": nets(self.critics), "targets": nets(self.targets),
+              "log_alpha": c(self.log_alpha), "gamma": c(self.gamma), "target_entropy": c(self.target_entropy),
+              "optimizers": {k: copy.deepcopy(getattr(self, k + "_optimizer").state_dict())
+                             for k in ("actor", "critic", "alpha")},
+              "normalizer": self._normalizer_state(),
+              "seed": self.seed, "round": self._round, "n_written": self.n_written, "generator": self._gen.get_state(),
+              "newest": {"obs": c(self._obs[newest]), "reward": c(self._reward[newest]),
+                         "discount": c(self._discount[newest]), "step_type": c(self._step_type[newest])},
+              "episodes": self._episodes_state()}
+        if include_replay:
+            sd["replay"] = {k: c(v) for k, v in self.ring().items()}
+        return sd
+
+    def load_state_dict(self, sd):
+        """Without the ring in `sd` the ring restarts from the newest slot alone (SAC's rule).  A checkpoint written with
+        another `members`, dropout, utd or ln_eps is refused."""
+        if sd.get("members") != self.P:
+            raise ValueError(f"the checkpoint was written with members = {sd.get('members', 'nothing')}, this population "
+                             f"has members = {self.P}")
+        mine = {"dropout": self.dropout, "utd": self.utd, "ln_eps": self.ln_eps}
+        for k, v in mine.items():
+            if "droq" not in sd or sd["droq"].get(k) != v:
+                got = sd.get("droq", {}).get(k, "nothing")
+                raise ValueError(f"the checkpoint was written with {k} = {got}, this population has {k} = {v}")
+        self.actor.load_state_dict(sd["actor"])   # (in place)
+        for group, key in ((self.critics, "critics"), (self.targets, "targets")):
+            for m, s in zip(group, sd[key]):
+                m.load_state_dict(s)
+        with torch.no_grad():
+            self.log_alpha.copy_(sd["log_alpha"])
+            self.gamma.copy_(sd["gamma"])
+            self.target_entropy.copy_(sd["target_entropy"])
+        for k, s in sd["optimizers"].items():
+            getattr(self, k + "_optimizer").load_state_dict(copy.deepcopy(s))   # (Adam would adopt sd's own tensors)
+        self._load_shared_state(sd)
+        self.seed, self._round, self.n_written = int(sd["seed"]), int(sd["round"]), int(sd["n_written"])
+        self._gen.set_state(sd["generator"])
+        if "replay" in sd:
+            for k, v in sd["replay"].items():
+                self.ring()[k].copy_(v)
+        else:
+            self._step_type.fill_(STEP_LAST)
+        newest = (self.n_written - 1) % self.C if self.n_written else 0
+        for buf, key in ((self._obs, "obs"), (self._reward, "reward"), (self._discount, "discount"),
+                         (self._step_type, "step_type")):
+            buf[newest].copy_(sd["newest"][key])
+
+
+def _row(values, fmt="{:9.4f}"):
+    return " ".join(fmt.format(float(v)) for v in values)
+
+
+def train_and_evaluate(env, rounds: int, members: int, steps_per_round: int = 16, grad_steps: int = 1,
+                       time_limit: float = None, log=print, **kwargs):
+    """What the examples' --train-population does: `rounds` rounds of a `DroQPopulation` of `members` on `env` (a
+    batched Environment), one line per round with every member's mean return of the episodes that ended in it and the
+    smallest and largest temperature, then one deterministic episode of every env through a MidiEvaluationWrapper and
+    every member's precision, recall and F1 (the mean over its envs).  Stops early after `time_limit` seconds.  Returns
+    (population, log of the rounds, metrics: name -> [P] array)."""
+    import time
+    from robopianist_amd.wrappers import CanonicalSpecWrapper, MidiEvaluationWrapper
+    pop = DroQPopulation(env, members, **kwargs)
+    P = pop.P
+    t0 = time.perf_counter()
+    rounds_log = []
+    last_mean = np.full(P, np.nan)
+
+    def report(i, s):
+        rounds_log.append(s)
+        ended = s["episodes"] > 0
+        last_mean[ended] = s["mean_return"][ended]
+        # (a member none of whose episodes ended in the round shows the mean of the last round in which some did)
+        alpha = s.get("alpha", np.full(P, np.nan))
+        log(f"update {i + 1:4d}  episodes {int(s['episodes'].sum()):6d}  mean return per member {_row(last_mean)}  "
+            f"alpha {float(np.min(alpha)):8.5f} .. {float(np.max(alpha)):8.5f}  {time.perf_counter() - t0:7.1f} s")
+
+    for i in range(int(rounds)):
+        pop.train(1, steps_per_round, grad_steps, callback=lambda _, s, i=i: report(i, s))
+        if time_limit is not None and time.perf_counter() - t0 > time_limit:
+            log(f"stopped after {i + 1} updates: the time limit of {time_limit:.0f} s")
+            break
+    evaluated = CanonicalSpecWrapper(MidiEvaluationWrapper(pop.env))
+    ts = evaluated.reset()
+    done = torch.zeros(pop.E, dtype=torch.bool, device=ts.step_type.device)
+    for _ in range(100000):
+        ts = evaluated.step(pop.act(ts.observation, deterministic=True))
+        done |= ts.last()
+        if bool(done.all()):
+            break
+    per_env = evaluated.get_musical_metrics_per_env()
+    metrics = {k: torch.nanmean(v.view(pop.Em, P), dim=0).cpu().numpy() for k, v in per_env.items()}
+    for k, v in metrics.items():
+        log(f"\t{k} per member: {_row(v, '{:.4f}')}")
+    return pop, rounds_log, metrics

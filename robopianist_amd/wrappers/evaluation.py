@@ -102,3 +102,13 @@ class MidiEvaluationWrapper:
         allv = (self._hist * valid[..., None]).sum((0, 1)) / valid.sum()
         names = ["precision", "recall", "f1", "sustain_precision", "sustain_recall", "sustain_f1"]
         return {k: float(v) for k, v in zip(names, allv)}
+
+    def get_musical_metrics_per_env(self) -> Dict[str, torch.Tensor]:
+        """Every env's mean over its last `deque_size` finished episodes: name -> [E] float64 on the device; NaN for an
+        env without a finished episode."""
+        n = torch.clamp(self._n_finished, max=self._deque_size)
+        valid = torch.arange(self._deque_size, device=n.device)[None, :] < n[:, None]
+        per = (self._hist * valid[..., None]).sum(1) / torch.clamp(n, min=1)[:, None]
+        per = torch.where((n > 0)[:, None], per, torch.full_like(per, float("nan")))
+        names = ["precision", "recall", "f1", "sustain_precision", "sustain_recall", "sustain_f1"]
+        return {k: per[:, i] for i, k in enumerate(names)}
