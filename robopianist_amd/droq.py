@@ -5,8 +5,9 @@ unchanged; the critics are Linear -> Dropout -> LayerNorm -> ReLU twice and `utd
 The entry point is a module function taking raw device addresses (`target`); it enqueues one kernel on the caller's HIP
 stream and reads nothing back.  An actor step draws its utd x B rows with one `rp_sac_sample` launch and acts on all
 their next observations with one `rp_sac_act` launch; every critic step is one `rp_droq_target` launch on its B rows
-plus plain torch (the loss, autograd with torch's own dropout, Adam, the Polyak step).  Like the engine, the library has
-no CPU fallback: a missing library is an error.
+plus plain torch (the loss, autograd with torch's own dropout, Adam, the Polyak step), or, with
+`DroQ(critic_step="fused")`, plus the two launches of `critic.step` (include/learn/rp_critic.h), whose dropout masks are
+a function of (seed, round) too.  Like the engine, the library has no CPU fallback: a missing library is an error.
 """
 
 from __future__ import annotations
@@ -14,7 +15,7 @@ from __future__ import annotations
 import ctypes
 import os
 
-from robopianist_amd import _abi, offpolicy
+from robopianist_amd import _abi, critic, offpolicy
 from robopianist_amd.learning import LearnError, Mlp, _train_and_evaluate
 from robopianist_amd.offpolicy import SAC, _masked_mean, actor_loss, alpha_loss, critic_loss, squashed_gaussian
 
@@ -111,10 +112,18 @@ class DroQ(SAC):
     `update(g)` takes g actor steps.  Each draws utd x `batch_size` rows in one sampler launch and acts on all their
     next observations in one launch (the actor does not change in between); critic step u then computes its TD target
     on the rows [u B, (u + 1) B) with `rp_droq_target`, whose dropout masks come from the learner's (seed, round), and
-    takes its Adam and Polyak steps in torch.  The actor and the temperature step on the last range."""
+    takes its Adam and Polyak steps in torch.  The actor and the temperature step on the last range.
 
-    def __init__(self, env, *sac_args, dropout: float = 0.01, utd: int = 20, ln_eps: float = 1e-5, **sac_kwargs):
+    `critic_step`: "torch" (the default: autograd with torch's own dropout, torch's Adam, `_foreach_lerp_`) or "fused"
+    (`critic.step`: the same step in two launches, with Philox dropout masks keyed by (seed, round, row); the learner
+    then owns Adam's m and v and its step count, and torch's critic optimiser stays unused)."""
+
+    def __init__(self, env, *sac_args, dropout: float = 0.01, utd: int = 20, ln_eps: float = 1e-5,
+                 critic_step: str = "torch", **sac_kwargs):
         self.dropout, self.utd, self.ln_eps = float(dropout), int(utd), float(ln_eps)
+        if critic_step not in ("torch", "fused"):
+            raise ValueError(f'critic_step must be "torch" or "fused", got {critic_step!r}')
+        self.critic_mode = critic_step
         if not 0.0 <= self.dropout < 1.0:
             raise ValueError(f"dropout must lie in [0, 1), got {dropout}")
         if self.utd < 1:
@@ -130,6 +139,13 @@ class DroQ(SAC):
         self._u_reward, self._u_discount, self._u_mask = z(n), z(n), z(n)
         self._u_next_action, self._u_next_logp, self._u_y = z(n, A), z(n), z(n)
         self._set_range(self.utd - 1)
+        if self.critic_mode == "fused":
+            import torch
+            self._c_m = [[torch.zeros_like(t) for t in self._critic_tensors(c)] for c in self.critics]
+            self._c_v = [[torch.zeros_like(t) for t in self._critic_tensors(c)] for c in self.critics]
+            self._c_t = 0                                                    # Adam's step count, shared by all parameters
+            self._c_bytes = critic.workspace_bytes(self.n_critics, self.H1, self.H2, self.B)
+            self._c_ws, self._u_q = z(max(self._c_bytes // 4, 1)), z(self.n_critics, n)
 
     def _net(self, n_in, n_out):
         """SAC's constructor draws the actor (n_out = 2 A) and then the critics (n_out = 1) through here."""
@@ -141,15 +157,19 @@ class DroQ(SAC):
                              nn.Linear(self.H1, self.H2), nn.Dropout(p), nn.LayerNorm(self.H2, eps), nn.ReLU(),
                              nn.Linear(self.H2, 1))
 
-    def _critic_table(self, net):
-        """`net` as rp_droq_critic: the addresses of the parameters as they are now."""
+    def _critic_tensors(self, net):
+        """The ten parameters of `net` in rp_droq_critic's order, as they are now."""
         import torch
         tensors = [t for i in (0, 4, 8) for t in (net[i].weight, net[i].bias)]
         tensors += [t for i in (2, 6) for t in (net[i].weight, net[i].bias)]
         for t in tensors:
             if not t.is_contiguous() or t.dtype != torch.float32:
                 raise LearnError(f"{self._reads} contiguous float32 parameters")
-        return critic_entry(tensors)
+        return tensors
+
+    def _critic_table(self, net):
+        """`net` as rp_droq_critic: the addresses of the parameters as they are now."""
+        return critic_entry(self._critic_tensors(net))
 
     # -- the minibatch ---------------------------------------------------------------------------------------------------
     def _set_range(self, u):
@@ -196,10 +216,45 @@ class DroQ(SAC):
         return batch
 
     # -- the gradient steps ----------------------------------------------------------------------------------------------
-    def critic_step(self, batch):
-        """The critics' Adam step on `batch` (torch's own dropout: the modules are in train() mode) and the targets'
-        Polyak step over all parameters, LayerNorm's included.  Returns the loss (a tensor)."""
+    def _fused_range(self, batch):
+        """The range u whose views `batch` holds (what `target_range(u)` and `minibatch()` return)."""
+        D, B = self.D, self.B
+        off = batch["obs"].data_ptr() - self._u_obs.data_ptr()
+        u = off // (4 * D * B)
+        if off < 0 or off % (4 * D * B) or u >= self.utd or batch["obs"].shape[0] != B or \
+                any(batch[k].data_ptr() != getattr(self, "_u_" + k)[u * B:].data_ptr() for k in ("action", "y", "mask")):
+            raise LearnError('critic_step="fused" steps on a range of the learner\'s own minibatch: pass what '
+                             "target_range(u) or minibatch() returned")
+        return u
+
+    def _fused_critic_step(self, u, loss):
+        """`critic.step` on range u: two launches; the loss (from the step's q, y and mask) only where asked for."""
         import torch
+        group = self.critic_optimizer.param_groups[0]
+        self._c_t += 1
+        step_size, bc2_sqrt = critic.adam_scalars(group["lr"], self._c_t, group["betas"])
+        sets = lambda nets: [critic.set_entry(self._critic_tensors(net)) for net in nets]
+        B, n = self.B, self.utd * self.B
+        with torch.cuda.device(self._dev):
+            critic.step(self._u_obs.data_ptr(), self._u_action.data_ptr(), self._u_y.data_ptr(), self._u_mask.data_ptr(),
+                        self._mean_f32.data_ptr(), self._inv_std_f32.data_ptr(), self.obs_clip, sets(self.critics),
+                        [critic.set_entry(m) for m in self._c_m], [critic.set_entry(v) for v in self._c_v],
+                        sets(self.targets), self._u_q.data_ptr(), self._c_ws.data_ptr(), self._c_bytes, self.D, self.H1,
+                        self.H2, self.A, n, step_size, bc2_sqrt, eps=group["eps"], betas=group["betas"], tau=self.tau,
+                        threshold=self._threshold, keep_scale=self._keep_scale, ln_eps=self.ln_eps, seed=self.seed,
+                        round_=self._round, row_first=u * B, row_count=B, hip_stream=self._stream())
+        if not loss:
+            return None
+        r = slice(u * B, (u + 1) * B)
+        return critic_loss(list(self._u_q[:, r]), self._u_y[r], self._u_mask[r])
+
+    def critic_step(self, batch, loss: bool = True):
+        """The critics' Adam step on `batch` (torch's own dropout: the modules are in train() mode) and the targets'
+        Polyak step over all parameters, LayerNorm's included.  Returns the loss (a tensor).  With critic_step="fused":
+        the two launches of `critic.step` on the range `batch` views, and the loss only if `loss`."""
+        import torch
+        if self.critic_mode == "fused":
+            return self._fused_critic_step(self._fused_range(batch), loss)
         xa = torch.cat([self.normalize(batch["obs"]), batch["action"]], dim=1)
         lc = critic_loss([c(xa).squeeze(-1) for c in self.critics], batch["y"], batch["mask"])
         self.critic_optimizer.zero_grad(set_to_none=True)
@@ -240,20 +295,30 @@ class DroQ(SAC):
         if self.n_written < 2:
             raise LearnError("update() needs at least two TimeSteps in the ring: call collect() first")
         stats = {}
-        for _ in range(int(g)):
+        for k in range(int(g)):
             self.draw_and_act()
             for u in range(self.utd):
                 batch = self.target_range(u)
-                lc = self.critic_step(batch)
-            stats = dict({"critic_loss": lc}, **self.actor_step(batch))
+                if self.critic_mode == "fused":   # (the loss costs torch launches: only where it is returned)
+                    lc = self.critic_step(batch, loss=u == self.utd - 1 and k == int(g) - 1)
+                else:
+                    lc = self.critic_step(batch)
+            stats = dict({} if lc is None else {"critic_loss": lc}, **self.actor_step(batch))
+            if self.critic_mode == "fused":
+                self.critic_optimizer.zero_grad(set_to_none=True)   # (the actor pass's critic gradients: nobody reads them)
             self._round += 1
         return {k: float(v) for k, v in stats.items()}
 
     # -- checkpoint / resume -------------------------------------------------------------------------------------------
     def state_dict(self, include_replay: bool = False):
-        """SAC's (Module.state_dict carries the LayerNorm parameters), plus "dropout", "utd" and "ln_eps"."""
+        """SAC's (Module.state_dict carries the LayerNorm parameters), plus "dropout", "utd" and "ln_eps"; with
+        critic_step="fused" also the mode and the critics' Adam state (m, v per tensor and the step count)."""
         sd = super().state_dict(include_replay)
         sd["droq"] = {"dropout": self.dropout, "utd": self.utd, "ln_eps": self.ln_eps}
+        if self.critic_mode == "fused":
+            sd["droq"]["critic_step"] = "fused"
+            c = lambda group: [[t.detach().clone() for t in net] for net in group]
+            sd["critic_adam"] = {"m": c(self._c_m), "v": c(self._c_v), "t": self._c_t}
         return sd
 
     def load_state_dict(self, sd):
@@ -262,7 +327,17 @@ class DroQ(SAC):
             if "droq" not in sd or sd["droq"].get(k) != v:
                 got = sd.get("droq", {}).get(k, "nothing")
                 raise ValueError(f"the checkpoint was written with {k} = {got}, this learner has {k} = {v}")
+        got = sd["droq"].get("critic_step", "torch")
+        if got != self.critic_mode:
+            raise ValueError(f"the checkpoint was written with critic_step = {got}, this learner has critic_step = "
+                             f"{self.critic_mode}")
         super().load_state_dict(sd)
+        if self.critic_mode == "fused":
+            for mine, theirs in ((self._c_m, sd["critic_adam"]["m"]), (self._c_v, sd["critic_adam"]["v"])):
+                for net, src in zip(mine, theirs):
+                    for t, s_ in zip(net, src):
+                        t.copy_(s_)
+            self._c_t = int(sd["critic_adam"]["t"])
 
 
 def train_and_evaluate(env, rounds: int, steps_per_round: int = 16, grad_steps: int = 1, time_limit: float = None,
