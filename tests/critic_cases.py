@@ -4,7 +4,8 @@ second float32 restatement in another summation order, computed once per case fo
 not depend on how many critics the launch holds, so n critics' reference is the first n of the four.
 
 A case is (rows, D, H1, H2, A, p): droq_cases.CASES, plus one whose 70 rows exceed two stages (32 rows each) of the apply
-launch's reduction by 6, which is no multiple of 16, and whose last row tile holds 6 rows.  Every fourth row has mask 0.
+launch's reduction by 6, which is no multiple of 16, and whose last row tile holds 6 rows.  WIDE_CASES are droq_cases.WIDE_CASES: the row counts
+that are multiples of the tile and the stage, D + A = 16 and 64, and H1 < H2.  Every fourth row has mask 0.
 The modes: "on" (dropout p) and "off" (drop_threshold 0, keep_scale 1) start from non-trivial m and v at Adam's step 3;
 "first" (FIRST_CASE only, dropout on) is step 1 from zero m and v.  The live critics and the targets are different
 networks.  Scalars reach the twin as the float32 values the argument block carries.
@@ -35,7 +36,13 @@ CASES = list(dc.CASES) + [(70, 20, 32, 32, 6, 0.25)]
 FIRST_CASE = CASES[1]
 # chosen once, on the CPU, so that test_critic_host's conditioning check holds (it asserts it); nothing a kernel computed
 SEEDS = {CASES[0]: 67, CASES[1]: 210, CASES[2]: 38, CASES[3]: 89, CASES[4]: 1842}
+# droq_cases.WIDE_CASES (it says what each is for): full tiles and exact stages of rows, D + A a multiple of 16, H1 < H2,
+# 16 <-> 256.  Their seeds by the same rule, each the first from 0 that passes on the CPU.
+WIDE_CASES = list(dc.WIDE_CASES)
+SEEDS.update({WIDE_CASES[0]: 148, WIDE_CASES[1]: 144, WIDE_CASES[2]: 4244, WIDE_CASES[3]: 57})
+ALL_CASES = CASES + WIDE_CASES
 N_CRITICS = (1, 2, 3, 4)
+WIDE_N_CRITICS = (1, 4)   # of the wide cases in the GPU tests
 SEED, ROUND = (5 << 32) | 13, 6
 LN_EPS, CLIP, LR, TAU, EPS, BETAS = 1e-5, 5.0, 1e-2, 0.05, 1e-8, (0.9, 0.999)
 KINDS = ("grad", "p", "m", "v", "target")

@@ -134,8 +134,30 @@ def test_the_batch_sums_of_the_twin_follow_the_header():
     assert rows > critic.dim("stage_rows") and (rows % critic.dim("stage_rows")) % 16 != 0
 
 
+def test_the_wide_cases_are_what_the_first_five_are_not():
+    tile, stage = critic.dim("tile_rows"), critic.dim("stage_rows")
+    # the first five: no row count is a multiple of the tile, no D + A is, no H1 < H2
+    assert all(c[0] % tile and (c[1] + c[4]) % 16 and c[2] >= c[3] for c in cc.CASES)
+    assert cc.WIDE_CASES == dc.WIDE_CASES and len(cc.ALL_CASES) == 9 and len(set(cc.ALL_CASES)) == 9
+    assert set(cc.SEEDS) == set(cc.ALL_CASES) and set(dc.SEEDS) == set(dc.ALL_CASES) and len(dc.ALL_CASES) == 8
+    a, b, c, d = cc.WIDE_CASES
+    # every wide case: only full tiles (the last tile has no invalid row)
+    assert all(w[0] % tile == 0 for w in cc.WIDE_CASES)
+    # a: H1 < H2 (the transposed layer has K = H2 > N = H1; w2's apply blocks are H1 / 16 of N = H2), exactly one stage
+    assert a[2] < a[3] and a[0] == stage
+    # b: one full tile, fewer rows than a stage, D + A one exact column tile of w1
+    assert b[0] == tile < stage and b[1] + b[4] == 16
+    # c: the narrowest layer into the widest, D + A four exact column tiles, two exact stages (the prefetch of the apply
+    # launch's reduction is skipped after a full stage), five vector blocks of which the last holds 49 elements
+    assert (c[2], c[3]) == (16, learning.MAX_HIDDEN) and (c[1] + c[4]) % 16 == 0 and c[0] == 2 * stage
+    V = 3 * c[2] + 4 * c[3] + 1
+    assert V == 1073 and -(-V // 256) == 5 and V - 4 * 256 == 49
+    # d: the widest into the narrowest, a full stage plus a full tile
+    assert (d[2], d[3]) == (learning.MAX_HIDDEN, 16) and d[0] == stage + tile
+
+
 # ---- the conditioning of the GPU cases -----------------------------------------------------------------------------------
-@pytest.mark.parametrize("case", cc.CASES, ids=cc.case_id)
+@pytest.mark.parametrize("case", cc.ALL_CASES, ids=cc.case_id)
 def test_gpu_cases_are_well_conditioned(case):
     p = cc.problem(case)
     assert case[0] >= 5 and (p.kw["mask"] == 0).any() and (p.kw["mask"] == 1).any()

@@ -131,7 +131,19 @@ def test_the_sums_of_the_twin_follow_the_header():
 
 
 # ---- the conditioning of the GPU cases -----------------------------------------------------------------------------------
-@pytest.mark.parametrize("case", dc.CASES, ids=dc.case_id)
+def test_the_wide_cases_are_what_the_first_four_are_not():
+    tile = droq.dim("tile_rows")
+    assert all(c[0] % tile and (c[1] + c[4]) % 16 and c[2] >= c[3] for c in dc.CASES)
+    assert dc.ALL_CASES == dc.CASES + dc.WIDE_CASES and len(set(dc.ALL_CASES)) == 8 and set(dc.SEEDS) == set(dc.ALL_CASES)
+    a, b, c, d = dc.WIDE_CASES
+    assert all(w[0] % tile == 0 for w in dc.WIDE_CASES)                  # only full tiles: no invalid row in the last one
+    assert a[2] < a[3] and a[0] == 2 * tile                              # H1 < H2
+    assert b[0] == tile and b[1] + b[4] == 16                            # one full tile; D + A = 16
+    assert (c[2], c[3]) == (16, learning.MAX_HIDDEN) and (c[1] + c[4]) % 32 == 0   # narrowest into widest; exact k stages
+    assert (d[2], d[3]) == (learning.MAX_HIDDEN, 16) and d[0] == 3 * tile           # widest into narrowest
+
+
+@pytest.mark.parametrize("case", dc.ALL_CASES, ids=dc.case_id)
 def test_gpu_cases_are_well_conditioned(case):
     p = dc.problem(case)
     assert case[0] >= 5

@@ -12,7 +12,11 @@ piano -- the worst ratio of the kernels' error to the restatement's among the 51
 digits printed: with every product taken as the header's fused-multiply-add chain the restatement errs as the kernels do.  (With
 numpy's products in the restatement, which sum in blocks and err less than a chain, the ratios reached 7.4 and one
 single-number output, v3.b3 of a step-1 case, stood at 8.13.)  Against torch's own float32 step without dropout the worst
-outputs of the five cases lie between 2.0 and 3.8 restatement errors.  The toy task went from a mean reward of -0.3737
+outputs of the five cases lie between 2.0 and 3.8 restatement errors.  Over the wide cases (critic_cases.WIDE_CASES: full
+tiles, exact stages, D + A = 16 and 64, H1 < H2) and the tests added with them -- the deep range, the two launches, tau at
+its ends, the two masks, the dead layer -- the worst ratio is again 1.000 in every line (profiles/droq_wide_gpu_tests.txt);
+against torch's own step the wide cases' worst outputs lie between 2.5 and 4.9 restatement errors (the 4.9: grad1.g1 of
+(64, 44, 16, 256, 20, 0.25), 2.98e-08 | 6.05e-09).  The toy task went from a mean reward of -0.3737
 over the first 5 rounds to -0.0411 over the last 5 of 40 (ratio 0.110; with the torch critic step test_gpu_droq.py
 records 0.111).
 """
@@ -30,19 +34,23 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import critic_cases as cc  # noqa: E402
 import critic_reference as cr  # noqa: E402
 import droq_cases as dc  # noqa: E402
-from test_gpu_droq import TOY  # noqa: E402
+from test_gpu_droq import DEEP_B, DEEP_FIRST, TOY, deep  # noqa: E402
 from test_gpu_offpolicy import POISON, _ToyEnv, _dev, _piano_env, _same_bits, _stream, _up  # noqa: E402
 from robopianist_amd import critic, droq, offpolicy  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 
-def _run_step(p, n, mode="on", first=0, count=None, round_=cc.ROUND, **override):
-    """The step on the first n critics of case p; -> the flat dict of critic_cases (q: the rows of the range), "q_all"."""
-    rows, D, H1, H2, A, _ = p.case
+def _run_step(p, n, mode="on", first=0, count=None, round_=cc.ROUND, launches=(critic.STEP,), grad=True, tau=cc.TAU, **override):
+    """The step on the first n critics of case p; -> the flat dict of critic_cases (q: the rows of the range), "q_all".
+    `override`: inputs that are not p.kw's (the batch is as long as its obs).  `launches`: the `launches` of successive
+    calls on the same tensors and workspace; with more than one -> the list of the dicts after each call.  `grad`: whether
+    the call gets gradient pointers (without them the dict has no gradient keys)."""
+    _, D, H1, H2, A, _ = p.case
+    kw, md = dict(p.kw, **override), p.mode[mode]
+    rows = len(kw["obs"])
     count = rows - first if count is None else count
     dev = _dev()
-    kw, md = dict(p.kw, **override), p.mode[mode]
     d = {k: _up(kw[k]) for k in ("obs", "action", "y", "mask", "mean", "inv_std")}
     up = lambda group: [[_up(a) for a in net] for net in group[:n]]
     P, T, M, V = up(kw["critics"]), up(kw["targets"]), up(md["m"]), up(md["v"])
@@ -51,36 +59,51 @@ def _run_step(p, n, mode="on", first=0, count=None, round_=cc.ROUND, **override)
     nbytes = critic.workspace_bytes(n, H1, H2, count)
     ws = torch.full((max(nbytes // 4, 1),), float("nan"), device=dev)
     sets = lambda group: [critic.set_entry(net) for net in group]
-    critic.step(d["obs"].data_ptr(), d["action"].data_ptr(), d["y"].data_ptr(), d["mask"].data_ptr(), d["mean"].data_ptr(),
-                d["inv_std"].data_ptr(), cc.CLIP, sets(P), sets(M), sets(V), sets(T), q.data_ptr(), ws.data_ptr(), nbytes,
-                D, H1, H2, A, rows, md["step_size"], md["bc2_sqrt"], eps=cc.EPS, betas=cc.BETAS, tau=cc.TAU, grad=sets(G),
-                threshold=md["threshold"], keep_scale=md["keep_scale"], ln_eps=cc.LN_EPS, seed=cc.SEED, round_=round_,
-                row_first=first, row_count=count, hip_stream=_stream())
-    torch.cuda.synchronize()
     host = lambda group: [[t.cpu().numpy() for t in net] for net in group]
-    q = q.cpu().numpy()
-    out = cc.flat({"q": q[:, first:first + count], "grad": host(G), "p": host(P), "m": host(M), "v": host(V), "target": host(T)})
-    out["q_all"] = q
-    return out
+    outs = []
+    for launch in launches:
+        critic.step(d["obs"].data_ptr(), d["action"].data_ptr(), d["y"].data_ptr(), d["mask"].data_ptr(), d["mean"].data_ptr(),
+                    d["inv_std"].data_ptr(), cc.CLIP, sets(P), sets(M), sets(V), sets(T), q.data_ptr(), ws.data_ptr(), nbytes,
+                    D, H1, H2, A, rows, md["step_size"], md["bc2_sqrt"], eps=cc.EPS, betas=cc.BETAS, tau=tau,
+                    grad=sets(G) if grad else None, threshold=md["threshold"], keep_scale=md["keep_scale"], ln_eps=cc.LN_EPS,
+                    seed=cc.SEED, round_=round_, row_first=first, row_count=count, launches=launch, hip_stream=_stream())
+        torch.cuda.synchronize()
+        q_all = q.cpu().numpy()
+        out = cc.flat({"q": q_all[:, first:first + count], "grad": host(G), "p": host(P), "m": host(M), "v": host(V), "target": host(T)})
+        if not grad:
+            assert all((g == POISON).all() for net in host(G) for g in net)
+            out = {k: v for k, v in out.items() if not k.startswith("grad")}
+        out["q_all"] = q_all
+        outs.append(out)
+    return outs[0] if len(outs) == 1 else outs
+
+
+def _inputs(p, n, mode="on"):
+    """What _run_step uploads for the p, m, v and target tensors, under the keys of its dict."""
+    kw, md = p.kw, p.mode[mode]
+    groups = {"p": kw["critics"], "m": md["m"], "v": md["v"], "target": kw["targets"]}
+    return {f"{kind}{i}.{name}": a for kind, group in groups.items() for i in range(n) for name, a in zip(cr.PARAMS, group[i])}
 
 
 def _within(got, ref, err32, label):
     pairs = {k: (float(np.abs(np.asarray(got[k], np.float64) - ref[k]).max()), err32[k]) for k in ref}
-    worst = max(pairs, key=lambda k: pairs[k][0] / pairs[k][1] if pairs[k][1] > 0 else (np.inf if pairs[k][0] > 0 else 0.0))
+    ratio = lambda k: pairs[k][0] / pairs[k][1] if pairs[k][1] > 0 else (np.inf if pairs[k][0] > 0 else 0.0)
+    worst = max(pairs, key=ratio)
     show = [k for k in pairs if k in ("q0", "grad0.w1", "p0.w1", "m0.w1", "v0.w1", "target0.w1")] + [worst]
     print(f"{label}: kernel error | float32 restatement error: " +
-          ", ".join(f"{k} {pairs[k][0]:.2e} | {pairs[k][1]:.2e}" for k in dict.fromkeys(show)) + f" (worst ratio: {worst})")
+          ", ".join(f"{k} {pairs[k][0]:.2e} | {pairs[k][1]:.2e}" for k in dict.fromkeys(show)) +
+          f" (worst ratio: {worst} {ratio(worst):.3f})")
     for k, (e, b) in pairs.items():
         assert got[k].shape == ref[k].shape and e <= 8 * b, (label, k, e, b)
 
 
-@pytest.mark.parametrize("case", cc.CASES, ids=cc.case_id)
+@pytest.mark.parametrize("case", cc.ALL_CASES, ids=cc.case_id)
 def test_step_equals_the_float64_twin_within_8_float32_restatement_errors(case):
     p = cc.problem(case)
     for mode in cc.modes(case):
         if mode == "off":
             continue
-        for n in cc.N_CRITICS:
+        for n in (cc.N_CRITICS if case in cc.CASES else cc.WIDE_N_CRITICS):
             got = _run_step(p, n, mode)
             _within(cc.first(got, n), cc.first(p.ref[mode], n), p.err32[mode], f"step {case} {mode} critics {n}")
             assert all(np.isfinite(v).all() for v in got.values())
@@ -106,7 +129,7 @@ def test_step_is_deterministic_the_round_changes_it_and_the_masks_are_the_twins(
             assert np.abs(other[k] - moved[k]).max() < 0.01 * np.abs(moved[k] - wrong[k]).max()
 
 
-@pytest.mark.parametrize("case", cc.CASES, ids=cc.case_id)
+@pytest.mark.parametrize("case", cc.ALL_CASES, ids=cc.case_id)
 def test_step_without_dropout_is_torchs_own_step(case):
     p = cc.problem(case)
     rows, D, H1, H2, A, _ = case
@@ -125,11 +148,17 @@ def test_step_without_dropout_is_torchs_own_step(case):
     assert not missed, (case, missed)
 
 
-@pytest.mark.parametrize("case", [cc.CASES[2], cc.CASES[4]], ids=cc.case_id)
+def _row_ranges(case):
+    """The wide case: a tile-aligned inner range, one exact stage, the last row alone."""
+    rows = case[0]
+    return ((16, 32), (0, 32), (63, 1)) if case == cc.WIDE_CASES[2] else ((3, rows - 7), (rows - 1, 1), (0, 17))
+
+
+@pytest.mark.parametrize("case", [cc.CASES[2], cc.CASES[4], cc.WIDE_CASES[2]], ids=cc.case_id)
 def test_step_row_ranges_read_and_write_nothing_outside(case):
     p = cc.problem(case)
     rows = case[0]
-    for first, count in ((3, rows - 7), (rows - 1, 1), (0, 17)):
+    for first, count in _row_ranges(case):
         inside = np.zeros(rows, bool); inside[first:first + count] = True
         fill = lambda value: {k: np.where(inside.reshape((-1,) + (1,) * (p.kw[k].ndim - 1)), p.kw[k], np.float32(value))
                               for k in ("obs", "action", "y", "mask")}
@@ -157,6 +186,110 @@ def test_an_all_masked_range_is_adams_step_on_a_zero_gradient():
             for kind, w in zip(("p", "m", "v", "target"), want):
                 assert _same_bits(got[f"{kind}{i}.{name}"], w), (kind, i, name)
     assert np.isfinite(got["q_all"]).all()
+
+
+def _twin(p, n, mode="on", first=0, count=None, scalars=None, **override):
+    """The float64 twin and the float32 restatement's error on inputs that are not the case's own, computed here."""
+    md = dict(p.mode[mode], **(scalars or {}))
+    kw = dict(p.kw, **override)
+    kw.update(critics=kw["critics"][:n], targets=kw["targets"][:n])
+    run = lambda **o: cc.flat(cr.step(**kw, **md, row_first=first, row_count=count, **o), n)
+    ref = run(dtype=np.float64)
+    return ref, cc.errors(run(dtype=np.float32), ref)
+
+
+@pytest.mark.parametrize("case", [cc.CASES[4], cc.WIDE_CASES[0]], ids=cc.case_id)
+def test_the_two_launches_make_the_step(case):
+    """ROWS_ONLY and APPLY_ONLY, the modes tools/gpu/critic_bench.py times, are the two launches of a step: the first
+    writes q and the workspace only, the second on that workspace leaves what one STEP call leaves."""
+    p, rows, n = cc.problem(case), case[0], 2
+    before = _inputs(p, n)
+    for first, count in ((0, rows), (5, rows - 9)):
+        inside = np.zeros(rows, bool); inside[first:first + count] = True
+        step = _run_step(p, n, first=first, count=count)
+        rows_only, both = _run_step(p, n, first=first, count=count, launches=(critic.ROWS_ONLY, critic.APPLY_ONLY))
+        assert [k for k, a in before.items() if not _same_bits(rows_only[k], a)] == []
+        assert all((rows_only[k] == POISON).all() for k in rows_only if k.startswith("grad"))
+        assert (rows_only["q_all"][:, ~inside] == POISON).all() and _same_bits(rows_only["q_all"], step["q_all"])
+        assert set(both) == set(step) and [k for k in step if not _same_bits(both[k], step[k])] == [], (first, count)
+        assert all(not np.array_equal(step[k], a) for k, a in before.items())
+
+
+def test_the_step_without_gradient_pointers_is_the_step_with_them():
+    p, n = cc.problem(cc.WIDE_CASES[3]), 2
+    with_, without = _run_step(p, n), _run_step(p, n, grad=False)
+    kept = [k for k in with_ if not k.startswith("grad")]
+    assert set(without) == set(kept) and len(kept) == 1 + n * (1 + 4 * len(cr.PARAMS))
+    assert [k for k in kept if not _same_bits(without[k], with_[k])] == []
+    assert all((with_[k] != POISON).all() for k in with_ if k.startswith("grad"))
+
+
+def test_tau_at_its_ends():
+    case = cc.CASES[4]
+    p, n = cc.problem(case), 2
+    base, before = _run_step(p, n), _inputs(p, n)
+    # tau = 0: the targets keep their bits; the critics and their moments step as ever
+    still = _run_step(p, n, tau=0.0)
+    for k in base:
+        assert _same_bits(still[k], before[k] if k.startswith("target") else base[k]), k
+    # tau = 1: the twin's t + (p - t) 1, which need not round to p
+    ref, err32 = _twin(p, n, scalars=dict(tau=1.0))
+    full = _run_step(p, n, tau=1.0)
+    _within(cc.first(full, n), ref, err32, f"step {case} tau 1")
+    assert all(_same_bits(full[k], base[k]) for k in base if not k.startswith("target"))
+    assert all(not np.array_equal(full[k], base[k]) for k in base if k.startswith("target"))
+
+
+def test_step_deep_in_a_batch_differs_by_addresses_and_masks_only():
+    """test_gpu_droq's deep range on the step: rows [1024, 1040) of a batch of 1040 whose other rows are NaN."""
+    case = cc.WIDE_CASES[1]
+    p, rows, n = cc.problem(case), case[0], 2
+    far = deep(p.kw, ("obs", "action", "y", "mask"), rows)
+    far = {k: far[k] for k in ("obs", "action", "y", "mask")}
+    inside = np.zeros(DEEP_B, bool); inside[DEEP_FIRST:] = True
+    for mode in ("off", "on"):
+        compact = _run_step(p, n, mode)
+        got = _run_step(p, n, mode, first=DEEP_FIRST, count=rows, **far)
+        assert all(np.isfinite(v).all() for v in got.values())
+        assert (got["q_all"][:, ~inside] == POISON).all() and got["q_all"].shape == (n, DEEP_B)
+        there = {k: v for k, v in got.items() if k != "q_all"}
+        if mode == "off":
+            assert [k for k in there if not _same_bits(there[k], compact[k])] == []
+        else:
+            assert all(not np.array_equal(there[f"q{i}"], compact[f"q{i}"]) for i in range(n))
+        ref, err32 = _twin(p, n, mode, first=DEEP_FIRST, count=rows, **far)
+        _within(there, ref, err32, f"step {case} rows [{DEEP_FIRST}, {DEEP_B}) dropout {mode}")
+
+
+def test_a_mask_sum_between_0_and_1_clamps_to_1_and_one_row_of_a_partial_tile_carries_a_step():
+    case = cc.CASES[4]
+    p, rows, n = cc.problem(case), case[0], 2
+    quarter, last = np.zeros(rows, np.float32), np.zeros(rows, np.float32)
+    quarter[[1, 33, 69]] = 0.25                                          # MSUM = 0.75: M = 1, not 0.75
+    last[rows - 1] = 1.0                                                 # row 5 of the last tile's 6
+    assert rows % 16 == 6 and cr.mask_sum(quarter) == np.float32(0.75)
+    for label, mask in (("three rows of mask 0.25", quarter), ("the last row alone", last)):
+        ref, err32 = _twin(p, n, mask=mask)
+        got = _run_step(p, n, mask=mask)
+        _within(cc.first(got, n), ref, err32, f"step {case} {label}")
+        assert all(got[k].any() and ref[k].any() for k in ref if k.startswith("grad")), label
+
+
+def test_a_dead_first_layer_has_variance_0_and_the_other_critic_does_not_see_it():
+    """w1 = 0 and b1 = 0 in critic 0: every row of its layer 1 is 0 before LayerNorm, so 1 / sigma = 1 / sqrt(ln_eps)
+    carries its backward pass (and o1 = 0: g1's gradient is 0).  Critic 1, in the same launches, is not touched."""
+    case = cc.WIDE_CASES[0]
+    p, n = cc.problem(case), 2
+    critics = [list(net) for net in p.kw["critics"]]
+    critics[0][0], critics[0][1] = np.zeros_like(critics[0][0]), np.zeros_like(critics[0][1])
+    base, got = _run_step(p, n), _run_step(p, n, critics=critics)
+    assert all(np.isfinite(v).all() for v in got.values())
+    ref, err32 = _twin(p, n, critics=critics)
+    _within(cc.first(got, n), ref, err32, f"step {case} critic 0's first layer dead")
+    own = lambda k, i: k.split(".")[0].endswith(str(i))
+    assert [k for k in base if k != "q_all" and own(k, 1) and not _same_bits(got[k], base[k])] == []
+    assert not got["grad0.g1"].any() and got["grad0.w1"].any() and got["grad0.be1"].any()
+    assert not np.array_equal(got["q0"], base["q0"])
 
 
 # ---- the learner ---------------------------------------------------------------------------------------------------------

@@ -9,6 +9,10 @@ requested member and row ranges are seen untouched.  act and target are also hel
 test_gpu_offpolicy.py and test_gpu_droq.py: 8 times the error of a float32 numpy restatement on the same inputs,
 computed by the test.
 
+Measured on an MI355X (profiles/droq_wide_gpu_tests.txt): the target test also runs on droq_cases.WIDE_CASES (full tiles,
+D + A = 16 and 64, H1 < H2, 16 <-> 256); the bits are the single-learner kernel's in every one, and the worst ratio of the
+kernel's error to the restatement's per line lies between 1.2 and 2.7 there (between 1.0 and 3.6 over the four old cases).
+
 The toy task.  `_ToyEnv` with a reward that depends on the member: -mean((a - c_p obs[:2] / 2)^2), c_p = +1 for even
 members and -1 for odd ones, so one shared policy cannot be optimal for both.  The criterion is PPO's for EVERY member.
 The hyper-parameters (TOY) were fixed once, before any GPU run, from a CPU restatement of the same algorithm in torch
@@ -55,7 +59,9 @@ def _bar(got, ref, f32, keys, label):
     """8 times the float32 restatement's own error against the float64 twin."""
     pairs = {k: (float(np.abs(got[k].astype(np.float64) - ref[k]).max()),
                  float(np.abs(f32[k].astype(np.float64) - ref[k]).max())) for k in keys}
-    print(f"{label}: kernel error | float32 restatement error: " + ", ".join(f"{k} {e:.2e} | {b:.2e}" for k, (e, b) in pairs.items()))
+    worst = max((e / b if b > 0 else (np.inf if e > 0 else 0.0)) for e, b in pairs.values())
+    print(f"{label}: kernel error | float32 restatement error: " + ", ".join(f"{k} {e:.2e} | {b:.2e}" for k, (e, b) in pairs.items()) +
+          f" (worst ratio: {worst:.2f})")
     for k, (e, b) in pairs.items():
         assert e <= 8 * b, (label, k, e, b)
 
@@ -313,7 +319,7 @@ def _flat(out):
 
 
 @pytest.mark.parametrize("P", TARGET_P)
-@pytest.mark.parametrize("case", dc.CASES, ids=dc.case_id)
+@pytest.mark.parametrize("case", dc.ALL_CASES, ids=dc.case_id)
 def test_target_equals_the_single_learner_kernel_per_member_and_range_bit_for_bit(case, P):
     prob = _target_problem(case, P)
     n = prob.n
