@@ -118,8 +118,9 @@ def main() -> None:
                     help="train a policy with droq.DroQ for that many rounds (16 control steps and one actor step of 20 "
                          "critic steps each) instead; prints the same lines and the F1 of the trained policy at the end")
     ap.add_argument("--fused-critic", action="store_true",
-                    help="--train-droq: take the critic steps with the fused HIP step (droq.DroQ(critic_step=\"fused\")) "
-                         "instead of torch's autograd, Adam and lerp")
+                    help="--train-droq, --train-population: take the critic steps with the fused HIP step "
+                         "(droq.DroQ / population.DroQPopulation(critic_step=\"fused\")) instead of torch's autograd, "
+                         "Adam and lerp")
     ap.add_argument("--train-population", type=int, default=0, metavar="ROUNDS",
                     help="train --members independent DroQ learners (population.DroQPopulation; member p owns the envs "
                          "e %% members == p) for that many rounds instead; prints the same lines and the F1, per member")
@@ -144,8 +145,8 @@ def main() -> None:
             warnings.simplefilter("ignore")
             return _load(args, n_envs)
 
-    if args.fused_critic and not args.train_droq > 0:
-        ap.error("--fused-critic goes with --train-droq")
+    if args.fused_critic and not (args.train_droq > 0 or args.train_population > 0):
+        ap.error("--fused-critic goes with --train-droq or --train-population")
     if (args.train_ppo > 0) + (args.train_sac > 0) + (args.train_droq > 0) + (args.train_population > 0) > 1:
         ap.error("--train-ppo, --train-sac, --train-droq and --train-population are four learners: choose one")
     if args.train_population > 0:
@@ -160,7 +161,8 @@ def main() -> None:
             warnings.simplefilter("ignore")
             env = _load_members(args, args.n_envs, names)
         population.train_and_evaluate(env, args.train_population, args.members, time_limit=args.time_limit, seed=args.seed,
-                                      batch_size=max(1, min(4096, 16 * args.n_envs) // args.members))
+                                      batch_size=max(1, min(4096, 16 * args.n_envs) // args.members),
+                                      critic_step="fused" if args.fused_critic else "torch")
         return
     if args.train_droq > 0:
         if (args.fingertip_pianist or args.plan or args.action_sequence or args.pixels or args.hear or args.record

@@ -1,5 +1,5 @@
-"""What the ctypes bindings of the HIP libraries share: the library opener (all twelve bindings) and the entry table of the
-libraries whose entry points take one argument block each (planning, learning, offpolicy, droq, population, critic)."""
+"""What the ctypes bindings of the HIP libraries share: the library opener (all thirteen bindings) and the entry table of the
+libraries whose entry points take one argument block each (planning, learning, offpolicy, droq, population, critic, pop_critic)."""
 
 from __future__ import annotations
 

@@ -1,5 +1,5 @@
 // rp_abi_host.hpp -- the host side that the libraries whose entry points take one argument block each share
-// (rp_plan.hip, rp_learn.hip, rp_sac.hip, rp_droq.hip, rp_pop.hip): the thread-local message behind <prefix>last_error, the head of an entry point
+// (rp_plan.hip, rp_learn.hip, rp_sac.hip, rp_droq.hip, rp_pop.hip, rp_critic.hip, rp_pop_critic.hip): the thread-local message behind <prefix>last_error, the head of an entry point
 // and the launch grid's size.  Everything here has internal linkage, so each library has a message of its own.
 #ifndef RP_ABI_HOST_HPP_
 #define RP_ABI_HOST_HPP_

@@ -3,7 +3,9 @@
 //
 // The checks are host code and touch no device: a refused call returns its message before anything is launched.  The
 // device text is parametrised as rp_droq.hpp's: a row map resolved at compile time (the kernels of librp_critic.so pass
-// the identity) and the weight sets in use, by value, so that a population can run it on a member's rows and slices.
+// the identity) and the weight sets in use, by value, so that a population can run it on a member's rows and slices:
+// `member` (0 in librp_critic.so, where the compiler folds it away) selects the slice of stacked tensors [P][...] whose
+// bases the sets hold.
 #ifndef RP_CRITIC_HPP_
 #define RP_CRITIC_HPP_
 
@@ -96,6 +98,17 @@ namespace {
 struct RpcSets {
   rp_critic_set p[RP_DROQ_MAX_CRITICS], m[RP_DROQ_MAX_CRITICS], v[RP_DROQ_MAX_CRITICS], t[RP_DROQ_MAX_CRITICS], g[RP_DROQ_MAX_CRITICS];
 };
+
+// The elements of tensor `which` of a critic: what lies between two members' slices of a stacked tensor.
+__device__ inline size_t rpc_elems(int which, int K, int H1, int H2) {
+  switch (which) {
+    case RP_CRITIC_W1: return (size_t)H1 * K;
+    case RP_CRITIC_W2: return (size_t)H2 * H1;
+    case RP_CRITIC_B1: case RP_CRITIC_G1: case RP_CRITIC_BE1: return (size_t)H1;
+    case RP_CRITIC_B3: return 1;
+    default: return (size_t)H2;   // b2, w3, g2, be2
+  }
+}
 
 // rpl_layer (rp_mlp_tile.hpp) with the weights behind a loader too: acc[i] (column tile wave + 4 i) = the chain over k
 // ascending, from 0, of load_a(r, k) load_w(n, k).  kColFast says which index is consecutive in memory and so which one
@@ -329,7 +342,7 @@ __device__ inline void rpc_store(const f32x4 (&acc)[RPL_ACC], const float* __res
 // array row (the masks' row too).  All 256 threads call it together.
 template <typename Rows>
 __device__ __forceinline__ void rpc_rows_tile(const rp_critic_step_args& a, const RpcSets& sets, const Rows rows, int tile, int i,
-                                              float* ws, float* lds) {
+                                              float* ws, float* lds, const size_t member = 0) {
   float* sa = lds;
   float* sw = sa + RPL_TILE_R * RPL_S_PITCH;
   float* st = sw + RP_LEARN_MAX_H * RPL_S_PITCH;    // sums, then gradients   (16 x 34 and 256 x 34 floats: 16-byte multiples)
@@ -346,7 +359,9 @@ __device__ __forceinline__ void rpc_rows_tile(const rp_critic_step_args& a, cons
   const int l0 = tile * RPL_TILE_R;
   const bool valid = l0 + r < R;
   const long long e = valid ? rows((long long)a.row_first + l0 + r) : 0;
-  const rp_critic_set P = sets.p[i];
+  rp_critic_set P = sets.p[i];
+#pragma unroll
+  for (int k = 0; k < RP_CRITIC_PARAMS; k++) P.t[k] += member * rpc_elems(k, D + A, H1, H2);
   const uint32_t ctr = RP_CRITIC_COUNTER + 2u * (uint32_t)i;
 
   // M: the header's MSUM
@@ -471,9 +486,9 @@ __device__ inline void rpc_adam(const rp_critic_step_args& a, const RpcSets& set
 }
 
 // Adam on the 16 x N tile of a weight matrix [N][K] whose gradient `acc` holds: row 4 kq + reg is column k0 + .. of the
-// matrix, the accumulator's column its row n.
+// matrix, the accumulator's column its row n.  `base`: the matrix's first element in the tensor (a member's slice).
 __device__ inline void rpc_adam_tile(const rp_critic_step_args& a, const RpcSets& sets, int i, int which, const f32x4 (&acc)[RPL_ACC],
-                                     int k0, int K, int N) {
+                                     int k0, int K, int N, size_t base) {
   const int tid = (int)threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int r16 = lane & 15, kq = lane >> 4;
 #pragma unroll
@@ -483,7 +498,7 @@ __device__ inline void rpc_adam_tile(const rp_critic_step_args& a, const RpcSets
 #pragma unroll
       for (int reg = 0; reg < 4; reg++) {
         const int k = k0 + 4 * kq + reg;
-        if (k < K) rpc_adam(a, sets, i, which, (size_t)n * K + k, acc[t][reg]);
+        if (k < K) rpc_adam(a, sets, i, which, base + (size_t)n * K + k, acc[t][reg]);
       }
     }
   }
@@ -492,7 +507,7 @@ __device__ inline void rpc_adam_tile(const rp_critic_step_args& a, const RpcSets
 // The apply launch: block `blk` of critic i.  `lds`: the two staging arrays of rpc_layer.
 template <typename Rows>
 __device__ __forceinline__ void rpc_apply_block(const rp_critic_step_args& a, const RpcSets& sets, const Rows rows, int blk, int i,
-                                                const float* ws, float* lds) {
+                                                const float* ws, float* lds, const size_t member = 0) {
   float* sa = lds;
   float* sw = sa + RPL_TILE_R * RPL_S_PITCH;
   const int D = a.D, A = a.A, H1 = a.H1, H2 = a.H2, R = a.row_count;
@@ -509,7 +524,7 @@ __device__ __forceinline__ void rpc_apply_block(const rp_critic_step_args& a, co
           return rpc_x(a, rows((long long)a.row_first + l), k0 + rr);
         },
         [&](int n, int l) { return ds1[(size_t)l * H1 + n]; }, R, H1, sa, sw, acc);
-    rpc_adam_tile(a, sets, i, RP_CRITIC_W1, acc, k0, D + A, H1);
+    rpc_adam_tile(a, sets, i, RP_CRITIC_W1, acc, k0, D + A, H1, member * rpc_elems(RP_CRITIC_W1, D + A, H1, H2));
     return;
   }
   blk -= tiles1;
@@ -519,7 +534,7 @@ __device__ __forceinline__ void rpc_apply_block(const rp_critic_step_args& a, co
     const float* ds2 = wsc + lay.ds2;
     rpc_layer<true>([&](int rr, int l) { return out1[(size_t)l * H1 + k0 + rr]; },
                     [&](int n, int l) { return ds2[(size_t)l * H2 + n]; }, R, H2, sa, sw, acc);
-    rpc_adam_tile(a, sets, i, RP_CRITIC_W2, acc, k0, H1, H2);
+    rpc_adam_tile(a, sets, i, RP_CRITIC_W2, acc, k0, H1, H2, member * rpc_elems(RP_CRITIC_W2, D + A, H1, H2));
     return;
   }
   blk -= tiles2;
@@ -537,7 +552,7 @@ __device__ __forceinline__ void rpc_apply_block(const rp_critic_step_args& a, co
   else if ((idx -= H2) < H2) which = RP_CRITIC_BE2;
   else if ((idx -= H2) < H2) which = RP_CRITIC_W3;
   else { idx -= H2; which = RP_CRITIC_B3; }
-  rpc_adam(a, sets, i, which, (size_t)idx, g);
+  rpc_adam(a, sets, i, which, member * rpc_elems(which, D + A, H1, H2) + (size_t)idx, g);
 }
 
 }  // namespace

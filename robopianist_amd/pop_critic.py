@@ -1,0 +1,95 @@
+"""ctypes binding of the population's fused critic step (include/learn/rp_pop_critic.h, librp_pop_critic.so): `critic.step`
+for every member of a population in the same two launches, on the members' blocked rows, their slices of the stacked
+tensors and one workspace segment each.
+
+The entry points are module functions taking raw device addresses (`step`, `workspace_bytes`); `step` enqueues its two
+kernels on the caller's HIP stream and reads nothing back.  `population.DroQPopulation(critic_step="fused")` is the
+learner that uses it.  Like the engine, the library has no CPU fallback: a missing library is an error.
+"""
+
+from __future__ import annotations
+
+import ctypes
+import os
+
+from robopianist_amd import _abi, critic
+from robopianist_amd.critic import APPLY_ONLY, COUNTER, MAX_CRITICS, PARAMS, ROWS_ONLY, STEP, Set, adam_scalars, set_entry, set_table  # noqa: F401
+from robopianist_amd.learning import LearnError
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+LIB_PATH = os.environ.get("RP_POP_CRITIC_LIB") or os.path.join(_HERE, "csrc", "librp_pop_critic.so")
+
+EXPORTED_SYMBOLS = ("rp_pop_critic_step", "rp_pop_critic_workspace", "rp_pop_critic_dim", "rp_pop_critic_last_error")
+
+TILE_MAJOR, MEMBER_MAJOR = 0, 1      # the workgroup order of both launches (speed only): population's
+
+_lib = None
+
+_p, _i, _u32, _f, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_float, ctypes.c_size_t
+
+
+class StepArgs(ctypes.Structure):
+    _fields_ = [("struct_size", _sz), ("obs", _p), ("action", _p), ("y", _p), ("mask", _p), ("mean", _p), ("inv_std", _p),
+                ("obs_clip", _f), ("p", ctypes.POINTER(Set)), ("m", ctypes.POINTER(Set)), ("v", ctypes.POINTER(Set)),
+                ("target", ctypes.POINTER(Set)), ("grad", ctypes.POINTER(Set)), ("n_critics", _i), ("q", _p),
+                ("workspace", _p), ("workspace_bytes", _sz), ("drop_threshold", _u32), ("keep_scale", _f), ("ln_eps", _f),
+                ("seed_lo", _u32), ("seed_hi", _u32), ("round", _u32), ("one_minus_beta1", _f), ("beta2", _f),
+                ("one_minus_beta2", _f), ("step_size", _f), ("bc2_sqrt", _f), ("eps", _f), ("tau", _f), ("D", _i),
+                ("H1", _i), ("H2", _i), ("A", _i), ("P", _i), ("n", _i), ("grid_order", _i), ("member_first", _i),
+                ("member_count", _i), ("row_first", _i), ("row_count", _i), ("launches", _i), ("hip_stream", _p)]
+
+
+class WorkspaceArgs(ctypes.Structure):
+    _fields_ = [("struct_size", _sz), ("n_critics", _i), ("H1", _i), ("H2", _i), ("row_count", _i), ("member_count", _i),
+                ("bytes", _sz)]
+
+
+_ARGS = {"step": StepArgs, "workspace": WorkspaceArgs}
+
+
+def load_library(path: str = LIB_PATH):
+    """Loads librp_pop_critic.so; raises LearnError if it has not been built."""
+    global _lib
+    if _lib is None:
+        _lib = declare(_abi.open_library(path, "population critic step", LearnError))
+    return _lib
+
+
+_entries = _abi.EntryTable("rp_pop_critic_", _ARGS, LearnError, load_library)
+make_args, call_raw, last_error, dim, _call = (_entries.make_args, _entries.call_raw, _entries.last_error, _entries.dim,
+                                               _entries.call)
+
+
+def declare(L, prefix: str = "rp_pop_critic_"):
+    """Declares the ABI's prototypes on a loaded library whose symbols start with `prefix`."""
+    return _entries.declare(L, prefix)
+
+
+def workspace_bytes(n_critics, H1, H2, row_count, member_count) -> int:
+    """The bytes `step` needs as its workspace for these sizes: `member_count` segments of `critic.workspace_bytes`."""
+    a = make_args("workspace", n_critics=n_critics, H1=H1, H2=H2, row_count=row_count, member_count=member_count)
+    if call_raw("workspace", a) != 0:
+        raise LearnError(last_error())
+    return int(a.bytes)
+
+
+def step(obs, action, y, mask, mean, inv_std, obs_clip, p, m, v, target, q, workspace, workspace_bytes_, D, H1, H2, A, P, n,
+         step_size, bc2_sqrt, eps=1e-8, betas=(0.9, 0.999), tau=0.005, grad=None, threshold=0, keep_scale=1.0, ln_eps=1e-5,
+         seed=0, round_=0, member_first=0, member_count=None, row_first=0, row_count=None, grid_order=None, launches=STEP,
+         hip_stream=None):
+    """`p`, `m`, `v`, `target` (and `grad`, optional): sequences of `Set` of the bases of the stacked tensors [P][...],
+    one per critic.  `n`: minibatch rows per member; the arrays hold P n rows, member p's at [p n, (p + 1) n).
+    `step_size`, `bc2_sqrt`: `adam_scalars(lr, t)`, shared by the members."""
+    tp = set_table(p)
+    k = len(tp)
+    tm, tv, tt = set_table(m, k), set_table(v, k), set_table(target, k)
+    tg = None if grad is None else set_table(grad, k)
+    _call("step", obs=obs, action=action, y=y, mask=mask, mean=mean, inv_std=inv_std, obs_clip=float(obs_clip), p=tp, m=tm,
+          v=tv, target=tt, grad=tg, n_critics=k, q=q, workspace=workspace, workspace_bytes=int(workspace_bytes_),
+          drop_threshold=int(threshold), keep_scale=float(keep_scale), ln_eps=float(ln_eps),
+          one_minus_beta1=1.0 - betas[0], beta2=betas[1], one_minus_beta2=1.0 - betas[1], step_size=float(step_size),
+          bc2_sqrt=float(bc2_sqrt), eps=float(eps), tau=float(tau), D=D, H1=H1, H2=H2, A=A, P=P, n=n,
+          grid_order=dim("default_grid_order") if grid_order is None else int(grid_order), member_first=member_first,
+          member_count=P - member_first if member_count is None else member_count, row_first=row_first,
+          row_count=n - row_first if row_count is None else row_count, launches=int(launches), hip_stream=hip_stream,
+          **_abi.seed_args(seed, round_))

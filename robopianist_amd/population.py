@@ -9,7 +9,9 @@ enqueues one kernel on the caller's HIP stream and reads nothing back.  They are
 stacked parameters.  The ring is SAC's [C][E]..., written by the learner's unchanged `pack`.  The gradient step is plain
 torch on stacked parameters [P][out][in] (`torch.baddbmm`): a loss is the sum over the members of the per-member masked
 means, so member p's gradient depends on member p's rows alone, and Adam, being element-wise, keeps the members
-independent.  Like the engine, the library has no CPU fallback: a missing library is an error.
+independent.  With `DroQPopulation(critic_step="fused")` the critic step is instead the two launches of
+`pop_critic.step` (include/learn/rp_pop_critic.h) for all members.  Like the engine, the library has no CPU fallback: a
+missing library is an error.
 """
 
 from __future__ import annotations
@@ -24,7 +26,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from robopianist_amd import _abi, droq
+from robopianist_amd import _abi, critic, droq, pop_critic
 from robopianist_amd.droq import Critic, drop_threshold
 from robopianist_amd.learning import STEP_FIRST, STEP_LAST, DeviceLearner, LearnError, Mlp
 from robopianist_amd.offpolicy import MAX_CRITICS, squashed_gaussian
@@ -267,15 +269,24 @@ class DroQPopulation(DeviceLearner):
 
     `collect(n)` launches, per control step, one `rp_pop_act` over all envs (each env by its member's actor), the env's
     step and `pack`, then one `rp_pop_moments` per contiguous run of new slots; nothing is read back.  `update(g)` is
-    DroQ's schedule with one `rp_pop_sample`, one `rp_pop_act` and, per range, one `rp_pop_target` for all members."""
+    DroQ's schedule with one `rp_pop_sample`, one `rp_pop_act` and, per range, one `rp_pop_target` for all members.
+
+    `critic_step`: "torch" (the default: autograd on the stacked tensors with torch's own dropout, torch's Adam,
+    `_foreach_lerp_`) or "fused" (`pop_critic.step`: the step of all members in two launches, with Philox dropout masks
+    keyed by (seed, round, row); the population then owns Adam's stacked m and v and one step count for all members,
+    and torch's critic optimiser stays unused) -- `droq.DroQ`'s contract."""
 
     _reads = "the population kernels read"
 
     def __init__(self, env, members: int, hidden=(256, 256), n_critics: int = 2, capacity: int = 64,
                  batch_size: int = 256, gamma=0.99, tau: float = 0.005, lr: float = 3e-4, init_alpha=1.0,
                  target_entropy=None, log_std_bounds=(-5.0, 2.0), learning_starts: int = 0, obs_clip: float = 10.0,
-                 seed: int = 0, norm_eps: float = 1e-8, dropout: float = 0.01, utd: int = 20, ln_eps: float = 1e-5):
+                 seed: int = 0, norm_eps: float = 1e-8, dropout: float = 0.01, utd: int = 20, ln_eps: float = 1e-5,
+                 critic_step: str = "torch"):
         super().__init__(env)
+        if critic_step not in ("torch", "fused"):
+            raise ValueError(f'critic_step must be "torch" or "fused", got {critic_step!r}')
+        self.critic_mode = critic_step
         self.P = int(members)
         if self.P < 1:
             raise ValueError(f"members must be >= 1, got {members}")
@@ -343,6 +354,12 @@ class DroQPopulation(DeviceLearner):
         self._u_reward, self._u_discount, self._u_mask = z(P * n), z(P * n), z(P * n)
         self._u_next_action, self._u_next_logp, self._u_y = z(P * n, A), z(P * n), z(P * n)
         self._range = self.utd - 1
+        if self.critic_mode == "fused":
+            self._c_m = [[torch.zeros_like(t) for t in self._critic_tensors(c)] for c in self.critics]
+            self._c_v = [[torch.zeros_like(t) for t in self._critic_tensors(c)] for c in self.critics]
+            self._c_t = 0                                  # Adam's step count: the members step together
+            self._c_bytes = pop_critic.workspace_bytes(self.n_critics, self.H1, self.H2, self.B, P)
+            self._c_ws, self._u_q = z(max(self._c_bytes // 4, 1)), z(self.n_critics, P * n)
 
     def _critic_net(self, n_in):
         """One member's critic, drawn as droq.DroQ draws it."""
@@ -393,11 +410,15 @@ class DroQPopulation(DeviceLearner):
             setattr(m, name, t.data_ptr())
         return m
 
-    def _critic_table(self, net):
-        """A stacked critic as rp_droq_critic."""
+    def _critic_tensors(self, net):
+        """The ten stacked parameters of `net` in rp_droq_critic's order, as they are now."""
         tensors = [t for i in (0, 4, 8) for t in (net[i].weight, net[i].bias)]
         tensors += [t for i in (2, 6) for t in (net[i].weight, net[i].bias)]
-        return droq.critic_entry(self._checked(tensors))
+        return self._checked(tensors)
+
+    def _critic_table(self, net):
+        """A stacked critic as rp_droq_critic."""
+        return droq.critic_entry(self._critic_tensors(net))
 
     def _act(self, obs, rows, layout, st, **out):
         act(obs.data_ptr(), self._mean_f32.data_ptr(), self._inv_std_f32.data_ptr(), self.obs_clip, self._actor_table(),
@@ -476,9 +497,50 @@ class DroQPopulation(DeviceLearner):
         self._range = u
         return self.minibatch()
 
-    def critic_step(self, batch):
+    def _fused_range(self, batch):
+        """The range u whose views `batch` holds (what `target_range(u)` and `minibatch()` return)."""
+        D, B, n = self.D, self.B, self.utd * self.B
+        obs = batch["obs"]
+        off = obs.data_ptr() - self._u_obs.data_ptr()
+        u = off // (4 * D * B)
+        if off < 0 or off % (4 * D * B) or u >= self.utd or tuple(obs.shape) != (self.P, B, D) or \
+                (self.P > 1 and obs.stride(0) != n * D) or \
+                any(batch[k].data_ptr() != getattr(self, "_u_" + k)[u * B:].data_ptr() or batch[k].shape[:2] != obs.shape[:2] or
+                    (self.P > 1 and batch[k].stride(0) != getattr(self, "_u_" + k)[0].numel() * n)
+                    for k in ("action", "y", "mask")):
+            raise LearnError('critic_step="fused" steps on a range of the population\'s own minibatches: pass what '
+                             "target_range(u) or minibatch() returned")
+        return u
+
+    def _fused_critic_step(self, u, loss):
+        """`pop_critic.step` on range u of all members: two launches; the per-member losses (from the step's q, y and
+        mask) only where asked for."""
+        group = self.critic_optimizer.param_groups[0]
+        self._c_t += 1
+        step_size, bc2_sqrt = critic.adam_scalars(group["lr"], self._c_t, group["betas"])
+        sets = lambda nets: [critic.set_entry(self._critic_tensors(net)) for net in nets]
+        P, B, n = self.P, self.B, self.utd * self.B
+        with torch.cuda.device(self._dev):
+            pop_critic.step(self._u_obs.data_ptr(), self._u_action.data_ptr(), self._u_y.data_ptr(),
+                            self._u_mask.data_ptr(), self._mean_f32.data_ptr(), self._inv_std_f32.data_ptr(), self.obs_clip,
+                            sets(self.critics), [critic.set_entry(m) for m in self._c_m],
+                            [critic.set_entry(v) for v in self._c_v], sets(self.targets), self._u_q.data_ptr(),
+                            self._c_ws.data_ptr(), self._c_bytes, self.D, self.H1, self.H2, self.A, P, n, step_size,
+                            bc2_sqrt, eps=group["eps"], betas=group["betas"], tau=self.tau, threshold=self._threshold,
+                            keep_scale=self._keep_scale, ln_eps=self.ln_eps, seed=self.seed, round_=self._round,
+                            row_first=u * B, row_count=B, hip_stream=self._stream())
+        if not loss:
+            return None
+        r = slice(u * B, (u + 1) * B)
+        v = lambda t: t.view(P, n)[:, r]
+        return critic_losses([v(q) for q in self._u_q], v(self._u_y), v(self._u_mask))
+
+    def critic_step(self, batch, loss: bool = True):
         """The critics' Adam step on `batch` ([P, n, ...]; torch's own dropout) and the targets' Polyak step over the
-        stacked tensors.  Returns the per-member losses [P] (a tensor)."""
+        stacked tensors.  Returns the per-member losses [P] (a tensor).  With critic_step="fused": the two launches of
+        `pop_critic.step` on the range `batch` views, and the losses only if `loss`."""
+        if self.critic_mode == "fused":
+            return self._fused_critic_step(self._fused_range(batch), loss)
         xa = torch.cat([self.normalize(batch["obs"]), batch["action"]], dim=2)
         per = critic_losses([c(xa).squeeze(-1) for c in self.critics], batch["y"], batch["mask"])
         self.critic_optimizer.zero_grad(set_to_none=True)
@@ -514,12 +576,17 @@ class DroQPopulation(DeviceLearner):
         if self.n_written < 2:
             raise LearnError("update() needs at least two TimeSteps in the ring: call collect() first")
         stats = {}
-        for _ in range(int(g)):
+        for k in range(int(g)):
             self.draw_and_act()
             for u in range(self.utd):
                 batch = self.target_range(u)
-                lc = self.critic_step(batch)
-            stats = dict({"critic_loss": lc}, **self.actor_step(batch))
+                if self.critic_mode == "fused":   # (the loss costs torch launches: only where it is returned)
+                    lc = self.critic_step(batch, loss=u == self.utd - 1 and k == int(g) - 1)
+                else:
+                    lc = self.critic_step(batch)
+            stats = dict({} if lc is None else {"critic_loss": lc}, **self.actor_step(batch))
+            if self.critic_mode == "fused":
+                self.critic_optimizer.zero_grad(set_to_none=True)   # (the actor pass's critic gradients: nobody reads them)
             self._round += 1
         if not stats:
             return {}
@@ -587,7 +654,8 @@ class DroQPopulation(DeviceLearner):
     # -- checkpoint / resume -------------------------------------------------------------------------------------------
     def state_dict(self, include_replay: bool = False):
         """SAC's contract on the stacked tensors, plus "members" and DroQ's "droq" block; the whole ring only with
-        `include_replay`.  With the env's own `state_dict()` the next `collect()` is resumed bit for bit."""
+        `include_replay`.  With the env's own `state_dict()` the next `collect()` is resumed bit for bit.  With
+        critic_step="fused" also the mode and the critics' Adam state (the stacked m, v per tensor and the step count)."""
         c = lambda t: t.detach().clone()
         nets = lambda ms: [{k: c(v) for k, v in m.state_dict().items()} for m in ms]
         newest = (self.n_written - 1) % self.C if self.n_written else 0
@@ -601,13 +669,17 @@ class DroQPopulation(DeviceLearner):
               "newest": {"obs": c(self._obs[newest]), "reward": c(self._reward[newest]),
                          "discount": c(self._discount[newest]), "step_type": c(self._step_type[newest])},
               "episodes": self._episodes_state()}
+        if self.critic_mode == "fused":
+            sd["droq"]["critic_step"] = "fused"
+            moments = lambda group: [[c(t) for t in net] for net in group]
+            sd["critic_adam"] = {"m": moments(self._c_m), "v": moments(self._c_v), "t": self._c_t}
         if include_replay:
             sd["replay"] = {k: c(v) for k, v in self.ring().items()}
         return sd
 
     def load_state_dict(self, sd):
         """Without the ring in `sd` the ring restarts from the newest slot alone (SAC's rule).  A checkpoint written with
-        another `members`, dropout, utd or ln_eps is refused."""
+        another `members`, dropout, utd, ln_eps or critic_step is refused."""
         if sd.get("members") != self.P:
             raise ValueError(f"the checkpoint was written with members = {sd.get('members', 'nothing')}, this population "
                              f"has members = {self.P}")
@@ -616,6 +688,10 @@ class DroQPopulation(DeviceLearner):
             if "droq" not in sd or sd["droq"].get(k) != v:
                 got = sd.get("droq", {}).get(k, "nothing")
                 raise ValueError(f"the checkpoint was written with {k} = {got}, this population has {k} = {v}")
+        got = sd["droq"].get("critic_step", "torch")
+        if got != self.critic_mode:
+            raise ValueError(f"the checkpoint was written with critic_step = {got}, this population has critic_step = "
+                             f"{self.critic_mode}")
         self.actor.load_state_dict(sd["actor"])   # (in place)
         for group, key in ((self.critics, "critics"), (self.targets, "targets")):
             for m, s in zip(group, sd[key]):
@@ -638,6 +714,12 @@ class DroQPopulation(DeviceLearner):
         for buf, key in ((self._obs, "obs"), (self._reward, "reward"), (self._discount, "discount"),
                          (self._step_type, "step_type")):
             buf[newest].copy_(sd["newest"][key])
+        if self.critic_mode == "fused":
+            for mine, theirs in ((self._c_m, sd["critic_adam"]["m"]), (self._c_v, sd["critic_adam"]["v"])):
+                for net, src in zip(mine, theirs):
+                    for t, s_ in zip(net, src):
+                        t.copy_(s_)
+            self._c_t = int(sd["critic_adam"]["t"])
 
 
 def _row(values, fmt="{:9.4f}"):
