@@ -35,15 +35,20 @@ class Set(ctypes.Structure):
     _fields_ = [("t", _p * len(PARAMS))]
 
 
+def step_fields(*rows):
+    """The fields of a step block: the fused step's, with the block's own row dimensions `rows` between A and row_first."""
+    return [("struct_size", _sz), ("obs", _p), ("action", _p), ("y", _p), ("mask", _p), ("mean", _p), ("inv_std", _p),
+            ("obs_clip", _f), ("p", ctypes.POINTER(Set)), ("m", ctypes.POINTER(Set)), ("v", ctypes.POINTER(Set)),
+            ("target", ctypes.POINTER(Set)), ("grad", ctypes.POINTER(Set)), ("n_critics", _i), ("q", _p),
+            ("workspace", _p), ("workspace_bytes", _sz), ("drop_threshold", _u32), ("keep_scale", _f), ("ln_eps", _f),
+            ("seed_lo", _u32), ("seed_hi", _u32), ("round", _u32), ("one_minus_beta1", _f), ("beta2", _f),
+            ("one_minus_beta2", _f), ("step_size", _f), ("bc2_sqrt", _f), ("eps", _f), ("tau", _f), ("D", _i),
+            ("H1", _i), ("H2", _i), ("A", _i), *rows, ("row_first", _i), ("row_count", _i), ("launches", _i),
+            ("hip_stream", _p)]
+
+
 class StepArgs(ctypes.Structure):
-    _fields_ = [("struct_size", _sz), ("obs", _p), ("action", _p), ("y", _p), ("mask", _p), ("mean", _p), ("inv_std", _p),
-                ("obs_clip", _f), ("p", ctypes.POINTER(Set)), ("m", ctypes.POINTER(Set)), ("v", ctypes.POINTER(Set)),
-                ("target", ctypes.POINTER(Set)), ("grad", ctypes.POINTER(Set)), ("n_critics", _i), ("q", _p),
-                ("workspace", _p), ("workspace_bytes", _sz), ("drop_threshold", _u32), ("keep_scale", _f), ("ln_eps", _f),
-                ("seed_lo", _u32), ("seed_hi", _u32), ("round", _u32), ("one_minus_beta1", _f), ("beta2", _f),
-                ("one_minus_beta2", _f), ("step_size", _f), ("bc2_sqrt", _f), ("eps", _f), ("tau", _f), ("D", _i),
-                ("H1", _i), ("H2", _i), ("A", _i), ("B", _i), ("row_first", _i), ("row_count", _i), ("launches", _i),
-                ("hip_stream", _p)]
+    _fields_ = step_fields(("B", _i))
 
 
 class WorkspaceArgs(ctypes.Structure):
@@ -106,18 +111,27 @@ def adam_scalars(lr, t, betas=(0.9, 0.999)):
     return float(lr) / (1.0 - betas[0] ** t), math.sqrt(1.0 - betas[1] ** t)
 
 
-def step(obs, action, y, mask, mean, inv_std, obs_clip, p, m, v, target, q, workspace, workspace_bytes_, D, H1, H2, A, B,
-         step_size, bc2_sqrt, eps=1e-8, betas=(0.9, 0.999), tau=0.005, grad=None, threshold=0, keep_scale=1.0, ln_eps=1e-5,
-         seed=0, round_=0, row_first=0, row_count=None, launches=STEP, hip_stream=None):
-    """`p`, `m`, `v`, `target` (and `grad`, optional): sequences of `Set`, one per critic.  `threshold`:
-    `droq.drop_threshold(p)`.  `step_size`, `bc2_sqrt`: `adam_scalars(lr, t)`."""
+def step_keywords(obs, action, y, mask, mean, inv_std, obs_clip, p, m, v, target, q, workspace, workspace_bytes_, D, H1, H2, A,
+                  rows, step_size, bc2_sqrt, eps=1e-8, betas=(0.9, 0.999), tau=0.005, grad=None, threshold=0, keep_scale=1.0,
+                  ln_eps=1e-5, seed=0, round_=0, row_first=0, row_count=None, launches=STEP, hip_stream=None):
+    """The keywords of a step block but its own row dimensions; `rows`: the rows that `row_count` defaults to the rest of."""
     tp = set_table(p)
     n = len(tp)
     tm, tv, tt = set_table(m, n), set_table(v, n), set_table(target, n)
     tg = None if grad is None else set_table(grad, n)
-    _call("step", obs=obs, action=action, y=y, mask=mask, mean=mean, inv_std=inv_std, obs_clip=float(obs_clip), p=tp, m=tm,
-          v=tv, target=tt, grad=tg, n_critics=n, q=q, workspace=workspace, workspace_bytes=int(workspace_bytes_),
-          drop_threshold=int(threshold), keep_scale=float(keep_scale), ln_eps=float(ln_eps),
-          one_minus_beta1=1.0 - betas[0], beta2=betas[1], one_minus_beta2=1.0 - betas[1], step_size=float(step_size),
-          bc2_sqrt=float(bc2_sqrt), eps=float(eps), tau=float(tau), D=D, H1=H1, H2=H2, A=A, B=B, row_first=row_first,
-          row_count=B - row_first if row_count is None else row_count, launches=int(launches), hip_stream=hip_stream, **_abi.seed_args(seed, round_))
+    return dict(obs=obs, action=action, y=y, mask=mask, mean=mean, inv_std=inv_std, obs_clip=float(obs_clip), p=tp, m=tm,
+                v=tv, target=tt, grad=tg, n_critics=n, q=q, workspace=workspace, workspace_bytes=int(workspace_bytes_),
+                drop_threshold=int(threshold), keep_scale=float(keep_scale), ln_eps=float(ln_eps),
+                one_minus_beta1=1.0 - betas[0], beta2=betas[1], one_minus_beta2=1.0 - betas[1], step_size=float(step_size),
+                bc2_sqrt=float(bc2_sqrt), eps=float(eps), tau=float(tau), D=D, H1=H1, H2=H2, A=A, row_first=row_first,
+                row_count=rows - row_first if row_count is None else row_count, launches=int(launches),
+                hip_stream=hip_stream, **_abi.seed_args(seed, round_))
+
+
+def step(obs, action, y, mask, mean, inv_std, obs_clip, p, m, v, target, q, workspace, workspace_bytes_, D, H1, H2, A, B,
+         step_size, bc2_sqrt, **options):
+    """`p`, `m`, `v`, `target` (and `grad`, optional): sequences of `Set`, one per critic.  `threshold`:
+    `droq.drop_threshold(p)`.  `step_size`, `bc2_sqrt`: `adam_scalars(lr, t)`.  `options`: `step_keywords`' (eps, betas,
+    tau, grad, threshold, keep_scale, ln_eps, seed, round_, row_first, row_count, launches, hip_stream)."""
+    _call("step", B=B, **step_keywords(obs, action, y, mask, mean, inv_std, obs_clip, p, m, v, target, q, workspace,
+                                       workspace_bytes_, D, H1, H2, A, B, step_size, bc2_sqrt, **options))

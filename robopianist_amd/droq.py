@@ -7,7 +7,8 @@ stream and reads nothing back.  An actor step draws its utd x B rows with one `r
 their next observations with one `rp_sac_act` launch; every critic step is one `rp_droq_target` launch on its B rows
 plus plain torch (the loss, autograd with torch's own dropout, Adam, the Polyak step), or, with
 `DroQ(critic_step="fused")`, plus the two launches of `critic.step` (include/learn/rp_critic.h), whose dropout masks are
-a function of (seed, round) too.  Like the engine, the library has no CPU fallback: a missing library is an error.
+a function of (seed, round) too.  What does not depend on the number of learners is `DroQCore`, which
+`population.DroQPopulation` shares.  Like the engine, the library has no CPU fallback: a missing library is an error.
 """
 
 from __future__ import annotations
@@ -105,21 +106,17 @@ def target(next_obs, action, logp, reward, discount, mean, inv_std, obs_clip, ga
           **_abi.seed_args(seed, round_))
 
 
-class DroQ(SAC):
-    """DroQ (Hiroe et al. 2022): `SAC` whose critics are Linear -> Dropout(`dropout`) -> LayerNorm -> ReLU twice, with
-    `utd` critic steps (the update-to-data ratio) per actor step.  The actor stays SAC's tanh network.
+class DroQCore:
+    """What the DroQ learners (`DroQ`, population's `DroQPopulation`) share, as a mixin in front of an
+    `offpolicy.ReplayLearner`: the hyper-parameters, the critic's architecture and its ten tensors, the utd ranges of the
+    minibatch, the schedule of `update()`, the bookkeeping of the fused critic step and the "droq" and "critic_adam" blocks
+    of the checkpoint.  A subclass states `draw_and_act()`, `target_range(u)`, the torch body of `critic_step()`,
+    `actor_step()`, `_fused_range()`, and of the fused step its workspace (`_workspace_bytes()`), its launch
+    (`_launch_critic_step()`) and its loss (`_range_loss(u)`)."""
 
-    `update(g)` takes g actor steps.  Each draws utd x `batch_size` rows in one sampler launch and acts on all their
-    next observations in one launch (the actor does not change in between); critic step u then computes its TD target
-    on the rows [u B, (u + 1) B) with `rp_droq_target`, whose dropout masks come from the learner's (seed, round), and
-    takes its Adam and Polyak steps in torch.  The actor and the temperature step on the last range.
+    _me = "learner"   # (how the checkpoint's refusals name the reader)
 
-    `critic_step`: "torch" (the default: autograd with torch's own dropout, torch's Adam, `_foreach_lerp_`) or "fused"
-    (`critic.step`: the same step in two launches, with Philox dropout masks keyed by (seed, round, row); the learner
-    then owns Adam's m and v and its step count, and torch's critic optimiser stays unused)."""
-
-    def __init__(self, env, *sac_args, dropout: float = 0.01, utd: int = 20, ln_eps: float = 1e-5,
-                 critic_step: str = "torch", **sac_kwargs):
+    def _init_droq(self, dropout, utd, ln_eps, critic_step):
         self.dropout, self.utd, self.ln_eps = float(dropout), int(utd), float(ln_eps)
         if critic_step not in ("torch", "fused"):
             raise ValueError(f'critic_step must be "torch" or "fused", got {critic_step!r}')
@@ -132,30 +129,32 @@ class DroQ(SAC):
             raise ValueError(f"ln_eps must be > 0, got {ln_eps}")
         self._threshold = drop_threshold(self.dropout)
         self._keep_scale = 1.0 / (1.0 - self.dropout)
-        super().__init__(env, *sac_args, **sac_kwargs)
-        # the minibatch: utd ranges of B rows, drawn and acted on at once
-        n, D, A, z = self.utd * self.B, self.D, self.A, self._zeros
+
+    def _init_ranges(self, n):
+        """The minibatch of n rows in all: utd ranges of B rows per learner, drawn and acted on at once; with
+        critic_step="fused" also Adam's m and v, its step count (one for all parameters), the workspace and the step's q."""
+        import torch
+        D, A, z = self.D, self.A, self._zeros
         self._u_obs, self._u_next, self._u_action = z(n, D), z(n, D), z(n, A)
         self._u_reward, self._u_discount, self._u_mask = z(n), z(n), z(n)
         self._u_next_action, self._u_next_logp, self._u_y = z(n, A), z(n), z(n)
-        self._set_range(self.utd - 1)
         if self.critic_mode == "fused":
-            import torch
             self._c_m = [[torch.zeros_like(t) for t in self._critic_tensors(c)] for c in self.critics]
             self._c_v = [[torch.zeros_like(t) for t in self._critic_tensors(c)] for c in self.critics]
-            self._c_t = 0                                                    # Adam's step count, shared by all parameters
-            self._c_bytes = critic.workspace_bytes(self.n_critics, self.H1, self.H2, self.B)
+            self._c_t = 0
+            self._c_bytes = self._workspace_bytes()
             self._c_ws, self._u_q = z(max(self._c_bytes // 4, 1)), z(self.n_critics, n)
 
-    def _net(self, n_in, n_out):
-        """SAC's constructor draws the actor (n_out = 2 A) and then the critics (n_out = 1) through here."""
+    def _draw_member(self):
+        """One learner's actor (SAC's tanh network) and critics, drawn in this order from torch's global generator."""
         from torch import nn
-        if n_out != 1:
-            return super()._net(n_in, n_out)
         p, eps = self.dropout, self.ln_eps
-        return nn.Sequential(nn.Linear(n_in, self.H1), nn.Dropout(p), nn.LayerNorm(self.H1, eps), nn.ReLU(),
-                             nn.Linear(self.H1, self.H2), nn.Dropout(p), nn.LayerNorm(self.H2, eps), nn.ReLU(),
-                             nn.Linear(self.H2, 1))
+        critic_net = lambda n_in: nn.Sequential(
+            nn.Linear(n_in, self.H1), nn.Dropout(p), nn.LayerNorm(self.H1, eps), nn.ReLU(),
+            nn.Linear(self.H1, self.H2), nn.Dropout(p), nn.LayerNorm(self.H2, eps), nn.ReLU(), nn.Linear(self.H2, 1))
+        return self._net(self.D, 2 * self.A), [critic_net(self.D + self.A) for _ in range(self.n_critics)]
+
+    _draw = _draw_member   # (a learner of one member; a population stacks its members' draws)
 
     def _critic_tensors(self, net):
         """The ten parameters of `net` in rp_droq_critic's order, as they are now."""
@@ -170,6 +169,99 @@ class DroQ(SAC):
     def _critic_table(self, net):
         """`net` as rp_droq_critic: the addresses of the parameters as they are now."""
         return critic_entry(self._critic_tensors(net))
+
+    # -- the gradient steps ----------------------------------------------------------------------------------------------
+    def _fused_critic_step(self, u, loss):
+        """The fused step on range u: two launches; the loss (from the step's q, y and mask) only where asked for."""
+        import torch
+        group = self.critic_optimizer.param_groups[0]
+        self._c_t += 1
+        step_size, bc2_sqrt = critic.adam_scalars(group["lr"], self._c_t, group["betas"])
+        sets = lambda nets: [critic.set_entry(self._critic_tensors(net)) for net in nets]
+        with torch.cuda.device(self._dev):
+            self._launch_critic_step(
+                self._u_obs.data_ptr(), self._u_action.data_ptr(), self._u_y.data_ptr(), self._u_mask.data_ptr(),
+                self._mean_f32.data_ptr(), self._inv_std_f32.data_ptr(), self.obs_clip, sets(self.critics),
+                [critic.set_entry(m) for m in self._c_m], [critic.set_entry(v) for v in self._c_v], sets(self.targets),
+                self._u_q.data_ptr(), self._c_ws.data_ptr(), self._c_bytes, self.D, self.H1, self.H2, self.A,
+                step_size=step_size, bc2_sqrt=bc2_sqrt, eps=group["eps"], betas=group["betas"], tau=self.tau,
+                threshold=self._threshold, keep_scale=self._keep_scale, ln_eps=self.ln_eps, seed=self.seed,
+                round_=self._round, row_first=u * self.B, row_count=self.B, hip_stream=self._stream())
+        return self._range_loss(u) if loss else None
+
+    def update(self, g: int = 1):
+        """g actor steps of utd critic steps each; returns the statistics of the last one (`_host_stats`)."""
+        if self.n_written < 2:
+            raise LearnError("update() needs at least two TimeSteps in the ring: call collect() first")
+        stats = {}
+        for k in range(int(g)):
+            self.draw_and_act()
+            for u in range(self.utd):
+                batch = self.target_range(u)
+                if self.critic_mode == "fused":   # (the loss costs torch launches: only where it is returned)
+                    lc = self.critic_step(batch, loss=u == self.utd - 1 and k == int(g) - 1)
+                else:
+                    lc = self.critic_step(batch)
+            stats = dict({} if lc is None else {"critic_loss": lc}, **self.actor_step(batch))
+            if self.critic_mode == "fused":
+                self.critic_optimizer.zero_grad(set_to_none=True)   # (the actor pass's critic gradients: nobody reads them)
+            self._round += 1
+        return self._host_stats(stats)
+
+    # -- checkpoint / resume -------------------------------------------------------------------------------------------
+    def state_dict(self, include_replay: bool = False):
+        """The replay learner's (Module.state_dict carries the LayerNorm parameters), plus "dropout", "utd" and "ln_eps";
+        with critic_step="fused" also the mode and the critics' Adam state (m, v per tensor and the step count)."""
+        sd = super().state_dict(include_replay)
+        sd["droq"] = {"dropout": self.dropout, "utd": self.utd, "ln_eps": self.ln_eps}
+        if self.critic_mode == "fused":
+            sd["droq"]["critic_step"] = "fused"
+            c = lambda group: [[t.detach().clone() for t in net] for net in group]
+            sd["critic_adam"] = {"m": c(self._c_m), "v": c(self._c_v), "t": self._c_t}
+        return sd
+
+    def load_state_dict(self, sd):
+        """A checkpoint written with another dropout, utd, ln_eps or critic_step is refused."""
+        mine = {"dropout": self.dropout, "utd": self.utd, "ln_eps": self.ln_eps}
+        for k, v in mine.items():
+            if "droq" not in sd or sd["droq"].get(k) != v:
+                got = sd.get("droq", {}).get(k, "nothing")
+                raise ValueError(f"the checkpoint was written with {k} = {got}, this {self._me} has {k} = {v}")
+        got = sd["droq"].get("critic_step", "torch")
+        if got != self.critic_mode:
+            raise ValueError(f"the checkpoint was written with critic_step = {got}, this {self._me} has critic_step = "
+                             f"{self.critic_mode}")
+        super().load_state_dict(sd)
+        if self.critic_mode == "fused":
+            for mine, theirs in ((self._c_m, sd["critic_adam"]["m"]), (self._c_v, sd["critic_adam"]["v"])):
+                for net, src in zip(mine, theirs):
+                    for t, s_ in zip(net, src):
+                        t.copy_(s_)
+            self._c_t = int(sd["critic_adam"]["t"])
+
+
+class DroQ(DroQCore, SAC):
+    """DroQ (Hiroe et al. 2022): `SAC` whose critics are Linear -> Dropout(`dropout`) -> LayerNorm -> ReLU twice, with
+    `utd` critic steps (the update-to-data ratio) per actor step.  The actor stays SAC's tanh network.
+
+    `update(g)` takes g actor steps.  Each draws utd x `batch_size` rows in one sampler launch and acts on all their
+    next observations in one launch (the actor does not change in between); critic step u then computes its TD target
+    on the rows [u B, (u + 1) B) with `rp_droq_target`, whose dropout masks come from the learner's (seed, round), and
+    takes its Adam and Polyak steps in torch.  The actor and the temperature step on the last range.
+
+    `critic_step`: "torch" (the default: autograd with torch's own dropout, torch's Adam, `_foreach_lerp_`) or "fused"
+    (`critic.step`: the same step in two launches, with Philox dropout masks keyed by (seed, round, row); the learner
+    then owns Adam's m and v and its step count, and torch's critic optimiser stays unused)."""
+
+    def __init__(self, env, *sac_args, dropout: float = 0.01, utd: int = 20, ln_eps: float = 1e-5,
+                 critic_step: str = "torch", **sac_kwargs):
+        self._init_droq(dropout, utd, ln_eps, critic_step)
+        super().__init__(env, *sac_args, **sac_kwargs)
+        self._init_ranges(self.utd * self.B)
+        self._set_range(self.utd - 1)
+
+    def _workspace_bytes(self):
+        return critic.workspace_bytes(self.n_critics, self.H1, self.H2, self.B)
 
     # -- the minibatch ---------------------------------------------------------------------------------------------------
     def _set_range(self, u):
@@ -227,25 +319,11 @@ class DroQ(SAC):
                              "target_range(u) or minibatch() returned")
         return u
 
-    def _fused_critic_step(self, u, loss):
-        """`critic.step` on range u: two launches; the loss (from the step's q, y and mask) only where asked for."""
-        import torch
-        group = self.critic_optimizer.param_groups[0]
-        self._c_t += 1
-        step_size, bc2_sqrt = critic.adam_scalars(group["lr"], self._c_t, group["betas"])
-        sets = lambda nets: [critic.set_entry(self._critic_tensors(net)) for net in nets]
-        B, n = self.B, self.utd * self.B
-        with torch.cuda.device(self._dev):
-            critic.step(self._u_obs.data_ptr(), self._u_action.data_ptr(), self._u_y.data_ptr(), self._u_mask.data_ptr(),
-                        self._mean_f32.data_ptr(), self._inv_std_f32.data_ptr(), self.obs_clip, sets(self.critics),
-                        [critic.set_entry(m) for m in self._c_m], [critic.set_entry(v) for v in self._c_v],
-                        sets(self.targets), self._u_q.data_ptr(), self._c_ws.data_ptr(), self._c_bytes, self.D, self.H1,
-                        self.H2, self.A, n, step_size, bc2_sqrt, eps=group["eps"], betas=group["betas"], tau=self.tau,
-                        threshold=self._threshold, keep_scale=self._keep_scale, ln_eps=self.ln_eps, seed=self.seed,
-                        round_=self._round, row_first=u * B, row_count=B, hip_stream=self._stream())
-        if not loss:
-            return None
-        r = slice(u * B, (u + 1) * B)
+    def _launch_critic_step(self, *block, **options):
+        critic.step(*block, self.utd * self.B, **options)
+
+    def _range_loss(self, u):
+        r = slice(u * self.B, (u + 1) * self.B)
         return critic_loss(list(self._u_q[:, r]), self._u_y[r], self._u_mask[r])
 
     def critic_step(self, batch, loss: bool = True):
@@ -289,55 +367,6 @@ class DroQ(SAC):
         """One critic step (with its Polyak step) and one actor and temperature step on `batch`: SAC's meaning."""
         lc = self.critic_step(batch)
         return dict({"critic_loss": lc}, **self.actor_step(batch))
-
-    def update(self, g: int = 1):
-        """g actor steps of utd critic steps each; returns the statistics of the last one as floats."""
-        if self.n_written < 2:
-            raise LearnError("update() needs at least two TimeSteps in the ring: call collect() first")
-        stats = {}
-        for k in range(int(g)):
-            self.draw_and_act()
-            for u in range(self.utd):
-                batch = self.target_range(u)
-                if self.critic_mode == "fused":   # (the loss costs torch launches: only where it is returned)
-                    lc = self.critic_step(batch, loss=u == self.utd - 1 and k == int(g) - 1)
-                else:
-                    lc = self.critic_step(batch)
-            stats = dict({} if lc is None else {"critic_loss": lc}, **self.actor_step(batch))
-            if self.critic_mode == "fused":
-                self.critic_optimizer.zero_grad(set_to_none=True)   # (the actor pass's critic gradients: nobody reads them)
-            self._round += 1
-        return {k: float(v) for k, v in stats.items()}
-
-    # -- checkpoint / resume -------------------------------------------------------------------------------------------
-    def state_dict(self, include_replay: bool = False):
-        """SAC's (Module.state_dict carries the LayerNorm parameters), plus "dropout", "utd" and "ln_eps"; with
-        critic_step="fused" also the mode and the critics' Adam state (m, v per tensor and the step count)."""
-        sd = super().state_dict(include_replay)
-        sd["droq"] = {"dropout": self.dropout, "utd": self.utd, "ln_eps": self.ln_eps}
-        if self.critic_mode == "fused":
-            sd["droq"]["critic_step"] = "fused"
-            c = lambda group: [[t.detach().clone() for t in net] for net in group]
-            sd["critic_adam"] = {"m": c(self._c_m), "v": c(self._c_v), "t": self._c_t}
-        return sd
-
-    def load_state_dict(self, sd):
-        mine = {"dropout": self.dropout, "utd": self.utd, "ln_eps": self.ln_eps}
-        for k, v in mine.items():
-            if "droq" not in sd or sd["droq"].get(k) != v:
-                got = sd.get("droq", {}).get(k, "nothing")
-                raise ValueError(f"the checkpoint was written with {k} = {got}, this learner has {k} = {v}")
-        got = sd["droq"].get("critic_step", "torch")
-        if got != self.critic_mode:
-            raise ValueError(f"the checkpoint was written with critic_step = {got}, this learner has critic_step = "
-                             f"{self.critic_mode}")
-        super().load_state_dict(sd)
-        if self.critic_mode == "fused":
-            for mine, theirs in ((self._c_m, sd["critic_adam"]["m"]), (self._c_v, sd["critic_adam"]["v"])):
-                for net, src in zip(mine, theirs):
-                    for t, s_ in zip(net, src):
-                        t.copy_(s_)
-            self._c_t = int(sd["critic_adam"]["t"])
 
 
 def train_and_evaluate(env, rounds: int, steps_per_round: int = 16, grad_steps: int = 1, time_limit: float = None,

@@ -557,10 +557,11 @@ class PPO(DeviceLearner):
             buf[T].copy_(sd["last"][key])
 
 
-def _train_and_evaluate(learner, rounds, train_one, shown, time_limit, log):
-    """What both `train_and_evaluate` do: `rounds` calls of `train_one(callback)` (one round of training each), one line
+def _train_and_evaluate(learner, rounds, train_one, shown, time_limit, log, line=None, metrics=None):
+    """What every `train_and_evaluate` does: `rounds` calls of `train_one(callback)` (one round of training each), one line
     per round with the mean return of the episodes that ended in it and the statistic `shown` = (label, key), then one
-    deterministic episode of every env through a MidiEvaluationWrapper.  Returns (log of the rounds, metrics)."""
+    deterministic episode of every env through a MidiEvaluationWrapper.  Returns (log of the rounds, metrics).  A learner
+    whose statistics are no floats states its own `line(i, s, seconds)` and `metrics(evaluated, log)`."""
     import time
     import torch
     from robopianist_amd.wrappers import CanonicalSpecWrapper, MidiEvaluationWrapper
@@ -568,14 +569,16 @@ def _train_and_evaluate(learner, rounds, train_one, shown, time_limit, log):
     rounds_log = []
     last_mean = [float("nan")]
 
-    def report(i, s):
-        rounds_log.append(s)
+    def mean_return_line(i, s, seconds):
         if s["episodes"]:
             last_mean[0] = s["mean_return"]
         # (a round in which no episode ended shows the mean of the last round in which some did)
-        log(f"update {i + 1:4d}  episodes {s['episodes']:6d}  mean return {last_mean[0]:10.4f}  "
-            f"mean reward {s['mean_reward']:8.4f}  {shown[0]} {s.get(shown[1], float('nan')):8.5f}  "
-            f"{time.perf_counter() - t0:7.1f} s")
+        return (f"update {i + 1:4d}  episodes {s['episodes']:6d}  mean return {last_mean[0]:10.4f}  "
+                f"mean reward {s['mean_reward']:8.4f}  {shown[0]} {s.get(shown[1], float('nan')):8.5f}  {seconds:7.1f} s")
+
+    def report(i, s):
+        rounds_log.append(s)
+        log((line or mean_return_line)(i, s, time.perf_counter() - t0))
 
     for i in range(int(rounds)):
         train_one(lambda _, s, i=i: report(i, s))
@@ -590,10 +593,12 @@ def _train_and_evaluate(learner, rounds, train_one, shown, time_limit, log):
         done |= ts.last()
         if bool(done.all()):
             break
-    metrics = evaluated.get_musical_metrics()
-    for k, v in metrics.items():
+    if metrics is not None:
+        return rounds_log, metrics(evaluated, log)
+    found = evaluated.get_musical_metrics()
+    for k, v in found.items():
         log(f"\t{k}: {v:.4f}")
-    return rounds_log, metrics
+    return rounds_log, found
 
 
 def train_and_evaluate(env, updates: int, time_limit: float = None, log=print, **ppo_kwargs):

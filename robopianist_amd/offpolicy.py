@@ -156,38 +156,31 @@ def alpha_loss(log_alpha, logp_new, target_entropy, mask):
     return _masked_mean(-log_alpha * (logp_new.detach() + float(target_entropy)), mask)
 
 
-class SAC(DeviceLearner):
-    """Soft actor-critic (Haarnoja et al. 2018) with a tanh-squashed, state-dependent Gaussian policy, an ensemble of
-    `n_critics` critics with Polyak-averaged targets and a learned temperature, over every env of `env` at once.  `env`
-    is a batched `Environment` or a `CanonicalSpecWrapper` around one; the squashed action in [-1, 1]^A is what is
-    stored and what `step_canonical` receives.
+class ReplayLearner(DeviceLearner):
+    """What the learners over a replay ring (`SAC`, population's `DroQPopulation`) share: the ring of `capacity` slots of E
+    rows, `collect()` into it, the networks' targets, the three Adams, the round loop of `train()` and the checkpoint.  A
+    slot's rows belong to one actor or to several; a subclass says which: `_draw()` (the actor and the critics, from
+    torch's global generator), `_act()` and `_act_envs()` (the policy kernel on any rows, and on a slot's), `_merge_run()`
+    (k slots into the normaliser), `_mean_reward()` (of a round's new slots) and `_host_stats()` (an update's read-back).
+    Its constructor calls `DeviceLearner.__init__`, then `_init_replay`."""
 
-    The replay ring holds `capacity` slots of E rows, so (capacity - 1) E transitions; TimeStep number m lives in slot
-    m mod capacity and the next observation is never stored twice.  `collect(n)` launches, on torch's current stream
-    and without reading anything back, n x (act on the newest slot, env step, pack into the next slot) and merges the
-    new slots into the observation normaliser.  `update(g)` takes g gradient steps on minibatches of `batch_size` rows
-    drawn by the sampler kernel; rows for which the sampler found no valid transition carry mask 0 and zeros."""
-
-    def __init__(self, env, hidden=(256, 256), n_critics: int = 2, capacity: int = 64, batch_size: int = 4096,
-                 gamma: float = 0.99, tau: float = 0.005, lr: float = 3e-4, init_alpha: float = 1.0,
-                 target_entropy: float = None, log_std_bounds=(-5.0, 2.0), learning_starts: int = 0,
-                 obs_clip: float = 10.0, seed: int = 0, norm_eps: float = 1e-8):
+    def _init_replay(self, rows, per, hidden, n_critics, capacity, batch_size, tau, lr, log_alpha, log_std_bounds,
+                     learning_starts, obs_clip, seed, norm_eps):
+        """`rows`: the rows of a slot that one actor owns, named `per` by the 2^32 bound; `log_alpha`: a list of floats."""
         import torch
         from torch import nn
-        super().__init__(env)
         self.C, self.B = int(capacity), int(batch_size)
         if self.C < 2:
             raise ValueError("capacity must be >= 2 slots")
         if self.B < 1:
             raise ValueError("batch_size must be >= 1")
-        if (self.C - 1) * self.E >= 2 ** 32:
-            raise ValueError("(capacity - 1) x n_envs must stay below 2^32")
+        if (self.C - 1) * rows >= 2 ** 32:
+            raise ValueError(f"(capacity - 1) x {per} must stay below 2^32")
         self._init_specs(hidden, obs_clip, seed, norm_eps)
         self.n_critics = int(n_critics)
         if not 1 <= self.n_critics <= MAX_CRITICS:
             raise ValueError(f"n_critics must be 1 .. {MAX_CRITICS}, got {n_critics}")
-        self.gamma, self.tau = float(gamma), float(tau)
-        self.target_entropy = -float(self.A) if target_entropy is None else float(target_entropy)
+        self.tau = float(tau)
         self.log_std_bounds = (float(log_std_bounds[0]), float(log_std_bounds[1]))
         if not self.log_std_bounds[0] <= self.log_std_bounds[1]:
             raise ValueError("log_std_bounds must be (min, max) with min <= max")
@@ -195,50 +188,29 @@ class SAC(DeviceLearner):
         self.n_written = 0
         with torch.random.fork_rng(devices=[]):   # (the global generator is left as it was)
             torch.manual_seed(self.seed)
-            self.actor = self._net(self.D, 2 * self.A)
-            self.critics = [self._net(self.D + self.A, 1) for _ in range(self.n_critics)]
+            self.actor, self.critics = self._draw()
         self.actor.to(self._dev)
         for c in self.critics:
             c.to(self._dev)
         self.targets = [copy.deepcopy(c) for c in self.critics]
         for t in self.targets:
             t.requires_grad_(False)
-        self.log_alpha = nn.Parameter(torch.full((1,), math.log(float(init_alpha)), device=self._dev))
+        self.log_alpha = nn.Parameter(torch.tensor(log_alpha, dtype=torch.float32, device=self._dev))
         adam = lambda params: torch.optim.Adam(params, lr=float(lr))
         self.actor_optimizer = adam(list(self.actor.parameters()))
         self.critic_optimizer = adam([p for c in self.critics for p in c.parameters()])
         self.alpha_optimizer = adam([self.log_alpha])
         # the gradient step's own draws (torch's rsample); a CPU device keeps the host tests possible
         self._gen = torch.Generator(device=self._dev).manual_seed(self.seed)
-        C, E, D, A, B, z = self.C, self.E, self.D, self.A, self.B, self._zeros
+        C, E, D, A, z = self.C, self.E, self.D, self.A, self._zeros
         self._obs, self._reward, self._discount = z(C, E, D), z(C, E), z(C, E)
         self._step_type, self._action = z(C, E, dtype=torch.int32), z(C, E, A)
         self._logp, self._env_action = z(E), z(E, A, dtype=self._dtype)
-        # the minibatch
-        self._b_obs, self._b_next, self._b_action = z(B, D), z(B, D), z(B, A)
-        self._b_reward, self._b_discount, self._b_mask = z(B), z(B), z(B)
-        self._b_next_action, self._b_next_logp, self._b_y = z(B, A), z(B), z(B)
-
-    # -- accessors ---------------------------------------------------------------------------------------------------
-    @property
-    def alpha(self):
-        return float(self.log_alpha.detach().exp())
 
     def ring(self):
         """The replay ring as a dict of views (live); TimeStep m lives in slot m mod capacity."""
         return {"obs": self._obs, "reward": self._reward, "discount": self._discount, "step_type": self._step_type,
                 "action": self._action}
-
-    def minibatch(self):
-        """The buffers the last gradient step's kernels filled (live)."""
-        return {"obs": self._b_obs, "next_obs": self._b_next, "action": self._b_action, "reward": self._b_reward,
-                "discount": self._b_discount, "mask": self._b_mask, "next_action": self._b_next_action,
-                "next_logp": self._b_next_logp, "y": self._b_y}
-
-    def _act(self, obs, n_rows, st, **out):
-        act(obs.data_ptr(), self._mean_f32.data_ptr(), self._inv_std_f32.data_ptr(), self.obs_clip, self._mlp(self.actor),
-            self.D, self.H1, self.H2, self.A, n_rows, log_std_bounds=self.log_std_bounds, seed=self.seed,
-            round_=self._round, hip_stream=st, **out)
 
     # -- collection ----------------------------------------------------------------------------------------------------
     def collect(self, n: int):
@@ -257,8 +229,8 @@ class SAC(DeviceLearner):
                 self.n_written = 1
             for _ in range(n):
                 newest = (self.n_written - 1) % C
-                self._act(self._obs[newest], self.E, st, action=self._action[newest].data_ptr(),
-                          logp=self._logp.data_ptr(), env_action=self._env_action.data_ptr(), precision=self._precision)
+                self._act_envs(self._obs[newest], st, action=self._action[newest].data_ptr(), logp=self._logp.data_ptr(),
+                               env_action=self._env_action.data_ptr(), precision=self._precision)
                 self._round += 1
                 ts = self._env.step_canonical(self._env_action, self._bounds, False)
                 self._pack(ts, self.n_written % C, st)
@@ -269,15 +241,155 @@ class SAC(DeviceLearner):
         return self.ring()
 
     def _merge(self, first, end, st):
-        """The TimeSteps first .. end - 1 that the ring still holds into the running moments: one launch, two where the
-        slots wrap."""
+        """The TimeSteps first .. end - 1 that the ring still holds into the running moments: one launch per contiguous
+        run of slots (two where the slots wrap)."""
         C = self.C
         first = max(first, end - C)
         while first < end:
             s = first % C
             k = min(end - first, C - s)
-            self._merge_moments(self._obs[s], k * self.E, st)
+            self._merge_run(self._obs[s], k, st)
             first += k
+
+    def _host_stats(self, stats):
+        """The last gradient step's statistics as `update()` returns them."""
+        return {k: float(v) for k, v in stats.items()}
+
+    def train(self, n: int, steps_per_round: int = 1, grad_steps: int = 1, callback=None):
+        """n rounds of collect(steps_per_round) and, once `learning_starts` control steps have been collected,
+        update(grad_steps); returns the list of per-round statistics (the update's, plus "mean_reward": the mean reward
+        of the round's new TimeSteps that are not FIRST, and `episode_stats()`)."""
+        import torch
+        log = []
+        for i in range(int(n)):
+            first = max(self.n_written, 1)
+            self.collect(steps_per_round)
+            s = self.update(grad_steps) if self.n_written - 1 >= max(self.learning_starts, 1) and grad_steps > 0 else {}
+            slots = torch.arange(max(first, self.n_written - self.C), self.n_written, device=self._dev) % self.C
+            s["mean_reward"] = self._mean_reward(slots)
+            s.update(self.episode_stats())
+            log.append(s)
+            if callback is not None:
+                callback(i, s)
+        return log
+
+    # -- evaluation ----------------------------------------------------------------------------------------------------
+    def act(self, observation, deterministic: bool = True):
+        """The policy's action for an observation dict of E rows: [E, A] of the engine's dtype in [-1, 1] (what a
+        CanonicalSpecWrapper's step takes).  Live: the next call overwrites it."""
+        import torch
+        with torch.cuda.device(self._dev):
+            st = self._stream()
+            self._pack_observation(observation, st)
+            self._act_envs(self._e_obs, st, action=self._e_action.data_ptr(), logp=self._e_logp.data_ptr(),
+                           env_action=self._e_env_action.data_ptr(), precision=self._precision, deterministic=deterministic)
+            if not deterministic:
+                self._round += 1
+        return self._e_env_action
+
+    # -- checkpoint / resume -------------------------------------------------------------------------------------------
+    def state_dict(self, include_replay: bool = False):
+        """The networks, the targets, the three Adams, log_alpha, the normaliser, the seed, round and n_written
+        counters, the torch generator of the gradient step, the running episode statistics and the newest slot (the
+        TimeStep the next `collect()` acts on); the whole ring only with `include_replay`.  With the env's own
+        `state_dict()` the next `collect()` is resumed bit for bit."""
+        c = lambda t: t.detach().clone()
+        nets = lambda ms: [{k: c(v) for k, v in m.state_dict().items()} for m in ms]
+        newest = (self.n_written - 1) % self.C if self.n_written else 0
+        sd = {"actor": nets([self.actor])[0], "critics": nets(self.critics), "targets": nets(self.targets),
+              "log_alpha": c(self.log_alpha),
+              "optimizers": {k: copy.deepcopy(getattr(self, k + "_optimizer").state_dict())
+                             for k in ("actor", "critic", "alpha")},
+              "normalizer": self._normalizer_state(),
+              "seed": self.seed, "round": self._round, "n_written": self.n_written, "generator": self._gen.get_state(),
+              "newest": {"obs": c(self._obs[newest]), "reward": c(self._reward[newest]),
+                         "discount": c(self._discount[newest]), "step_type": c(self._step_type[newest])},
+              "episodes": self._episodes_state()}
+        if include_replay:
+            sd["replay"] = {k: c(v) for k, v in self.ring().items()}
+        return sd
+
+    def load_state_dict(self, sd):
+        """Without the ring in `sd` the ring restarts from the newest slot alone: its older slots are marked LAST, so
+        nothing the snapshot did not hold can be drawn."""
+        import torch
+        self.actor.load_state_dict(sd["actor"])   # (in place)
+        for group, key in ((self.critics, "critics"), (self.targets, "targets")):
+            for m, s in zip(group, sd[key]):
+                m.load_state_dict(s)
+        with torch.no_grad():
+            self.log_alpha.copy_(sd["log_alpha"])
+        for k, s in sd["optimizers"].items():
+            getattr(self, k + "_optimizer").load_state_dict(copy.deepcopy(s))   # (Adam would adopt sd's own tensors)
+        self._load_shared_state(sd)
+        self.seed, self._round, self.n_written = int(sd["seed"]), int(sd["round"]), int(sd["n_written"])
+        self._gen.set_state(sd["generator"])
+        if "replay" in sd:
+            for k, v in sd["replay"].items():
+                self.ring()[k].copy_(v)
+        else:
+            self._step_type.fill_(STEP_LAST)
+        newest = (self.n_written - 1) % self.C if self.n_written else 0
+        for buf, key in ((self._obs, "obs"), (self._reward, "reward"), (self._discount, "discount"),
+                         (self._step_type, "step_type")):
+            buf[newest].copy_(sd["newest"][key])
+
+
+class SAC(ReplayLearner):
+    """Soft actor-critic (Haarnoja et al. 2018) with a tanh-squashed, state-dependent Gaussian policy, an ensemble of
+    `n_critics` critics with Polyak-averaged targets and a learned temperature, over every env of `env` at once.  `env`
+    is a batched `Environment` or a `CanonicalSpecWrapper` around one; the squashed action in [-1, 1]^A is what is
+    stored and what `step_canonical` receives.
+
+    The replay ring holds `capacity` slots of E rows, so (capacity - 1) E transitions; TimeStep number m lives in slot
+    m mod capacity and the next observation is never stored twice.  `collect(n)` launches, on torch's current stream
+    and without reading anything back, n x (act on the newest slot, env step, pack into the next slot) and merges the
+    new slots into the observation normaliser.  `update(g)` takes g gradient steps on minibatches of `batch_size` rows
+    drawn by the sampler kernel; rows for which the sampler found no valid transition carry mask 0 and zeros."""
+
+    def __init__(self, env, hidden=(256, 256), n_critics: int = 2, capacity: int = 64, batch_size: int = 4096,
+                 gamma: float = 0.99, tau: float = 0.005, lr: float = 3e-4, init_alpha: float = 1.0,
+                 target_entropy: float = None, log_std_bounds=(-5.0, 2.0), learning_starts: int = 0,
+                 obs_clip: float = 10.0, seed: int = 0, norm_eps: float = 1e-8):
+        super().__init__(env)
+        self._init_replay(self.E, "n_envs", hidden, n_critics, capacity, batch_size, tau, lr, [math.log(float(init_alpha))],
+                          log_std_bounds, learning_starts, obs_clip, seed, norm_eps)
+        self.gamma = float(gamma)
+        self.target_entropy = -float(self.A) if target_entropy is None else float(target_entropy)
+        # the minibatch
+        B, D, A, z = self.B, self.D, self.A, self._zeros
+        self._b_obs, self._b_next, self._b_action = z(B, D), z(B, D), z(B, A)
+        self._b_reward, self._b_discount, self._b_mask = z(B), z(B), z(B)
+        self._b_next_action, self._b_next_logp, self._b_y = z(B, A), z(B), z(B)
+
+    def _draw(self):
+        return self._net(self.D, 2 * self.A), [self._net(self.D + self.A, 1) for _ in range(self.n_critics)]
+
+    # -- accessors ---------------------------------------------------------------------------------------------------
+    @property
+    def alpha(self):
+        return float(self.log_alpha.detach().exp())
+
+    def minibatch(self):
+        """The buffers the last gradient step's kernels filled (live)."""
+        return {"obs": self._b_obs, "next_obs": self._b_next, "action": self._b_action, "reward": self._b_reward,
+                "discount": self._b_discount, "mask": self._b_mask, "next_action": self._b_next_action,
+                "next_logp": self._b_next_logp, "y": self._b_y}
+
+    def _act(self, obs, n_rows, st, **out):
+        act(obs.data_ptr(), self._mean_f32.data_ptr(), self._inv_std_f32.data_ptr(), self.obs_clip, self._mlp(self.actor),
+            self.D, self.H1, self.H2, self.A, n_rows, log_std_bounds=self.log_std_bounds, seed=self.seed,
+            round_=self._round, hip_stream=st, **out)
+
+    def _act_envs(self, obs, st, **out):
+        self._act(obs, self.E, st, **out)
+
+    def _merge_run(self, obs, k, st):
+        self._merge_moments(obs, k * self.E, st)
+
+    def _mean_reward(self, slots):
+        live = self._step_type[slots] != STEP_FIRST
+        return float(self._reward[slots][live].mean()) if bool(live.any()) else float("nan")
 
     # -- the gradient step ---------------------------------------------------------------------------------------------
     def sample_and_target(self):
@@ -335,87 +447,7 @@ class SAC(DeviceLearner):
         stats = {}
         for _ in range(int(g)):
             stats = self.gradient_step(self.sample_and_target())
-        return {k: float(v) for k, v in stats.items()}
-
-    def train(self, n: int, steps_per_round: int = 1, grad_steps: int = 1, callback=None):
-        """n rounds of collect(steps_per_round) and, once `learning_starts` control steps have been collected,
-        update(grad_steps); returns the list of per-round statistics (the update's, plus "mean_reward": the mean reward
-        of the round's new TimeSteps that are not FIRST, and `episode_stats()`)."""
-        import torch
-        log = []
-        for i in range(int(n)):
-            first = max(self.n_written, 1)
-            self.collect(steps_per_round)
-            s = self.update(grad_steps) if self.n_written - 1 >= max(self.learning_starts, 1) and grad_steps > 0 else {}
-            slots = torch.arange(max(first, self.n_written - self.C), self.n_written, device=self._dev) % self.C
-            live = self._step_type[slots] != STEP_FIRST
-            s["mean_reward"] = float(self._reward[slots][live].mean()) if bool(live.any()) else float("nan")
-            s.update(self.episode_stats())
-            log.append(s)
-            if callback is not None:
-                callback(i, s)
-        return log
-
-    # -- evaluation ----------------------------------------------------------------------------------------------------
-    def act(self, observation, deterministic: bool = True):
-        """The policy's action for an observation dict of E rows: [E, A] of the engine's dtype in [-1, 1] (what a
-        CanonicalSpecWrapper's step takes).  Live: the next call overwrites it."""
-        import torch
-        with torch.cuda.device(self._dev):
-            st = self._stream()
-            self._pack_observation(observation, st)
-            self._act(self._e_obs, self.E, st, action=self._e_action.data_ptr(), logp=self._e_logp.data_ptr(),
-                      env_action=self._e_env_action.data_ptr(), precision=self._precision, deterministic=deterministic)
-            if not deterministic:
-                self._round += 1
-        return self._e_env_action
-
-    # -- checkpoint / resume -------------------------------------------------------------------------------------------
-    def state_dict(self, include_replay: bool = False):
-        """The networks, the targets, the three Adams, log_alpha, the normaliser, the seed, round and n_written
-        counters, the torch generator of the gradient step, the running episode statistics and the newest slot (the
-        TimeStep the next `collect()` acts on); the whole ring only with `include_replay`.  With the env's own
-        `state_dict()` the next `collect()` is resumed bit for bit."""
-        c = lambda t: t.detach().clone()
-        nets = lambda ms: [{k: c(v) for k, v in m.state_dict().items()} for m in ms]
-        newest = (self.n_written - 1) % self.C if self.n_written else 0
-        sd = {"actor": nets([self.actor])[0], "critics": nets(self.critics), "targets": nets(self.targets),
-              "log_alpha": c(self.log_alpha),
-              "optimizers": {k: copy.deepcopy(getattr(self, k + "_optimizer").state_dict())
-                             for k in ("actor", "critic", "alpha")},
-              "normalizer": self._normalizer_state(),
-              "seed": self.seed, "round": self._round, "n_written": self.n_written, "generator": self._gen.get_state(),
-              "newest": {"obs": c(self._obs[newest]), "reward": c(self._reward[newest]),
-                         "discount": c(self._discount[newest]), "step_type": c(self._step_type[newest])},
-              "episodes": self._episodes_state()}
-        if include_replay:
-            sd["replay"] = {k: c(v) for k, v in self.ring().items()}
-        return sd
-
-    def load_state_dict(self, sd):
-        """Without the ring in `sd` the ring restarts from the newest slot alone: its older slots are marked LAST, so
-        nothing the snapshot did not hold can be drawn."""
-        import torch
-        self.actor.load_state_dict(sd["actor"])   # (in place)
-        for group, key in ((self.critics, "critics"), (self.targets, "targets")):
-            for m, s in zip(group, sd[key]):
-                m.load_state_dict(s)
-        with torch.no_grad():
-            self.log_alpha.copy_(sd["log_alpha"])
-        for k, s in sd["optimizers"].items():
-            getattr(self, k + "_optimizer").load_state_dict(copy.deepcopy(s))   # (Adam would adopt sd's own tensors)
-        self._load_shared_state(sd)
-        self.seed, self._round, self.n_written = int(sd["seed"]), int(sd["round"]), int(sd["n_written"])
-        self._gen.set_state(sd["generator"])
-        if "replay" in sd:
-            for k, v in sd["replay"].items():
-                self.ring()[k].copy_(v)
-        else:
-            self._step_type.fill_(STEP_LAST)
-        newest = (self.n_written - 1) % self.C if self.n_written else 0
-        for buf, key in ((self._obs, "obs"), (self._reward, "reward"), (self._discount, "discount"),
-                         (self._step_type, "step_type")):
-            buf[newest].copy_(sd["newest"][key])
+        return self._host_stats(stats)
 
 
 def train_and_evaluate(env, rounds: int, steps_per_round: int = 16, grad_steps: int = 4, time_limit: float = None,

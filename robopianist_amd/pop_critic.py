@@ -25,18 +25,11 @@ TILE_MAJOR, MEMBER_MAJOR = 0, 1      # the workgroup order of both launches (spe
 
 _lib = None
 
-_p, _i, _u32, _f, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_float, ctypes.c_size_t
+_i, _sz = ctypes.c_int, ctypes.c_size_t
 
 
 class StepArgs(ctypes.Structure):
-    _fields_ = [("struct_size", _sz), ("obs", _p), ("action", _p), ("y", _p), ("mask", _p), ("mean", _p), ("inv_std", _p),
-                ("obs_clip", _f), ("p", ctypes.POINTER(Set)), ("m", ctypes.POINTER(Set)), ("v", ctypes.POINTER(Set)),
-                ("target", ctypes.POINTER(Set)), ("grad", ctypes.POINTER(Set)), ("n_critics", _i), ("q", _p),
-                ("workspace", _p), ("workspace_bytes", _sz), ("drop_threshold", _u32), ("keep_scale", _f), ("ln_eps", _f),
-                ("seed_lo", _u32), ("seed_hi", _u32), ("round", _u32), ("one_minus_beta1", _f), ("beta2", _f),
-                ("one_minus_beta2", _f), ("step_size", _f), ("bc2_sqrt", _f), ("eps", _f), ("tau", _f), ("D", _i),
-                ("H1", _i), ("H2", _i), ("A", _i), ("P", _i), ("n", _i), ("grid_order", _i), ("member_first", _i),
-                ("member_count", _i), ("row_first", _i), ("row_count", _i), ("launches", _i), ("hip_stream", _p)]
+    _fields_ = critic.step_fields(("P", _i), ("n", _i), ("grid_order", _i), ("member_first", _i), ("member_count", _i))
 
 
 class WorkspaceArgs(ctypes.Structure):
@@ -74,22 +67,11 @@ def workspace_bytes(n_critics, H1, H2, row_count, member_count) -> int:
 
 
 def step(obs, action, y, mask, mean, inv_std, obs_clip, p, m, v, target, q, workspace, workspace_bytes_, D, H1, H2, A, P, n,
-         step_size, bc2_sqrt, eps=1e-8, betas=(0.9, 0.999), tau=0.005, grad=None, threshold=0, keep_scale=1.0, ln_eps=1e-5,
-         seed=0, round_=0, member_first=0, member_count=None, row_first=0, row_count=None, grid_order=None, launches=STEP,
-         hip_stream=None):
-    """`p`, `m`, `v`, `target` (and `grad`, optional): sequences of `Set` of the bases of the stacked tensors [P][...],
-    one per critic.  `n`: minibatch rows per member; the arrays hold P n rows, member p's at [p n, (p + 1) n).
-    `step_size`, `bc2_sqrt`: `adam_scalars(lr, t)`, shared by the members."""
-    tp = set_table(p)
-    k = len(tp)
-    tm, tv, tt = set_table(m, k), set_table(v, k), set_table(target, k)
-    tg = None if grad is None else set_table(grad, k)
-    _call("step", obs=obs, action=action, y=y, mask=mask, mean=mean, inv_std=inv_std, obs_clip=float(obs_clip), p=tp, m=tm,
-          v=tv, target=tt, grad=tg, n_critics=k, q=q, workspace=workspace, workspace_bytes=int(workspace_bytes_),
-          drop_threshold=int(threshold), keep_scale=float(keep_scale), ln_eps=float(ln_eps),
-          one_minus_beta1=1.0 - betas[0], beta2=betas[1], one_minus_beta2=1.0 - betas[1], step_size=float(step_size),
-          bc2_sqrt=float(bc2_sqrt), eps=float(eps), tau=float(tau), D=D, H1=H1, H2=H2, A=A, P=P, n=n,
-          grid_order=dim("default_grid_order") if grid_order is None else int(grid_order), member_first=member_first,
-          member_count=P - member_first if member_count is None else member_count, row_first=row_first,
-          row_count=n - row_first if row_count is None else row_count, launches=int(launches), hip_stream=hip_stream,
-          **_abi.seed_args(seed, round_))
+         step_size, bc2_sqrt, member_first=0, member_count=None, grid_order=None, **options):
+    """`critic.step` with `p`, `m`, `v`, `target` (and `grad`, optional) the `Set`s of the bases of the stacked tensors
+    [P][...].  `n`: minibatch rows per member; the arrays hold P n rows, member p's at [p n, (p + 1) n).  `step_size`,
+    `bc2_sqrt`: `adam_scalars(lr, t)`, shared by the members."""
+    shared = critic.step_keywords(obs, action, y, mask, mean, inv_std, obs_clip, p, m, v, target, q, workspace,
+                                  workspace_bytes_, D, H1, H2, A, n, step_size, bc2_sqrt, **options)
+    _call("step", P=P, n=n, grid_order=dim("default_grid_order") if grid_order is None else int(grid_order),
+          member_first=member_first, member_count=P - member_first if member_count is None else member_count, **shared)

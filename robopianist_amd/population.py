@@ -16,7 +16,6 @@ missing library is an error.
 
 from __future__ import annotations
 
-import copy
 import ctypes
 import math
 import os
@@ -26,10 +25,10 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from robopianist_amd import _abi, critic, droq, pop_critic
-from robopianist_amd.droq import Critic, drop_threshold
-from robopianist_amd.learning import STEP_FIRST, STEP_LAST, DeviceLearner, LearnError, Mlp
-from robopianist_amd.offpolicy import MAX_CRITICS, squashed_gaussian
+from robopianist_amd import _abi, droq, pop_critic
+from robopianist_amd.droq import Critic, DroQCore
+from robopianist_amd.learning import STEP_FIRST, LearnError, Mlp, _train_and_evaluate, mlp_table
+from robopianist_amd.offpolicy import ReplayLearner, squashed_gaussian
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("RP_POP_LIB") or os.path.join(_HERE, "csrc", "librp_pop.so")
@@ -261,7 +260,7 @@ def _per_member(value, P, name):
     return out
 
 
-class DroQPopulation(DeviceLearner):
+class DroQPopulation(DroQCore, ReplayLearner):
     """`members` = P independent `droq.DroQ` learners over one env batch of E = P Em envs: member p collects with, and
     learns from, the envs p, p + P, p + 2 P, ... alone, and has its own actor, critics, targets, temperature, observation
     normaliser and minibatches of `batch_size` rows (per member).  `gamma`, `init_alpha` and `target_entropy` take a
@@ -276,7 +275,7 @@ class DroQPopulation(DeviceLearner):
     keyed by (seed, round, row); the population then owns Adam's stacked m and v and one step count for all members,
     and torch's critic optimiser stays unused) -- `droq.DroQ`'s contract."""
 
-    _reads = "the population kernels read"
+    _reads, _me = "the population kernels read", "population"
 
     def __init__(self, env, members: int, hidden=(256, 256), n_critics: int = 2, capacity: int = 64,
                  batch_size: int = 256, gamma=0.99, tau: float = 0.005, lr: float = 3e-4, init_alpha=1.0,
@@ -284,89 +283,38 @@ class DroQPopulation(DeviceLearner):
                  seed: int = 0, norm_eps: float = 1e-8, dropout: float = 0.01, utd: int = 20, ln_eps: float = 1e-5,
                  critic_step: str = "torch"):
         super().__init__(env)
-        if critic_step not in ("torch", "fused"):
-            raise ValueError(f'critic_step must be "torch" or "fused", got {critic_step!r}')
-        self.critic_mode = critic_step
-        self.P = int(members)
-        if self.P < 1:
+        self._init_droq(dropout, utd, ln_eps, critic_step)
+        self.P = P = int(members)
+        if P < 1:
             raise ValueError(f"members must be >= 1, got {members}")
-        if self.E % self.P:
-            raise ValueError(f"members = {self.P} does not divide n_envs = {self.E}: member p owns the envs e % members == p")
-        self.Em = self.E // self.P
-        self.C, self.B = int(capacity), int(batch_size)
-        if self.C < 2:
-            raise ValueError("capacity must be >= 2 slots")
-        if self.B < 1:
-            raise ValueError("batch_size must be >= 1")
-        if (self.C - 1) * self.Em >= 2 ** 32:
-            raise ValueError("(capacity - 1) x n_envs / members must stay below 2^32")
-        self.dropout, self.utd, self.ln_eps = float(dropout), int(utd), float(ln_eps)
-        if not 0.0 <= self.dropout < 1.0:
-            raise ValueError(f"dropout must lie in [0, 1), got {dropout}")
-        if self.utd < 1:
-            raise ValueError(f"utd must be >= 1, got {utd}")
-        if not self.ln_eps > 0.0:
-            raise ValueError(f"ln_eps must be > 0, got {ln_eps}")
-        if self.P * self.utd * self.B > 2 ** 31 - 1:
+        if self.E % P:
+            raise ValueError(f"members = {P} does not divide n_envs = {self.E}: member p owns the envs e % members == p")
+        self.Em = self.E // P
+        if P * self.utd * int(batch_size) > 2 ** 31 - 1:
             raise ValueError("members x utd x batch_size must stay below 2^31")
-        self._threshold = drop_threshold(self.dropout)
-        self._keep_scale = 1.0 / (1.0 - self.dropout)
-        self._init_specs(hidden, obs_clip, seed, norm_eps)
-        self.n_critics = int(n_critics)
-        if not 1 <= self.n_critics <= MAX_CRITICS:
-            raise ValueError(f"n_critics must be 1 .. {MAX_CRITICS}, got {n_critics}")
-        P, D, A = self.P, self.D, self.A
+        alpha0 = _per_member(init_alpha, P, "init_alpha")
+        self._init_replay(self.Em, "n_envs / members", hidden, n_critics, capacity, batch_size, tau, lr,
+                          [math.log(a) for a in alpha0], log_std_bounds, learning_starts, obs_clip, seed, norm_eps)
+        D, z = self.D, self._zeros
         f32 = lambda v: torch.tensor(v, dtype=torch.float32, device=self._dev)
         self.gamma = f32(_per_member(gamma, P, "gamma"))
-        self.target_entropy = f32(_per_member(-float(A) if target_entropy is None else target_entropy, P, "target_entropy"))
-        alpha0 = _per_member(init_alpha, P, "init_alpha")
-        self.tau = float(tau)
-        self.log_std_bounds = (float(log_std_bounds[0]), float(log_std_bounds[1]))
-        if not self.log_std_bounds[0] <= self.log_std_bounds[1]:
-            raise ValueError("log_std_bounds must be (min, max) with min <= max")
-        self.learning_starts = int(learning_starts)
-        self.n_written = 0
-        with torch.random.fork_rng(devices=[]):   # (the global generator is left as it was)
-            torch.manual_seed(self.seed)
-            drawn = [(self._net(D, 2 * A), [self._critic_net(D + A) for _ in range(self.n_critics)]) for _ in range(P)]
-        self.actor = stack_networks([a for a, _ in drawn]).to(self._dev)
-        self.critics = [stack_networks([cs[i] for _, cs in drawn]).to(self._dev) for i in range(self.n_critics)]
-        self.targets = [copy.deepcopy(c) for c in self.critics]
-        for t in self.targets:
-            t.requires_grad_(False)
-        self.log_alpha = nn.Parameter(f32([math.log(a) for a in alpha0]))
-        adam = lambda params: torch.optim.Adam(params, lr=float(lr))
-        self.actor_optimizer = adam(list(self.actor.parameters()))
-        self.critic_optimizer = adam([p for c in self.critics for p in c.parameters()])
-        self.alpha_optimizer = adam([self.log_alpha])
-        self._gen = torch.Generator(device=self._dev).manual_seed(self.seed)
-        C, E, z = self.C, self.E, self._zeros
+        entropy = -float(self.A) if target_entropy is None else target_entropy
+        self.target_entropy = f32(_per_member(entropy, P, "target_entropy"))
         # the normaliser, per member (DeviceLearner allocated one row)
         self._mean, self._M2 = z(P, D, dtype=torch.float64), z(P, D, dtype=torch.float64)
         self._mean_f32, self._inv_std_f32 = z(P, D), torch.ones(P, D, dtype=torch.float32, device=self._dev)
-        # the ring: SAC's
-        self._obs, self._reward, self._discount = z(C, E, D), z(C, E), z(C, E)
-        self._step_type, self._action = z(C, E, dtype=torch.int32), z(C, E, A)
-        self._logp, self._env_action = z(E), z(E, A, dtype=self._dtype)
         # the minibatches: member p's utd ranges of B rows at [p n, (p + 1) n), n = utd B
-        n = self.utd * self.B
-        self._u_obs, self._u_next, self._u_action = z(P * n, D), z(P * n, D), z(P * n, A)
-        self._u_reward, self._u_discount, self._u_mask = z(P * n), z(P * n), z(P * n)
-        self._u_next_action, self._u_next_logp, self._u_y = z(P * n, A), z(P * n), z(P * n)
+        self._init_ranges(P * self.utd * self.B)
         self._range = self.utd - 1
-        if self.critic_mode == "fused":
-            self._c_m = [[torch.zeros_like(t) for t in self._critic_tensors(c)] for c in self.critics]
-            self._c_v = [[torch.zeros_like(t) for t in self._critic_tensors(c)] for c in self.critics]
-            self._c_t = 0                                  # Adam's step count: the members step together
-            self._c_bytes = pop_critic.workspace_bytes(self.n_critics, self.H1, self.H2, self.B, P)
-            self._c_ws, self._u_q = z(max(self._c_bytes // 4, 1)), z(self.n_critics, P * n)
 
-    def _critic_net(self, n_in):
-        """One member's critic, drawn as droq.DroQ draws it."""
-        p, eps = self.dropout, self.ln_eps
-        return nn.Sequential(nn.Linear(n_in, self.H1), nn.Dropout(p), nn.LayerNorm(self.H1, eps), nn.ReLU(),
-                             nn.Linear(self.H1, self.H2), nn.Dropout(p), nn.LayerNorm(self.H2, eps), nn.ReLU(),
-                             nn.Linear(self.H2, 1))
+    def _draw(self):
+        """(actor, critics) member after member, as P single learners of this seed's stream would draw them, stacked."""
+        drawn = [self._draw_member() for _ in range(self.P)]
+        return (stack_networks([a for a, _ in drawn]),
+                [stack_networks([cs[i] for _, cs in drawn]) for i in range(self.n_critics)])
+
+    def _workspace_bytes(self):
+        return pop_critic.workspace_bytes(self.n_critics, self.H1, self.H2, self.B, self.P)
 
     # -- accessors ---------------------------------------------------------------------------------------------------
     @property
@@ -377,12 +325,6 @@ class DroQPopulation(DeviceLearner):
     def alpha(self):
         """[P] floats."""
         return self.log_alpha.detach().exp().cpu().numpy().astype(np.float64)
-
-    def ring(self):
-        """The replay ring as a dict of views (live); TimeStep m lives in slot m mod capacity, env e belongs to member
-        e % members."""
-        return {"obs": self._obs, "reward": self._reward, "discount": self._discount, "step_type": self._step_type,
-                "action": self._action}
 
     def rows(self):
         """The utd x batch_size rows per member that the last actor step drew, [P, utd B, ...] views (live)."""
@@ -396,74 +338,27 @@ class DroQPopulation(DeviceLearner):
         r = slice(self._range * self.B, (self._range + 1) * self.B)
         return {k: v[:, r] for k, v in self.rows().items()}
 
-    def _checked(self, tensors):
+    def _actor_table(self):
+        """The stacked actor as rp_learn_mlp: the bases of its tensors as they are now."""
+        tensors = [t for i in (0, 2, 4) for t in (self.actor[i].weight, self.actor[i].bias)]
         for t in tensors:
             if not t.is_contiguous() or t.dtype != torch.float32:
                 raise LearnError(f"{self._reads} contiguous float32 parameters")
-        return tensors
-
-    def _actor_table(self):
-        """The stacked actor as rp_learn_mlp: the bases of its tensors as they are now."""
-        net = self.actor
-        m = Mlp()
-        for (name, _), t in zip(Mlp._fields_, self._checked([t for i in (0, 2, 4) for t in (net[i].weight, net[i].bias)])):
-            setattr(m, name, t.data_ptr())
-        return m
-
-    def _critic_tensors(self, net):
-        """The ten stacked parameters of `net` in rp_droq_critic's order, as they are now."""
-        tensors = [t for i in (0, 4, 8) for t in (net[i].weight, net[i].bias)]
-        tensors += [t for i in (2, 6) for t in (net[i].weight, net[i].bias)]
-        return self._checked(tensors)
-
-    def _critic_table(self, net):
-        """A stacked critic as rp_droq_critic."""
-        return droq.critic_entry(self._critic_tensors(net))
+        return mlp_table(tensors)
 
     def _act(self, obs, rows, layout, st, **out):
         act(obs.data_ptr(), self._mean_f32.data_ptr(), self._inv_std_f32.data_ptr(), self.obs_clip, self._actor_table(),
             self.D, self.H1, self.H2, self.A, self.P, rows, layout, log_std_bounds=self.log_std_bounds, seed=self.seed,
             round_=self._round, hip_stream=st, **out)
 
-    # -- collection ----------------------------------------------------------------------------------------------------
-    def collect(self, n: int):
-        """The next n control steps of every env into the ring (the first call resets the env and writes TimeStep 0
-        first), then the new slots into the members' normalisers.  Returns `ring()`."""
-        C, n = self.C, int(n)
-        with torch.cuda.device(self._dev):
-            st = self._stream()
-            kept = []
-            first_new = self.n_written
-            if self.n_written == 0:
-                ts = self._env.reset()
-                self._pack(ts, 0, st)
-                kept.append(ts)
-                self.n_written = 1
-            for _ in range(n):
-                newest = (self.n_written - 1) % C
-                self._act(self._obs[newest], self.Em, INTERLEAVED, st, action=self._action[newest].data_ptr(),
-                          logp=self._logp.data_ptr(), env_action=self._env_action.data_ptr(), precision=self._precision)
-                self._round += 1
-                ts = self._env.step_canonical(self._env_action, self._bounds, False)
-                self._pack(ts, self.n_written % C, st)
-                self.n_written += 1
-                kept.append(ts)
-            self._merge(first_new, self.n_written, st)
-            self._keep = kept   # alive until the kernels have run
-        return self.ring()
+    def _act_envs(self, obs, st, **out):
+        self._act(obs, self.Em, INTERLEAVED, st, **out)
 
-    def _merge(self, first, end, st):
-        """The TimeSteps first .. end - 1 that the ring still holds into the running moments of every member: one launch
-        per contiguous run of slots (two where the slots wrap)."""
-        C = self.C
-        first = max(first, end - C)
-        while first < end:
-            s = first % C
-            k = min(end - first, C - s)
-            moments(self._obs[s].data_ptr(), self._mean.data_ptr(), self._M2.data_ptr(), self._mean_f32.data_ptr(),
-                    self._inv_std_f32.data_ptr(), self._count, self.norm_eps, k, self.E, self.D, self.P, hip_stream=st)
-            self._count += float(k * self.Em)
-            first += k
+    def _merge_run(self, obs, k, st):
+        """k consecutive slots into the running moments of every member (one launch)."""
+        moments(obs.data_ptr(), self._mean.data_ptr(), self._M2.data_ptr(), self._mean_f32.data_ptr(),
+                self._inv_std_f32.data_ptr(), self._count, self.norm_eps, k, self.E, self.D, self.P, hip_stream=st)
+        self._count += float(k * self.Em)
 
     def normalize(self, obs):
         """What the kernels feed the first layer (torch): obs [P, n, D] by the member's moments."""
@@ -512,27 +407,12 @@ class DroQPopulation(DeviceLearner):
                              "target_range(u) or minibatch() returned")
         return u
 
-    def _fused_critic_step(self, u, loss):
-        """`pop_critic.step` on range u of all members: two launches; the per-member losses (from the step's q, y and
-        mask) only where asked for."""
-        group = self.critic_optimizer.param_groups[0]
-        self._c_t += 1
-        step_size, bc2_sqrt = critic.adam_scalars(group["lr"], self._c_t, group["betas"])
-        sets = lambda nets: [critic.set_entry(self._critic_tensors(net)) for net in nets]
-        P, B, n = self.P, self.B, self.utd * self.B
-        with torch.cuda.device(self._dev):
-            pop_critic.step(self._u_obs.data_ptr(), self._u_action.data_ptr(), self._u_y.data_ptr(),
-                            self._u_mask.data_ptr(), self._mean_f32.data_ptr(), self._inv_std_f32.data_ptr(), self.obs_clip,
-                            sets(self.critics), [critic.set_entry(m) for m in self._c_m],
-                            [critic.set_entry(v) for v in self._c_v], sets(self.targets), self._u_q.data_ptr(),
-                            self._c_ws.data_ptr(), self._c_bytes, self.D, self.H1, self.H2, self.A, P, n, step_size,
-                            bc2_sqrt, eps=group["eps"], betas=group["betas"], tau=self.tau, threshold=self._threshold,
-                            keep_scale=self._keep_scale, ln_eps=self.ln_eps, seed=self.seed, round_=self._round,
-                            row_first=u * B, row_count=B, hip_stream=self._stream())
-        if not loss:
-            return None
-        r = slice(u * B, (u + 1) * B)
-        v = lambda t: t.view(P, n)[:, r]
+    def _launch_critic_step(self, *block, **options):
+        pop_critic.step(*block, self.P, self.utd * self.B, **options)
+
+    def _range_loss(self, u):
+        """The per-member losses of range u from the fused step's q."""
+        v = lambda t: t.view(self.P, self.utd * self.B)[:, u * self.B:(u + 1) * self.B]
         return critic_losses([v(q) for q in self._u_q], v(self._u_y), v(self._u_mask))
 
     def critic_step(self, batch, loss: bool = True):
@@ -571,27 +451,11 @@ class DroQPopulation(DeviceLearner):
         return {"actor_loss": la.detach(), "alpha_loss": lt.detach(), "alpha": self.log_alpha.detach().exp(),
                 "entropy": -member_means(logp_new.detach(), mask), "masked": 1.0 - mask.mean(1)}
 
-    def update(self, g: int = 1):
-        """g actor steps of utd critic steps each; returns the statistics of the last one: float64 arrays [P]."""
-        if self.n_written < 2:
-            raise LearnError("update() needs at least two TimeSteps in the ring: call collect() first")
-        stats = {}
-        for k in range(int(g)):
-            self.draw_and_act()
-            for u in range(self.utd):
-                batch = self.target_range(u)
-                if self.critic_mode == "fused":   # (the loss costs torch launches: only where it is returned)
-                    lc = self.critic_step(batch, loss=u == self.utd - 1 and k == int(g) - 1)
-                else:
-                    lc = self.critic_step(batch)
-            stats = dict({} if lc is None else {"critic_loss": lc}, **self.actor_step(batch))
-            if self.critic_mode == "fused":
-                self.critic_optimizer.zero_grad(set_to_none=True)   # (the actor pass's critic gradients: nobody reads them)
-            self._round += 1
+    def _host_stats(self, stats):
+        """float64 arrays [P] (one read-back)."""
         if not stats:
             return {}
-        host = torch.stack([v.to(torch.float64) for v in stats.values()]).cpu().numpy()   # (one read-back)
-        return dict(zip(stats, host))
+        return dict(zip(stats, torch.stack([v.to(torch.float64) for v in stats.values()]).cpu().numpy()))
 
     def episode_stats(self):
         """{"episodes" [P] int, "mean_return" [P], "mean_length" [P]} of the episodes that ended since the last call, per
@@ -605,41 +469,15 @@ class DroQPopulation(DeviceLearner):
         self._done_return.zero_(); self._done_len.zero_(); self._done_count.zero_()
         return out
 
-    def train(self, n: int, steps_per_round: int = 1, grad_steps: int = 1, callback=None):
-        """n rounds of collect(steps_per_round) and, once `learning_starts` control steps have been collected,
-        update(grad_steps); returns the list of per-round statistics, every one an array of length P (the update's, plus
-        "mean_reward": the mean reward of the member's new TimeSteps that are not FIRST, and `episode_stats()`)."""
-        log = []
-        for i in range(int(n)):
-            first = max(self.n_written, 1)
-            self.collect(steps_per_round)
-            s = self.update(grad_steps) if self.n_written - 1 >= max(self.learning_starts, 1) and grad_steps > 0 else {}
-            slots = torch.arange(max(first, self.n_written - self.C), self.n_written, device=self._dev) % self.C
-            live = (self._step_type[slots] != STEP_FIRST).to(torch.float64).view(-1, self.Em, self.P)
-            reward = self._reward[slots].to(torch.float64).view(-1, self.Em, self.P)
-            sums = torch.stack([(reward * live).sum((0, 1)), live.sum((0, 1))]).cpu().numpy()
-            with np.errstate(invalid="ignore", divide="ignore"):
-                s["mean_reward"] = np.where(sums[1] > 0, sums[0] / sums[1], np.nan)
-            s.update(self.episode_stats())
-            log.append(s)
-            if callback is not None:
-                callback(i, s)
-        return log
+    def _mean_reward(self, slots):
+        """[P]: of every member's new TimeSteps that are not FIRST (one read-back)."""
+        live = (self._step_type[slots] != STEP_FIRST).to(torch.float64).view(-1, self.Em, self.P)
+        reward = self._reward[slots].to(torch.float64).view(-1, self.Em, self.P)
+        sums = torch.stack([(reward * live).sum((0, 1)), live.sum((0, 1))]).cpu().numpy()
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(sums[1] > 0, sums[0] / sums[1], np.nan)
 
     # -- evaluation ----------------------------------------------------------------------------------------------------
-    def act(self, observation, deterministic: bool = True):
-        """The action for an observation dict of E rows, each env by its member's policy: [E, A] of the engine's dtype in
-        [-1, 1] (what a CanonicalSpecWrapper's step takes).  Live: the next call overwrites it."""
-        with torch.cuda.device(self._dev):
-            st = self._stream()
-            self._pack_observation(observation, st)
-            self._act(self._e_obs, self.Em, INTERLEAVED, st, action=self._e_action.data_ptr(),
-                      logp=self._e_logp.data_ptr(), env_action=self._e_env_action.data_ptr(), precision=self._precision,
-                      deterministic=deterministic)
-            if not deterministic:
-                self._round += 1
-        return self._e_env_action
-
     def actor_of(self, p: int):
         """Member p's actor as a plain `nn.Sequential` (a copy): what `droq.DroQ.actor` or `offpolicy.SAC.actor` of a
         single-learner env batch loads with `load_state_dict(actor_of(p).state_dict())`."""
@@ -653,73 +491,20 @@ class DroQPopulation(DeviceLearner):
 
     # -- checkpoint / resume -------------------------------------------------------------------------------------------
     def state_dict(self, include_replay: bool = False):
-        """SAC's contract on the stacked tensors, plus "members" and DroQ's "droq" block; the whole ring only with
-        `include_replay`.  With the env's own `state_dict()` the next `collect()` is resumed bit for bit.  With
-        critic_step="fused" also the mode and the critics' Adam state (the stacked m, v per tensor and the step count)."""
-        c = lambda t: t.detach().clone()
-        nets = lambda ms: [{k: c(v) for k, v in m.state_dict().items()} for m in ms]
-        newest = (self.n_written - 1) % self.C if self.n_written else 0
-        sd = {"members": self.P, "droq": {"dropout": self.dropout, "utd": self.utd, "ln_eps": self.ln_eps},
-              "actor": nets([self.actor])[0], "critics": nets(self.critics), "targets": nets(self.targets),
-              "log_alpha": c(self.log_alpha), "gamma": c(self.gamma), "target_entropy": c(self.target_entropy),
-              "optimizers": {k: copy.deepcopy(getattr(self, k + "_optimizer").state_dict())
-                             for k in ("actor", "critic", "alpha")},
-              "normalizer": self._normalizer_state(),
-              "seed": self.seed, "round": self._round, "n_written": self.n_written, "generator": self._gen.get_state(),
-              "newest": {"obs": c(self._obs[newest]), "reward": c(self._reward[newest]),
-                         "discount": c(self._discount[newest]), "step_type": c(self._step_type[newest])},
-              "episodes": self._episodes_state()}
-        if self.critic_mode == "fused":
-            sd["droq"]["critic_step"] = "fused"
-            moments = lambda group: [[c(t) for t in net] for net in group]
-            sd["critic_adam"] = {"m": moments(self._c_m), "v": moments(self._c_v), "t": self._c_t}
-        if include_replay:
-            sd["replay"] = {k: c(v) for k, v in self.ring().items()}
+        """The replay learner's contract on the stacked tensors and DroQ's blocks, plus "members", "gamma" and
+        "target_entropy"."""
+        sd = super().state_dict(include_replay)
+        sd.update(members=self.P, gamma=self.gamma.detach().clone(), target_entropy=self.target_entropy.detach().clone())
         return sd
 
     def load_state_dict(self, sd):
-        """Without the ring in `sd` the ring restarts from the newest slot alone (SAC's rule).  A checkpoint written with
-        another `members`, dropout, utd, ln_eps or critic_step is refused."""
+        """A checkpoint written with another `members`, dropout, utd, ln_eps or critic_step is refused."""
         if sd.get("members") != self.P:
             raise ValueError(f"the checkpoint was written with members = {sd.get('members', 'nothing')}, this population "
                              f"has members = {self.P}")
-        mine = {"dropout": self.dropout, "utd": self.utd, "ln_eps": self.ln_eps}
-        for k, v in mine.items():
-            if "droq" not in sd or sd["droq"].get(k) != v:
-                got = sd.get("droq", {}).get(k, "nothing")
-                raise ValueError(f"the checkpoint was written with {k} = {got}, this population has {k} = {v}")
-        got = sd["droq"].get("critic_step", "torch")
-        if got != self.critic_mode:
-            raise ValueError(f"the checkpoint was written with critic_step = {got}, this population has critic_step = "
-                             f"{self.critic_mode}")
-        self.actor.load_state_dict(sd["actor"])   # (in place)
-        for group, key in ((self.critics, "critics"), (self.targets, "targets")):
-            for m, s in zip(group, sd[key]):
-                m.load_state_dict(s)
-        with torch.no_grad():
-            self.log_alpha.copy_(sd["log_alpha"])
-            self.gamma.copy_(sd["gamma"])
-            self.target_entropy.copy_(sd["target_entropy"])
-        for k, s in sd["optimizers"].items():
-            getattr(self, k + "_optimizer").load_state_dict(copy.deepcopy(s))   # (Adam would adopt sd's own tensors)
-        self._load_shared_state(sd)
-        self.seed, self._round, self.n_written = int(sd["seed"]), int(sd["round"]), int(sd["n_written"])
-        self._gen.set_state(sd["generator"])
-        if "replay" in sd:
-            for k, v in sd["replay"].items():
-                self.ring()[k].copy_(v)
-        else:
-            self._step_type.fill_(STEP_LAST)
-        newest = (self.n_written - 1) % self.C if self.n_written else 0
-        for buf, key in ((self._obs, "obs"), (self._reward, "reward"), (self._discount, "discount"),
-                         (self._step_type, "step_type")):
-            buf[newest].copy_(sd["newest"][key])
-        if self.critic_mode == "fused":
-            for mine, theirs in ((self._c_m, sd["critic_adam"]["m"]), (self._c_v, sd["critic_adam"]["v"])):
-                for net, src in zip(mine, theirs):
-                    for t, s_ in zip(net, src):
-                        t.copy_(s_)
-            self._c_t = int(sd["critic_adam"]["t"])
+        super().load_state_dict(sd)
+        self.gamma.copy_(sd["gamma"])
+        self.target_entropy.copy_(sd["target_entropy"])
 
 
 def _row(values, fmt="{:9.4f}"):
@@ -733,38 +518,25 @@ def train_and_evaluate(env, rounds: int, members: int, steps_per_round: int = 16
     smallest and largest temperature, then one deterministic episode of every env through a MidiEvaluationWrapper and
     every member's precision, recall and F1 (the mean over its envs).  Stops early after `time_limit` seconds.  Returns
     (population, log of the rounds, metrics: name -> [P] array)."""
-    import time
-    from robopianist_amd.wrappers import CanonicalSpecWrapper, MidiEvaluationWrapper
     pop = DroQPopulation(env, members, **kwargs)
     P = pop.P
-    t0 = time.perf_counter()
-    rounds_log = []
     last_mean = np.full(P, np.nan)
 
-    def report(i, s):
-        rounds_log.append(s)
+    def line(i, s, seconds):
         ended = s["episodes"] > 0
         last_mean[ended] = s["mean_return"][ended]
         # (a member none of whose episodes ended in the round shows the mean of the last round in which some did)
         alpha = s.get("alpha", np.full(P, np.nan))
-        log(f"update {i + 1:4d}  episodes {int(s['episodes'].sum()):6d}  mean return per member {_row(last_mean)}  "
-            f"alpha {float(np.min(alpha)):8.5f} .. {float(np.max(alpha)):8.5f}  {time.perf_counter() - t0:7.1f} s")
+        return (f"update {i + 1:4d}  episodes {int(s['episodes'].sum()):6d}  mean return per member {_row(last_mean)}  "
+                f"alpha {float(np.min(alpha)):8.5f} .. {float(np.max(alpha)):8.5f}  {seconds:7.1f} s")
 
-    for i in range(int(rounds)):
-        pop.train(1, steps_per_round, grad_steps, callback=lambda _, s, i=i: report(i, s))
-        if time_limit is not None and time.perf_counter() - t0 > time_limit:
-            log(f"stopped after {i + 1} updates: the time limit of {time_limit:.0f} s")
-            break
-    evaluated = CanonicalSpecWrapper(MidiEvaluationWrapper(pop.env))
-    ts = evaluated.reset()
-    done = torch.zeros(pop.E, dtype=torch.bool, device=ts.step_type.device)
-    for _ in range(100000):
-        ts = evaluated.step(pop.act(ts.observation, deterministic=True))
-        done |= ts.last()
-        if bool(done.all()):
-            break
-    per_env = evaluated.get_musical_metrics_per_env()
-    metrics = {k: torch.nanmean(v.view(pop.Em, P), dim=0).cpu().numpy() for k, v in per_env.items()}
-    for k, v in metrics.items():
-        log(f"\t{k} per member: {_row(v, '{:.4f}')}")
-    return pop, rounds_log, metrics
+    def metrics(evaluated, log):
+        per_env = evaluated.get_musical_metrics_per_env()
+        found = {k: torch.nanmean(v.view(pop.Em, P), dim=0).cpu().numpy() for k, v in per_env.items()}
+        for k, v in found.items():
+            log(f"\t{k} per member: {_row(v, '{:.4f}')}")
+        return found
+
+    train_one = lambda cb: pop.train(1, steps_per_round, grad_steps, callback=cb)
+    rounds_log, found = _train_and_evaluate(pop, rounds, train_one, None, time_limit, log, line=line, metrics=metrics)
+    return pop, rounds_log, found
