@@ -121,6 +121,9 @@ def main() -> None:
                     help="--train-droq, --train-population: take the critic steps with the fused HIP step "
                          "(droq.DroQ / population.DroQPopulation(critic_step=\"fused\")) instead of torch's autograd, "
                          "Adam and lerp")
+    ap.add_argument("--fused-actor", action="store_true",
+                    help="--train-droq: take the actor and temperature steps with the fused HIP step "
+                         "(droq.DroQ(actor_step=\"fused\")) instead of torch's autograd and its two Adams")
     ap.add_argument("--train-population", type=int, default=0, metavar="ROUNDS",
                     help="train --members independent DroQ learners (population.DroQPopulation; member p owns the envs "
                          "e %% members == p) for that many rounds instead; prints the same lines and the F1, per member")
@@ -147,6 +150,8 @@ def main() -> None:
 
     if args.fused_critic and not (args.train_droq > 0 or args.train_population > 0):
         ap.error("--fused-critic goes with --train-droq or --train-population")
+    if args.fused_actor and not args.train_droq > 0:
+        ap.error("--fused-actor goes with --train-droq")
     if (args.train_ppo > 0) + (args.train_sac > 0) + (args.train_droq > 0) + (args.train_population > 0) > 1:
         ap.error("--train-ppo, --train-sac, --train-droq and --train-population are four learners: choose one")
     if args.train_population > 0:
@@ -171,7 +176,8 @@ def main() -> None:
         from robopianist_amd import droq
         droq.train_and_evaluate(load(args.n_envs), args.train_droq, time_limit=args.time_limit, seed=args.seed,
                                 batch_size=min(4096, 16 * args.n_envs),
-                                critic_step="fused" if args.fused_critic else "torch")
+                                critic_step="fused" if args.fused_critic else "torch",
+                                actor_step="fused" if args.fused_actor else "torch")
         return
     if args.train_sac > 0:
         if (args.fingertip_pianist or args.plan or args.action_sequence or args.pixels or args.hear or args.record

@@ -35,6 +35,9 @@ def main() -> None:
                     help="--train-droq, --train-population: take the critic steps with the fused HIP step "
                          "(droq.DroQ / population.DroQPopulation(critic_step=\"fused\")) instead of torch's autograd, "
                          "Adam and lerp")
+    ap.add_argument("--fused-actor", action="store_true",
+                    help="--train-droq: take the actor and temperature steps with the fused HIP step "
+                         "(droq.DroQ(actor_step=\"fused\")) instead of torch's autograd and its two Adams")
     ap.add_argument("--train-population", type=int, default=0, metavar="ROUNDS",
                     help="train --members independent DroQ learners (population.DroQPopulation; member p owns the envs "
                          "e %% members == p) for that many rounds instead; prints the same lines and the F1, per member")
@@ -44,6 +47,8 @@ def main() -> None:
     args = ap.parse_args()
     if args.fused_critic and not (args.train_droq > 0 or args.train_population > 0):
         ap.error("--fused-critic goes with --train-droq or --train-population")
+    if args.fused_actor and not args.train_droq > 0:
+        ap.error("--fused-actor goes with --train-droq")
     if (args.train_ppo > 0) + (args.train_sac > 0) + (args.train_droq > 0) + (args.train_population > 0) > 1:
         ap.error("--train-ppo, --train-sac, --train-droq and --train-population are four learners: choose one")
     if args.train_ppo > 0 or args.train_sac > 0 or args.train_droq > 0 or args.train_population > 0:
@@ -59,7 +64,8 @@ def main() -> None:
         elif args.train_droq > 0:
             droq.train_and_evaluate(env, args.train_droq, time_limit=args.time_limit,
                                     batch_size=min(4096, 16 * args.n_envs),
-                                    critic_step="fused" if args.fused_critic else "torch")
+                                    critic_step="fused" if args.fused_critic else "torch",
+                                    actor_step="fused" if args.fused_actor else "torch")
         elif args.train_population > 0:
             population.train_and_evaluate(env, args.train_population, args.members, time_limit=args.time_limit,
                                           batch_size=max(1, min(4096, 16 * args.n_envs) // args.members),

@@ -7,7 +7,9 @@ stream and reads nothing back.  An actor step draws its utd x B rows with one `r
 their next observations with one `rp_sac_act` launch; every critic step is one `rp_droq_target` launch on its B rows
 plus plain torch (the loss, autograd with torch's own dropout, Adam, the Polyak step), or, with
 `DroQ(critic_step="fused")`, plus the two launches of `critic.step` (include/learn/rp_critic.h), whose dropout masks are
-a function of (seed, round) too.  What does not depend on the number of learners is `DroQCore`, which
+a function of (seed, round) too; the actor's and the temperature's step is plain torch, or, with
+`DroQ(actor_step="fused")`, the two launches of `actor.step` (include/learn/rp_actor.h).  What does not depend on the
+number of learners is `DroQCore`, which
 `population.DroQPopulation` shares.  Like the engine, the library has no CPU fallback: a missing library is an error.
 """
 
@@ -16,7 +18,7 @@ from __future__ import annotations
 import ctypes
 import os
 
-from robopianist_amd import _abi, critic, offpolicy
+from robopianist_amd import _abi, actor, critic, offpolicy
 from robopianist_amd.learning import LearnError, Mlp, _train_and_evaluate
 from robopianist_amd.offpolicy import SAC, _masked_mean, actor_loss, alpha_loss, critic_loss, squashed_gaussian
 
@@ -109,18 +111,20 @@ def target(next_obs, action, logp, reward, discount, mean, inv_std, obs_clip, ga
 class DroQCore:
     """What the DroQ learners (`DroQ`, population's `DroQPopulation`) share, as a mixin in front of an
     `offpolicy.ReplayLearner`: the hyper-parameters, the critic's architecture and its ten tensors, the utd ranges of the
-    minibatch, the schedule of `update()`, the bookkeeping of the fused critic step and the "droq" and "critic_adam" blocks
-    of the checkpoint.  A subclass states `draw_and_act()`, `target_range(u)`, the torch body of `critic_step()`,
+    minibatch, the schedule of `update()`, the bookkeeping of the fused critic step and of the fused actor step and the
+    "droq", "critic_adam" and "actor_adam" blocks of the checkpoint.  A subclass states `draw_and_act()`, `target_range(u)`, the torch body of `critic_step()`,
     `actor_step()`, `_fused_range()`, and of the fused step its workspace (`_workspace_bytes()`), its launch
     (`_launch_critic_step()`) and its loss (`_range_loss(u)`)."""
 
     _me = "learner"   # (how the checkpoint's refusals name the reader)
 
-    def _init_droq(self, dropout, utd, ln_eps, critic_step):
+    def _init_droq(self, dropout, utd, ln_eps, critic_step, actor_step="torch"):
         self.dropout, self.utd, self.ln_eps = float(dropout), int(utd), float(ln_eps)
         if critic_step not in ("torch", "fused"):
             raise ValueError(f'critic_step must be "torch" or "fused", got {critic_step!r}')
-        self.critic_mode = critic_step
+        if actor_step not in ("torch", "fused"):
+            raise ValueError(f'actor_step must be "torch" or "fused", got {actor_step!r}')
+        self.critic_mode, self.actor_mode = critic_step, actor_step
         if not 0.0 <= self.dropout < 1.0:
             raise ValueError(f"dropout must lie in [0, 1), got {dropout}")
         if self.utd < 1:
@@ -144,6 +148,13 @@ class DroQCore:
             self._c_t = 0
             self._c_bytes = self._workspace_bytes()
             self._c_ws, self._u_q = z(max(self._c_bytes // 4, 1)), z(self.n_critics, n)
+        if self.actor_mode == "fused":
+            self._a_m = [torch.zeros_like(t) for t in self._actor_tensors()]
+            self._a_v = [torch.zeros_like(t) for t in self._actor_tensors()]
+            self._la_m, self._la_v = torch.zeros_like(self.log_alpha), torch.zeros_like(self.log_alpha)
+            self._a_t = self._la_t = 0
+            self._a_bytes = actor.workspace_bytes(self.H1, self.H2, self.A, self.B)
+            self._a_ws, self._a_stats = z(max(self._a_bytes // 4, 1)), z(len(actor.STATS))
 
     def _draw_member(self):
         """One learner's actor (SAC's tanh network) and critics, drawn in this order from torch's global generator."""
@@ -170,7 +181,44 @@ class DroQCore:
         """`net` as rp_droq_critic: the addresses of the parameters as they are now."""
         return critic_entry(self._critic_tensors(net))
 
+    def _actor_tensors(self):
+        """The six parameters of the actor in rp_actor_set's order, as they are now."""
+        import torch
+        tensors = [t for i in (0, 2, 4) for t in (self.actor[i].weight, self.actor[i].bias)]
+        for t in tensors:
+            if not t.is_contiguous() or t.dtype != torch.float32:
+                raise LearnError(f"{self._reads} contiguous float32 parameters")
+        return tensors
+
     # -- the gradient steps ----------------------------------------------------------------------------------------------
+    def _fused_actor_step(self, u):
+        """The fused actor and temperature step on range u: two launches; returns the device array of its statistics
+        (actor.STATS' order), which `_host_stats` reads."""
+        import torch
+        ga, gt = self.actor_optimizer.param_groups[0], self.alpha_optimizer.param_groups[0]
+        self._a_t += 1
+        self._la_t += 1
+        with torch.cuda.device(self._dev):
+            actor.step(self._u_obs.data_ptr(), self._u_mask.data_ptr(), self._mean_f32.data_ptr(), self._inv_std_f32.data_ptr(),
+                       self.obs_clip, actor.set_entry(self._actor_tensors()), actor.set_entry(self._a_m),
+                       actor.set_entry(self._a_v), [critic.set_entry(self._critic_tensors(c)) for c in self.critics],
+                       self.log_alpha.data_ptr(), self._la_m.data_ptr(), self._la_v.data_ptr(), self.target_entropy,
+                       self.log_std_bounds, self._a_ws.data_ptr(), self._a_bytes, self._a_stats.data_ptr(), self.D, self.H1,
+                       self.H2, self.A, self.utd * self.B,
+                       actor.adam_entry(ga["lr"], self._a_t, ga["betas"], ga["eps"]),
+                       actor.adam_entry(gt["lr"], self._la_t, gt["betas"], gt["eps"]), threshold=self._threshold,
+                       keep_scale=self._keep_scale, ln_eps=self.ln_eps, seed=self.seed, round_=self._round,
+                       row_first=u * self.B, row_count=self.B, hip_stream=self._stream())
+        return {"actor_stats": self._a_stats}
+
+    def _host_stats(self, stats):
+        """The replay learner's read-back; the fused actor step's five statistics come from its device array."""
+        stats = dict(stats)
+        fused = stats.pop("actor_stats", None)
+        if fused is not None:
+            stats.update(zip(actor.STATS, fused.tolist()))
+        return super()._host_stats(stats)
+
     def _fused_critic_step(self, u, loss):
         """The fused step on range u: two launches; the loss (from the step's q, y and mask) only where asked for."""
         import torch
@@ -203,7 +251,7 @@ class DroQCore:
                 else:
                     lc = self.critic_step(batch)
             stats = dict({} if lc is None else {"critic_loss": lc}, **self.actor_step(batch))
-            if self.critic_mode == "fused":
+            if self.critic_mode == "fused" and self.actor_mode == "torch":
                 self.critic_optimizer.zero_grad(set_to_none=True)   # (the actor pass's critic gradients: nobody reads them)
             self._round += 1
         return self._host_stats(stats)
@@ -218,6 +266,11 @@ class DroQCore:
             sd["droq"]["critic_step"] = "fused"
             c = lambda group: [[t.detach().clone() for t in net] for net in group]
             sd["critic_adam"] = {"m": c(self._c_m), "v": c(self._c_v), "t": self._c_t}
+        if self.actor_mode == "fused":
+            sd["droq"]["actor_step"] = "fused"
+            c = lambda group: [t.detach().clone() for t in group]
+            sd["actor_adam"] = {"actor": {"m": c(self._a_m), "v": c(self._a_v), "t": self._a_t},
+                                "log_alpha": {"m": self._la_m.detach().clone(), "v": self._la_v.detach().clone(), "t": self._la_t}}
         return sd
 
     def load_state_dict(self, sd):
@@ -231,7 +284,19 @@ class DroQCore:
         if got != self.critic_mode:
             raise ValueError(f"the checkpoint was written with critic_step = {got}, this {self._me} has critic_step = "
                              f"{self.critic_mode}")
+        got = sd["droq"].get("actor_step", "torch")
+        if got != self.actor_mode:
+            raise ValueError(f"the checkpoint was written with actor_step = {got}, this {self._me} has actor_step = "
+                             f"{self.actor_mode}")
         super().load_state_dict(sd)
+        if self.actor_mode == "fused":
+            mine = sd["actor_adam"]
+            for group, src in ((self._a_m, mine["actor"]["m"]), (self._a_v, mine["actor"]["v"])):
+                for t, s_ in zip(group, src):
+                    t.copy_(s_)
+            self._la_m.copy_(mine["log_alpha"]["m"])
+            self._la_v.copy_(mine["log_alpha"]["v"])
+            self._a_t, self._la_t = int(mine["actor"]["t"]), int(mine["log_alpha"]["t"])
         if self.critic_mode == "fused":
             for mine, theirs in ((self._c_m, sd["critic_adam"]["m"]), (self._c_v, sd["critic_adam"]["v"])):
                 for net, src in zip(mine, theirs):
@@ -251,11 +316,17 @@ class DroQ(DroQCore, SAC):
 
     `critic_step`: "torch" (the default: autograd with torch's own dropout, torch's Adam, `_foreach_lerp_`) or "fused"
     (`critic.step`: the same step in two launches, with Philox dropout masks keyed by (seed, round, row); the learner
-    then owns Adam's m and v and its step count, and torch's critic optimiser stays unused)."""
+    then owns Adam's m and v and its step count, and torch's critic optimiser stays unused).
+
+    `actor_step`: "torch" (the default: autograd through the actor and every critic, a draw from the learner's
+    `torch.Generator`, torch's two Adams) or "fused" (`actor.step`, include/learn/rp_actor.h: the actor's and the
+    temperature's step in two launches, with noise and dropout masks keyed by (seed, round, row); the learner then owns the
+    two optimisers' m, v and step counts, its generator is not advanced and no parameter gets a .grad).  The two options
+    are independent."""
 
     def __init__(self, env, *sac_args, dropout: float = 0.01, utd: int = 20, ln_eps: float = 1e-5,
-                 critic_step: str = "torch", **sac_kwargs):
-        self._init_droq(dropout, utd, ln_eps, critic_step)
+                 critic_step: str = "torch", actor_step: str = "torch", **sac_kwargs):
+        self._init_droq(dropout, utd, ln_eps, critic_step, actor_step)
         super().__init__(env, *sac_args, **sac_kwargs)
         self._init_ranges(self.utd * self.B)
         self._set_range(self.utd - 1)
@@ -308,14 +379,14 @@ class DroQ(DroQCore, SAC):
         return batch
 
     # -- the gradient steps ----------------------------------------------------------------------------------------------
-    def _fused_range(self, batch):
+    def _fused_range(self, batch, option="critic_step"):
         """The range u whose views `batch` holds (what `target_range(u)` and `minibatch()` return)."""
         D, B = self.D, self.B
         off = batch["obs"].data_ptr() - self._u_obs.data_ptr()
         u = off // (4 * D * B)
         if off < 0 or off % (4 * D * B) or u >= self.utd or batch["obs"].shape[0] != B or \
                 any(batch[k].data_ptr() != getattr(self, "_u_" + k)[u * B:].data_ptr() for k in ("action", "y", "mask")):
-            raise LearnError('critic_step="fused" steps on a range of the learner\'s own minibatch: pass what '
+            raise LearnError(f'{option}="fused" steps on a range of the learner\'s own minibatch: pass what '
                              "target_range(u) or minibatch() returned")
         return u
 
@@ -344,8 +415,12 @@ class DroQ(DroQCore, SAC):
         return lc.detach()
 
     def actor_step(self, batch):
-        """The actor's and the temperature's Adam steps on `batch`; the critics stay in train() mode, as in the paper."""
+        """The actor's and the temperature's Adam steps on `batch`; the critics stay in train() mode, as in the paper.
+        With actor_step="fused": the two launches of `actor.step` on the range `batch` views; the statistics then stay on
+        the device until `_host_stats` reads them."""
         import torch
+        if self.actor_mode == "fused":
+            return self._fused_actor_step(self._fused_range(batch, "actor_step"))
         mask = batch["mask"]
         xn = self.normalize(batch["obs"])
         eps = torch.randn(xn.shape[0], self.A, generator=self._gen, device=xn.device)

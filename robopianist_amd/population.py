@@ -273,7 +273,8 @@ class DroQPopulation(DroQCore, ReplayLearner):
     `critic_step`: "torch" (the default: autograd on the stacked tensors with torch's own dropout, torch's Adam,
     `_foreach_lerp_`) or "fused" (`pop_critic.step`: the step of all members in two launches, with Philox dropout masks
     keyed by (seed, round, row); the population then owns Adam's stacked m and v and one step count for all members,
-    and torch's critic optimiser stays unused) -- `droq.DroQ`'s contract."""
+    and torch's critic optimiser stays unused) -- `droq.DroQ`'s contract.  `actor_step`: "torch" only; `droq.DroQ`'s "fused"
+    (`actor.step`) is refused here: the population's actor step stays the stacked torch one."""
 
     _reads, _me = "the population kernels read", "population"
 
@@ -281,9 +282,12 @@ class DroQPopulation(DroQCore, ReplayLearner):
                  batch_size: int = 256, gamma=0.99, tau: float = 0.005, lr: float = 3e-4, init_alpha=1.0,
                  target_entropy=None, log_std_bounds=(-5.0, 2.0), learning_starts: int = 0, obs_clip: float = 10.0,
                  seed: int = 0, norm_eps: float = 1e-8, dropout: float = 0.01, utd: int = 20, ln_eps: float = 1e-5,
-                 critic_step: str = "torch"):
+                 critic_step: str = "torch", actor_step: str = "torch"):
         super().__init__(env)
-        self._init_droq(dropout, utd, ln_eps, critic_step)
+        if actor_step == "fused":
+            raise ValueError('DroQPopulation has no fused actor step yet: actor_step="fused" is droq.DroQ\'s; a population '
+                             'takes actor_step="torch"')
+        self._init_droq(dropout, utd, ln_eps, critic_step, actor_step)
         self.P = P = int(members)
         if P < 1:
             raise ValueError(f"members must be >= 1, got {members}")
