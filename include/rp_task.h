@@ -133,7 +133,7 @@ typedef struct rp_task_advance_args {
    * robopianist_amd/distributed.py: pack_trajectory_record), written by this launch straight into the buffer the
    * all-gather sends -- no allocation and no extra launch per step on the N > 1 path.  One row per env, in the engine's
    * precision T:  qpos[nv] | reward | discount | step_type | the 88 activation bits as raw bytes (little-endian, key k
-   * = bit k % 8 of byte k / 8) in the last 16 / sizeof(T) + (T == float) words, i.e. 2 (double) or 3 (float).
+   * = bit k % 8 of byte k / 8) in the last 2 (double: 16 bytes) or 3 (float: 12 bytes) words.
    * Row length = nv + 3 + (T == double ? 2 : 3). */
   void* traj_record;
 } rp_task_advance_args;
@@ -158,7 +158,7 @@ typedef struct rp_task_prestep_args {
   const void* act_range;             /* [n_action] hi - lo (with act_lo) */
   int clip;
   const unsigned char* needs_reset;  /* [E] */
-  const int* hand_act;               /* [n_action - 1] */
+  const int* hand_act;               /* [n_action - 1] (may be NULL when n_action == 1: the pedal alone) */
   void* ctrl;                        /* [E][nu], rows of the envs that are stepped */
   void* sustain_state;               /* [E] */
   int* active;                       /* [E] out */

@@ -515,7 +515,7 @@ int rp_task_prestep(const rp_task_prestep_args* a, void* hip_stream) {
   if (a->precision != 32 && a->precision != 64) { g_task_err = "rp_task_prestep: precision must be 32 or 64"; return -1; }
   if (a->n_envs <= 0 || a->n_action < 1 || a->nu < a->n_action - 1) { g_task_err = "rp_task_prestep: bad sizes"; return -1; }
   if ((!a->action && !a->action_table) || (a->action_table && (!a->action_index || a->action_table_len <= 0)) || !a->needs_reset ||
-      !a->hand_act || !a->ctrl || !a->sustain_state || !a->active || !a->reset_mask || (a->act_lo && !a->act_range)) {
+      (a->n_action > 1 && !a->hand_act) || !a->ctrl || !a->sustain_state || !a->active || !a->reset_mask || (a->act_lo && !a->act_range)) {
     g_task_err = "rp_task_prestep: null array pointer";
     return -1;
   }
