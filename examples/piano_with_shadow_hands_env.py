@@ -131,6 +131,12 @@ def main() -> None:
     ap.add_argument("--member-envs", dest="member_envs", default=None, metavar="NAME[,NAME...]",
                     help="--train-population: environment names of suite.ALL, one (every member learns that song) or "
                          "--members of them (member p learns song p); default: --env_name")
+    ap.add_argument("--evolve-every", dest="evolve_every", type=int, default=0, metavar="N",
+                    help="--train-population: population-based training (population.DroQPopulation(evolve=...)): after "
+                         "every N rounds the worst members take the best members' networks, with gamma and target_entropy "
+                         "perturbed; 0 (the default): the members stay independent")
+    ap.add_argument("--evolve-percent", dest="evolve_percent", type=int, default=25, metavar="Q",
+                    help="--evolve-every: the share of the members at either end, in percent")
     ap.add_argument("--time-limit", type=float, default=None,
                     help="--train-ppo, --train-sac, --train-droq, --train-population: stop after that many seconds")
     args = ap.parse_args()
@@ -152,6 +158,9 @@ def main() -> None:
         ap.error("--fused-critic goes with --train-droq or --train-population")
     if args.fused_actor and not args.train_droq > 0:
         ap.error("--fused-actor goes with --train-droq")
+    if args.evolve_every and not args.train_population > 0:
+        ap.error("--evolve-every goes with --train-population")
+    evolve = dict(every=args.evolve_every, percent=args.evolve_percent) if args.evolve_every else None
     if (args.train_ppo > 0) + (args.train_sac > 0) + (args.train_droq > 0) + (args.train_population > 0) > 1:
         ap.error("--train-ppo, --train-sac, --train-droq and --train-population are four learners: choose one")
     if args.train_population > 0:
@@ -167,7 +176,7 @@ def main() -> None:
             env = _load_members(args, args.n_envs, names)
         population.train_and_evaluate(env, args.train_population, args.members, time_limit=args.time_limit, seed=args.seed,
                                       batch_size=max(1, min(4096, 16 * args.n_envs) // args.members),
-                                      critic_step="fused" if args.fused_critic else "torch")
+                                      critic_step="fused" if args.fused_critic else "torch", evolve=evolve)
         return
     if args.train_droq > 0:
         if (args.fingertip_pianist or args.plan or args.action_sequence or args.pixels or args.hear or args.record

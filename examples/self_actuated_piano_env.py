@@ -42,6 +42,12 @@ def main() -> None:
                     help="train --members independent DroQ learners (population.DroQPopulation; member p owns the envs "
                          "e %% members == p) for that many rounds instead; prints the same lines and the F1, per member")
     ap.add_argument("--members", type=int, default=8, help="--train-population: the number of members (divides --n_envs)")
+    ap.add_argument("--evolve-every", dest="evolve_every", type=int, default=0, metavar="N",
+                    help="--train-population: population-based training (population.DroQPopulation(evolve=...)): after "
+                         "every N rounds the worst members take the best members' networks, with gamma and target_entropy "
+                         "perturbed; 0 (the default): the members stay independent")
+    ap.add_argument("--evolve-percent", dest="evolve_percent", type=int, default=25, metavar="Q",
+                    help="--evolve-every: the share of the members at either end, in percent")
     ap.add_argument("--time-limit", type=float, default=None,
                     help="--train-ppo, --train-sac, --train-droq, --train-population: stop after that many seconds")
     args = ap.parse_args()
@@ -49,6 +55,9 @@ def main() -> None:
         ap.error("--fused-critic goes with --train-droq or --train-population")
     if args.fused_actor and not args.train_droq > 0:
         ap.error("--fused-actor goes with --train-droq")
+    if args.evolve_every and not args.train_population > 0:
+        ap.error("--evolve-every goes with --train-population")
+    evolve = dict(every=args.evolve_every, percent=args.evolve_percent) if args.evolve_every else None
     if (args.train_ppo > 0) + (args.train_sac > 0) + (args.train_droq > 0) + (args.train_population > 0) > 1:
         ap.error("--train-ppo, --train-sac, --train-droq and --train-population are four learners: choose one")
     if args.train_ppo > 0 or args.train_sac > 0 or args.train_droq > 0 or args.train_population > 0:
@@ -69,7 +78,7 @@ def main() -> None:
         elif args.train_population > 0:
             population.train_and_evaluate(env, args.train_population, args.members, time_limit=args.time_limit,
                                           batch_size=max(1, min(4096, 16 * args.n_envs) // args.members),
-                                          critic_step="fused" if args.fused_critic else "torch")
+                                          critic_step="fused" if args.fused_critic else "torch", evolve=evolve)
         else:
             learning.train_and_evaluate(env, args.train_ppo, time_limit=args.time_limit)
         return

@@ -1,6 +1,6 @@
-"""What the ctypes bindings of the HIP libraries share: the library opener (all fourteen bindings) and the entry table of the
+"""What the ctypes bindings of the HIP libraries share: the library opener (all fifteen bindings) and the entry table of the
 libraries whose entry points take one argument block each (planning, learning, offpolicy, droq, population, critic, pop_critic,
-actor)."""
+actor, evolve)."""
 
 from __future__ import annotations
 

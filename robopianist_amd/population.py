@@ -10,7 +10,9 @@ stacked parameters.  The ring is SAC's [C][E]..., written by the learner's uncha
 torch on stacked parameters [P][out][in] (`torch.baddbmm`): a loss is the sum over the members of the per-member masked
 means, so member p's gradient depends on member p's rows alone, and Adam, being element-wise, keeps the members
 independent.  With `DroQPopulation(critic_step="fused")` the critic step is instead the two launches of
-`pop_critic.step` (include/learn/rp_pop_critic.h) for all members.  Like the engine, the library has no CPU fallback: a
+`pop_critic.step` (include/learn/rp_pop_critic.h) for all members.  With `DroQPopulation(evolve={...})` the members meet:
+population-based training's exploit and explore steps are the three kernels of `evolve` (include/learn/rp_evolve.h) on
+the stacked tensors.  Like the engine, the library has no CPU fallback: a
 missing library is an error.
 """
 
@@ -25,7 +27,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from robopianist_amd import _abi, droq, pop_critic
+from robopianist_amd import _abi, droq, evolve as _evolve, pop_critic
 from robopianist_amd.droq import Critic, DroQCore
 from robopianist_amd.learning import STEP_FIRST, LearnError, Mlp, _train_and_evaluate, mlp_table
 from robopianist_amd.offpolicy import ReplayLearner, squashed_gaussian
@@ -260,6 +262,51 @@ def _per_member(value, P, name):
     return out
 
 
+EVOLVE_DEFAULTS = {"every": 10, "percent": 25, "min_episodes": 1, "min_gap": 0.0, "factors": (0.8, 1.25),
+                   "gamma_bounds": (0.0, 0.9999), "entropy_bounds": (-math.inf, math.inf),
+                   "explore": ("gamma", "target_entropy")}
+
+
+def _evolve_options(evolve):
+    """`DroQPopulation`'s evolve option with its defaults filled in and its values checked; None stays None."""
+    if evolve is None:
+        return None
+    if not isinstance(evolve, dict):
+        raise ValueError(f"evolve must be None or a dict of options, got {evolve!r}")
+    unknown = sorted(set(evolve) - set(EVOLVE_DEFAULTS))
+    if unknown:
+        raise ValueError(f"evolve has no option {unknown[0]!r}: its options are {', '.join(EVOLVE_DEFAULTS)}")
+    o = dict(EVOLVE_DEFAULTS, **evolve)
+    for k in ("every", "percent", "min_episodes"):
+        if isinstance(o[k], bool) or int(o[k]) != o[k]:
+            raise ValueError(f"evolve's {k} must be an integer, got {o[k]!r}")
+        o[k] = int(o[k])
+    if o["every"] < 1:
+        raise ValueError(f"evolve's every must be >= 1, got {o['every']}")
+    if not 0 <= o["percent"] <= 100:
+        raise ValueError(f"evolve's percent must lie in [0, 100], got {o['percent']}")
+    if o["min_episodes"] < 1:
+        raise ValueError(f"evolve's min_episodes must be >= 1, got {o['min_episodes']}")
+    o["min_gap"] = float(o["min_gap"])
+    if not o["min_gap"] >= 0.0:
+        raise ValueError(f"evolve's min_gap must be >= 0, got {o['min_gap']}")
+    for k in ("factors", "gamma_bounds", "entropy_bounds"):
+        if np.ndim(o[k]) != 1 or len(o[k]) != 2:
+            raise ValueError(f"evolve's {k} must be a pair, got {o[k]!r}")
+        o[k] = (float(o[k][0]), float(o[k][1]))
+    if not (o["factors"][0] > 0.0 and o["factors"][1] > 0.0):
+        raise ValueError(f"evolve's factors must be (down, up), both > 0, got {o['factors']}")
+    for k in ("gamma_bounds", "entropy_bounds"):
+        if not o[k][0] <= o[k][1]:
+            raise ValueError(f"evolve's {k} must be (min, max) with min <= max, got {o[k]}")
+    explore = (o["explore"],) if isinstance(o["explore"], str) else tuple(o["explore"])
+    for name in explore:
+        if name not in EVOLVE_DEFAULTS["explore"]:
+            raise ValueError(f'evolve explores "gamma" and "target_entropy", got {name!r}')
+    o["explore"] = tuple(k for k in EVOLVE_DEFAULTS["explore"] if k in explore)
+    return o
+
+
 class DroQPopulation(DroQCore, ReplayLearner):
     """`members` = P independent `droq.DroQ` learners over one env batch of E = P Em envs: member p collects with, and
     learns from, the envs p, p + P, p + 2 P, ... alone, and has its own actor, critics, targets, temperature, observation
@@ -274,7 +321,17 @@ class DroQPopulation(DroQCore, ReplayLearner):
     `_foreach_lerp_`) or "fused" (`pop_critic.step`: the step of all members in two launches, with Philox dropout masks
     keyed by (seed, round, row); the population then owns Adam's stacked m and v and one step count for all members,
     and torch's critic optimiser stays unused) -- `droq.DroQ`'s contract.  `actor_step`: "torch" only; `droq.DroQ`'s "fused"
-    (`actor.step`) is refused here: the population's actor step stays the stacked torch one."""
+    (`actor.step`) is refused here: the population's actor step stays the stacked torch one.
+
+    `evolve`: None (the default: the members never meet) or a dict of population-based training's options (Jaderberg et
+    al. 2017; include/learn/rp_evolve.h), every key optional: `every` (10: the rounds of `train()` between two events),
+    `percent` (25: the share of the eligible members at either end), `min_episodes` (1: the ended episodes a member's
+    window needs to be ranked), `min_gap` (0: what a winner's mean return must exceed a loser's by), `factors`
+    ((0.8, 1.25): the two perturbations (down, up)), `gamma_bounds` ((0, 0.9999)), `entropy_bounds` ((-inf, inf)) and
+    `explore` (("gamma", "target_entropy"): the hyper-parameters a copy perturbs).  `episode_stats()` then folds the
+    ended episodes' returns into every member's window before it clears them, and `evolve()` -- called by `train()` after
+    every `every`-th round -- overwrites the losers' slices of every stacked tensor with a winner's and perturbs the
+    copied `gamma` and `target_entropy`, all on the device: `rp_evolve_plan`, then `rp_evolve_copy`."""
 
     _reads, _me = "the population kernels read", "population"
 
@@ -282,8 +339,9 @@ class DroQPopulation(DroQCore, ReplayLearner):
                  batch_size: int = 256, gamma=0.99, tau: float = 0.005, lr: float = 3e-4, init_alpha=1.0,
                  target_entropy=None, log_std_bounds=(-5.0, 2.0), learning_starts: int = 0, obs_clip: float = 10.0,
                  seed: int = 0, norm_eps: float = 1e-8, dropout: float = 0.01, utd: int = 20, ln_eps: float = 1e-5,
-                 critic_step: str = "torch", actor_step: str = "torch"):
+                 critic_step: str = "torch", actor_step: str = "torch", evolve=None):
         super().__init__(env)
+        self.evolve_options = _evolve_options(evolve)
         if actor_step == "fused":
             raise ValueError('DroQPopulation has no fused actor step yet: actor_step="fused" is droq.DroQ\'s; a population '
                              'takes actor_step="torch"')
@@ -310,6 +368,13 @@ class DroQPopulation(DroQCore, ReplayLearner):
         # the minibatches: member p's utd ranges of B rows at [p n, (p + 1) n), n = utd B
         self._init_ranges(P * self.utd * self.B)
         self._range = self.utd - 1
+        if self.evolve_options is not None:
+            if P > _evolve.MAX_MEMBERS:
+                raise ValueError(f"evolve ranks at most {_evolve.MAX_MEMBERS} members, got members = {P}")
+            # the members' fitness windows, the last event's decision, the events so far and the rounds train() has run
+            self._fit_sum, self._fit_count = z(P, dtype=torch.float64), z(P, dtype=torch.int64)
+            self._source = torch.arange(P, dtype=torch.int32, device=self._dev)
+            self.generation, self._evolve_rounds = 0, 0
 
     def _draw(self):
         """(actor, critics) member after member, as P single learners of this seed's stream would draw them, stacked."""
@@ -464,6 +529,10 @@ class DroQPopulation(DroQCore, ReplayLearner):
     def episode_stats(self):
         """{"episodes" [P] int, "mean_return" [P], "mean_length" [P]} of the episodes that ended since the last call, per
         member (one read-back); the counters start again from zero."""
+        if self.evolve_options is not None:   # (the windows see the counters before they are cleared)
+            with torch.cuda.device(self._dev):
+                _evolve.fold(self._done_return.data_ptr(), self._done_count.data_ptr(), self._fit_sum.data_ptr(),
+                             self._fit_count.data_ptr(), self.E, self.P, hip_stream=self._stream())
         by_member = lambda t: t.view(self.Em, self.P).sum(0).to(torch.float64)
         host = torch.stack([by_member(self._done_count), by_member(self._done_return), by_member(self._done_len)]).cpu().numpy()
         n = host[0]
@@ -481,6 +550,75 @@ class DroQPopulation(DroQCore, ReplayLearner):
         with np.errstate(invalid="ignore", divide="ignore"):
             return np.where(sums[1] > 0, sums[0] / sums[1], np.nan)
 
+    # -- population-based training ---------------------------------------------------------------------------------------
+    def _member_fields(self):
+        """[(name, tensor)]: every tensor [P][...] a member owns a slice of, as they are now -- the actor's 6, every
+        critic's and every target's 10, log_alpha, the normaliser's four, the fused critic step's m and v, and the
+        moments of torch's three Adams where they exist.  `gamma` and `target_entropy` are the plan's to write; the step
+        counts, the normaliser's count, the ring and the generator are shared and stay out."""
+        fields = [(f"actor.{i}", t) for i, t in enumerate(self._actor_tensors())]
+        for group, nets in (("critics", self.critics), ("targets", self.targets)):
+            fields += [(f"{group}.{c}.{i}", t) for c, net in enumerate(nets) for i, t in enumerate(self._critic_tensors(net))]
+        fields.append(("log_alpha", self.log_alpha))
+        fields += [(k, getattr(self, k)) for k in ("_mean", "_M2", "_mean_f32", "_inv_std_f32")]
+        if self.critic_mode == "fused":
+            for k, group in (("_c_m", self._c_m), ("_c_v", self._c_v)):
+                fields += [(f"{k}.{c}.{i}", t) for c, net in enumerate(group) for i, t in enumerate(net)]
+        for name in ("actor", "critic", "alpha"):
+            opt = getattr(self, name + "_optimizer")
+            for i, param in enumerate(opt.param_groups[0]["params"]):
+                fields += [(f"{name}_optimizer.{i}.{k}", opt.state[param][k]) for k in ("exp_avg", "exp_avg_sq")
+                           if param in opt.state and k in opt.state[param]]
+        for name, t in fields:
+            if not t.is_contiguous() or t.shape[0] != self.P or t.element_size() % 4:
+                raise LearnError(f"evolve copies contiguous stacked tensors [members][...] of 4- or 8-byte elements: {name}")
+        return fields
+
+    def _field_table(self):
+        """`_member_fields()` as rp_evolve_field rows: (base address, 4-byte words per member)."""
+        return [(t.data_ptr(), t[0].numel() * t.element_size() // 4) for _, t in self._member_fields()]
+
+    def evolve(self):
+        """One event of population-based training on the learner's stream, nothing read back: `rp_evolve_plan` on the
+        members' fitness windows (which it clears), then `rp_evolve_copy` over `_member_fields()`; `generation`, the
+        Philox round word of the plan, then counts one more.  Returns the launches enqueued."""
+        o = self.evolve_options
+        if o is None:
+            raise LearnError("evolve() needs the population's evolve option: DroQPopulation(..., evolve={...})")
+        ptr = lambda name, t: t.data_ptr() if name in o["explore"] else None
+        with torch.cuda.device(self._dev):
+            st = self._stream()
+            _evolve.plan(self._fit_sum.data_ptr(), self._fit_count.data_ptr(), self._source.data_ptr(), self.P,
+                         percent=o["percent"], min_episodes=o["min_episodes"], min_gap=o["min_gap"], factors=o["factors"],
+                         gamma=ptr("gamma", self.gamma), gamma_bounds=o["gamma_bounds"],
+                         target_entropy=ptr("target_entropy", self.target_entropy), entropy_bounds=o["entropy_bounds"],
+                         seed=self.seed, generation=self.generation, hip_stream=st)
+            launches = 1 + _evolve.copy(self._field_table(), self._source.data_ptr(), self.P, hip_stream=st)
+        self.generation += 1
+        return launches
+
+    def last_evolution(self):
+        """`source` [P] of the last event as a numpy array (the one read-back): member p took member source[p]'s slices;
+        source[p] == p: it kept its own."""
+        if self.evolve_options is None:
+            raise LearnError("last_evolution() needs the population's evolve option")
+        return self._source.cpu().numpy()
+
+    def train(self, n: int, steps_per_round: int = 1, grad_steps: int = 1, callback=None):
+        """The replay learner's rounds; with the evolve option, `evolve()` after every `every`-th round this population
+        has trained (counted over all calls)."""
+        if self.evolve_options is None:
+            return super().train(n, steps_per_round, grad_steps, callback)
+        log = []
+        for i in range(int(n)):
+            log += ReplayLearner.train(self, 1, steps_per_round, grad_steps)
+            self._evolve_rounds += 1
+            if self._evolve_rounds % self.evolve_options["every"] == 0:
+                self.evolve()
+            if callback is not None:   # (after the round's event, so that it sees it)
+                callback(i, log[-1])
+        return log
+
     # -- evaluation ----------------------------------------------------------------------------------------------------
     def actor_of(self, p: int):
         """Member p's actor as a plain `nn.Sequential` (a copy): what `droq.DroQ.actor` or `offpolicy.SAC.actor` of a
@@ -496,19 +634,34 @@ class DroQPopulation(DroQCore, ReplayLearner):
     # -- checkpoint / resume -------------------------------------------------------------------------------------------
     def state_dict(self, include_replay: bool = False):
         """The replay learner's contract on the stacked tensors and DroQ's blocks, plus "members", "gamma" and
-        "target_entropy"."""
+        "target_entropy"; with the evolve option also "evolve": the options, `generation`, the rounds trained, the
+        fitness windows and the last event's `source`."""
         sd = super().state_dict(include_replay)
         sd.update(members=self.P, gamma=self.gamma.detach().clone(), target_entropy=self.target_entropy.detach().clone())
+        if self.evolve_options is not None:
+            sd["evolve"] = {"options": dict(self.evolve_options), "generation": self.generation,
+                            "rounds": self._evolve_rounds, "fit_sum": self._fit_sum.detach().clone(),
+                            "fit_count": self._fit_count.detach().clone(), "source": self._source.detach().clone()}
         return sd
 
     def load_state_dict(self, sd):
-        """A checkpoint written with another `members`, dropout, utd, ln_eps or critic_step is refused."""
+        """A checkpoint written with another `members`, dropout, utd, ln_eps, critic_step or evolve is refused."""
         if sd.get("members") != self.P:
             raise ValueError(f"the checkpoint was written with members = {sd.get('members', 'nothing')}, this population "
                              f"has members = {self.P}")
+        got = sd["evolve"]["options"] if "evolve" in sd else None
+        if got != self.evolve_options:
+            raise ValueError(f"the checkpoint was written with evolve = {got}, this population has evolve = "
+                             f"{self.evolve_options}")
         super().load_state_dict(sd)
         self.gamma.copy_(sd["gamma"])
         self.target_entropy.copy_(sd["target_entropy"])
+        if got is not None:
+            mine = sd["evolve"]
+            self.generation, self._evolve_rounds = int(mine["generation"]), int(mine["rounds"])
+            self._fit_sum.copy_(mine["fit_sum"])
+            self._fit_count.copy_(mine["fit_count"])
+            self._source.copy_(mine["source"])
 
 
 def _row(values, fmt="{:9.4f}"):
@@ -525,14 +678,27 @@ def train_and_evaluate(env, rounds: int, members: int, steps_per_round: int = 16
     pop = DroQPopulation(env, members, **kwargs)
     P = pop.P
     last_mean = np.full(P, np.nan)
+    evolved = {"generation": 0, "replaced": 0}
+
+    def replaced():
+        """The members replaced so far: one read-back per event (`last_evolution`), none in between."""
+        if pop.generation != evolved["generation"]:
+            source = pop.last_evolution()
+            evolved["replaced"] += int((source != np.arange(P)).sum())
+            evolved["generation"] = pop.generation
+            changed = np.flatnonzero(source != np.arange(P))
+            if len(changed):
+                log(f"\tgeneration {pop.generation}: " + ", ".join(f"member {p} <- {source[p]}" for p in changed))
+        return evolved["replaced"]
 
     def line(i, s, seconds):
         ended = s["episodes"] > 0
         last_mean[ended] = s["mean_return"][ended]
         # (a member none of whose episodes ended in the round shows the mean of the last round in which some did)
         alpha = s.get("alpha", np.full(P, np.nan))
+        swaps = f"  replaced {replaced():4d}" if pop.evolve_options is not None else ""
         return (f"update {i + 1:4d}  episodes {int(s['episodes'].sum()):6d}  mean return per member {_row(last_mean)}  "
-                f"alpha {float(np.min(alpha)):8.5f} .. {float(np.max(alpha)):8.5f}  {seconds:7.1f} s")
+                f"alpha {float(np.min(alpha)):8.5f} .. {float(np.max(alpha)):8.5f}{swaps}  {seconds:7.1f} s")
 
     def metrics(evaluated, log):
         per_env = evaluated.get_musical_metrics_per_env()
