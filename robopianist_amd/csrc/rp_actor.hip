@@ -4,7 +4,7 @@
 //   rp_actor_rows_kernel   grid (tiles of 16 rows), four waves.  The policy on the tile of rp_mlp_tile.hpp (h1 and h2 go to
 //                          the workspace as they are made: the critics need the tile's arrays), its epilogue keeping a, t,
 //                          `inside` and logp in LDS; then the critics one after the other in the critic step's tile
-//                          (rp_critic.hpp: forward with saved activations, the head, backward with dq = 1), each followed
+//                          (rp_droq.hpp: forward with saved activations, the head, backward with dq = 1), each followed
 //                          by one more transposed layer through the A action columns of its W1, whose result a row copies
 //                          only if this critic's q is the smallest so far; then the head gradient and the actor's
 //                          backward pass (W3 and W2 transposed through the same tile, h2 and h1 read back from the
@@ -33,12 +33,12 @@ namespace {
 
 __global__ __launch_bounds__(RPL_BLOCK) void rp_actor_rows_kernel(const rp_actor_step_args a, const RpaCritics cs) {
   __shared__ __attribute__((aligned(16))) float lds[RPA_ROWS_LDS_FLOATS];
-  rpa_rows_tile(a, cs, RplRowIdentity{}, (int)blockIdx.x, (float*)a.workspace, lds);
+  rpa_rows_tile(a, cs, (int)blockIdx.x, (float*)a.workspace, lds);
 }
 
 __global__ __launch_bounds__(RPL_BLOCK) void rp_actor_apply_kernel(const rp_actor_step_args a) {
   __shared__ __attribute__((aligned(16))) float lds[RPL_TILE_R * RPL_S_PITCH + RP_LEARN_MAX_H * RPL_S_PITCH];
-  rpa_apply_block(a, RplRowIdentity{}, (int)blockIdx.x, (const float*)a.workspace, lds);
+  rpa_apply_block(a, (int)blockIdx.x, (const float*)a.workspace, lds);
 }
 
 }  // namespace

@@ -2,11 +2,13 @@
 // device text of its two launches.
 //
 // The checks are host code and touch no device: a refused call returns its message before anything is launched.  The
-// device text is parametrised as rp_critic.hpp's: a row map resolved at compile time (the kernels of librp_actor.so pass
-// the identity) and the weight sets in use, by value; `member` (0 in librp_actor.so, where the compiler folds it away)
-// selects the slice of stacked tensors [P][...] whose bases the sets hold, so that a population can run it on a member's
-// rows and slices.  The critics go through rp_critic.hpp's own routines (rpc_layer, rpc_forward_rows, rpc_backward_rows),
-// which read their dropout scalars from an rp_critic_step_args: the rows launch fills one with just those.
+// device text is parametrised as rp_critic.hpp's: the weight sets in use by value, the rows through row_first, and
+// `member` (0 in librp_actor.so, where the compiler folds it away) selects the slice of stacked tensors [P][...] whose
+// bases the sets hold, so that a population can run it on a member's rows and slices.  The critics are the critic
+// step's: rp_droq.hpp's rpd_critic_forward and rpd_critic_backward on rp_critic.hpp's slices (rpc_critic_of).  The
+// layer, its store, the normalised read, the mask sum, Adam and the log-probability's per-unit term are
+// rp_mlp_tile.hpp's.  What is here is the step's own: the policy with its noise, the selection of the minimum, the dqa layer,
+// the head gradient, the tanh layers' backward pass and the apply launch.
 #ifndef RP_ACTOR_HPP_
 #define RP_ACTOR_HPP_
 
@@ -42,17 +44,9 @@ __host__ __device__ inline RpaLayout rpa_layout(int H1, int H2, int A, int R) {
 
 inline size_t rpa_workspace_bytes(int H1, int H2, int A, int R) { return rpa_layout(H1, H2, A, R).total * sizeof(float); }
 
-inline std::string rpa_check_sizes(const std::string& fn, int H1, int H2, int A) {
-  std::string err = rpl_check_hidden(fn, "H1", H1);
-  if (err.empty()) err = rpl_check_hidden(fn, "H2", H2);
-  if (!err.empty()) return err;
-  if (A < 1 || 2 * A > RP_SAC_MAX_HEAD) return fn + ": A must be 1 .. " + std::to_string(RP_SAC_MAX_HEAD / 2) + ", got " + std::to_string(A);
-  return "";
-}
-
 inline std::string rpa_check_workspace(const rp_actor_workspace_args* a) {
   const std::string fn = "rp_actor_workspace";
-  const std::string err = rpa_check_sizes(fn, a->H1, a->H2, a->A);
+  const std::string err = rpd_check_sizes(fn, 1, a->H1, a->H2, a->A);
   if (!err.empty()) return err;
   if (a->row_count < 0) return fn + ": row_count must be >= 0";
   return "";
@@ -83,9 +77,7 @@ inline std::string rpa_check_step(const rp_actor_step_args* a) {
   if (a->launches != RP_ACTOR_STEP && a->launches != RP_ACTOR_ROWS_ONLY && a->launches != RP_ACTOR_APPLY_ONLY)
     return fn + ": launches must be RP_ACTOR_STEP, RP_ACTOR_ROWS_ONLY or RP_ACTOR_APPLY_ONLY";
   if (a->D < 1) return fn + ": D must be >= 1";
-  if (a->n_critics < 1 || a->n_critics > RP_DROQ_MAX_CRITICS)
-    return fn + ": n_critics must be 1 .. " + std::to_string(RP_DROQ_MAX_CRITICS) + ", got " + std::to_string(a->n_critics);
-  err = rpa_check_sizes(fn, a->H1, a->H2, a->A);
+  err = rpd_check_sizes(fn, a->n_critics, a->H1, a->H2, a->A);
   if (!err.empty()) return err;
   const struct { const rp_actor_set* s; const char* what; } sets[3] = {{&a->p, "actor"}, {&a->m, "m of the actor"}, {&a->v, "v of the actor"}};
   for (const auto& s : sets)
@@ -139,11 +131,7 @@ __device__ inline double rpa_z(uint32_t seed_lo, uint32_t seed_hi, uint32_t roun
 
 // xn of array row e, column k < D, read and normalised in place.
 __device__ inline float rpa_x(const rp_actor_step_args& a, long long e, int k) {
-  const float x = a.obs[(size_t)e * a.D + k];
-  const float d = x - a.mean[k];
-  const float p = d * a.inv_std[k];
-  const float lo = fmaxf(p, -a.obs_clip);
-  return fminf(lo, a.obs_clip);
+  return rpl_xn(a.obs, a.mean, a.inv_std, a.obs_clip, e, a.D, k);
 }
 
 // The tile's rows of `sh` [16][RPL_H_PITCH] (H a multiple of 16) to `out` [.][H]; `out`: this thread's row, or NULL.
@@ -188,23 +176,17 @@ __device__ inline void rpa_column_sum(const float* sh, int N, float* db) {
 }
 
 #define RPA_HEAD_PITCH RP_LEARN_MAX_A
-// rp_critic.hpp's tile (the critics run in it), then six rows of 16 per-row scalars, then a, t and dqa of the selected
+// rp_droq.hpp's tile (the critics run in it), then six rows of 16 per-row scalars, then a, t and dqa of the selected
 // critic [16][RPA_HEAD_PITCH] and `inside` (bytes)
-#define RPA_ROWS_LDS_FLOATS (RPC_ROWS_LDS_FLOATS + 5 * RPL_TILE_R + 3 * RPL_TILE_R * RPA_HEAD_PITCH + RPL_TILE_R * RPA_HEAD_PITCH / 4)
+#define RPA_ROWS_LDS_FLOATS (RPD_CRITIC_LDS_FLOATS + 6 * RPL_TILE_R + 3 * RPL_TILE_R * RPA_HEAD_PITCH + RPL_TILE_R * RPA_HEAD_PITCH / 4)
 
-// The rows launch on tile `tile`.  `lds`: RPA_ROWS_LDS_FLOATS floats, 16-byte aligned.  `rows`: range row -> array row (the
-// noise's and the masks' row too).  All 256 threads call it together.
-template <typename Rows>
-__device__ __forceinline__ void rpa_rows_tile(const rp_actor_step_args& a, const RpaCritics& cs, const Rows rows, int tile, float* ws,
-                                              float* lds, const size_t member = 0) {
-  float* sa = lds;
-  float* sw = sa + RPL_TILE_R * RPL_S_PITCH;
-  float* st = sw + RP_LEARN_MAX_H * RPL_S_PITCH;    // sums, then gradients
-  float* a1 = st + RPL_TILE_R * RPL_H_PITCH;        // a critic's out1, then dz1; the actor's dh
-  float* n1 = a1 + RPL_TILE_R * RPL_H_PITCH;        // o1
-  float* a2 = n1 + RPL_TILE_R * RPL_H_PITCH;        // out2, then dz2, then dqa
-  float* n2 = a2 + RPL_TILE_R * RPL_H_PITCH;        // o2
-  float* slp = n2 + RPL_TILE_R * RPL_H_PITCH;       // per row: logp
+// The rows launch on tile `tile`.  `lds`: RPA_ROWS_LDS_FLOATS floats, 16-byte aligned.  Row l of the range is array row
+// row_first + l (the noise's and the masks' row too).  All 256 threads call it together.
+__device__ __forceinline__ void rpa_rows_tile(const rp_actor_step_args& a, const RpaCritics& cs, int tile, float* ws, float* lds,
+                                              const size_t member = 0) {
+  const RpdTile tl = rpd_tile(lds);                 // a1 is the actor's dh too, a2 a critic's dqa
+  float *sa = tl.sa, *sw = tl.sw, *st = tl.st, *a1 = tl.a1, *a2 = tl.a2;
+  float* slp = lds + RPD_CRITIC_LDS_FLOATS;         // per row: logp
   float* swt = slp + RPL_TILE_R;                    // w
   float* sla = swt + RPL_TILE_R;                    // la
   float* sgt = sla + RPL_TILE_R;                    // gt
@@ -220,22 +202,12 @@ __device__ __forceinline__ void rpa_rows_tile(const rp_actor_step_args& a, const
   float* part = ws + lay.part + (size_t)tile * lay.V;
   const int l0 = tile * RPL_TILE_R;
   const bool valid = l0 + r < R;
-  const long long e = valid ? rows((long long)a.row_first + l0 + r) : 0;
+  const long long e = valid ? (long long)a.row_first + l0 + r : 0;
   rp_actor_set P = a.p;
 #pragma unroll
   for (int k = 0; k < RP_ACTOR_PARAMS; k++) P.t[k] += member * rpa_elems(k, D, H1, H2, A);
 
-  // M: the header's MSUM
-  float pm = 0.f;
-  for (int l = tid; l < R; l += RPL_BLOCK) pm = pm + a.mask[rows((long long)a.row_first + l)];
-  sw[tid] = pm;
-  __syncthreads();
-  for (int s = RPL_BLOCK / 2; s > 0; s >>= 1) {
-    if (tid < s) sw[tid] = sw[tid] + sw[tid + s];
-    __syncthreads();
-  }
-  const float M = fmaxf(sw[0], 1.f);
-  __syncthreads();
+  const float M = rpl_mask_sum(a.mask + a.row_first, R, sw);   // the header's MSUM
   const float al = expf(a.log_alpha[member]);
   const float mk = valid ? a.mask[e] : 0.f;
   const float wt = mk / M;
@@ -247,7 +219,7 @@ __device__ __forceinline__ void rpa_rows_tile(const rp_actor_step_args& a, const
   f32x4 acc[RPL_ACC];
   auto xn = [&](int rr, int k) {
     if (l0 + rr >= R) return 0.f;
-    return rpa_x(a, rows((long long)a.row_first + l0 + rr), k);
+    return rpa_x(a, (long long)a.row_first + l0 + rr, k);
   };
   // 1. the policy
   rpl_layer(xn, D, P.t[RP_ACTOR_W1], H1, sa, sw, acc);
@@ -263,7 +235,7 @@ __device__ __forceinline__ void rpa_rows_tile(const rp_actor_step_args& a, const
     for (int idx = tid; idx < RPL_TILE_R * A; idx += RPL_BLOCK) {
       const int rr = idx / A, u = idx - rr * A;
       const bool ok = l0 + rr < R;
-      const long long ee = ok ? rows((long long)a.row_first + l0 + rr) : 0;
+      const long long ee = ok ? (long long)a.row_first + l0 + rr : 0;
       const float m = st[rr * RPL_H_PITCH + u];
       const float l = st[rr * RPL_H_PITCH + A + u];
       const float lc = fmaxf(l, a.log_std_min);
@@ -273,19 +245,7 @@ __device__ __forceinline__ void rpa_rows_tile(const rp_actor_step_args& a, const
       const float t = sd * zf;
       const float p = m + t;
       const float act = tanhf(p);
-      const float w = -2.f * p;
-      const float aw = fabsf(w);
-      const float ex = expf(-aw);
-      const float l1 = log1pf(ex);
-      const float wp = fmaxf(w, 0.f);
-      const float sp = wp + l1;
-      const float c1 = cs.ln2 - p;
-      const float c2 = c1 - sp;
-      const float lg = 2.f * c2;
-      const float q = zf * zf;
-      const float h = -0.5f * q;
-      const float g0 = h - ls;
-      sg[rr * RPA_HEAD_PITCH + u] = g0 - lg;
+      sg[rr * RPA_HEAD_PITCH + u] = rpl_logp_term(p, zf, ls, cs.ln2);
       sact[rr * RPA_HEAD_PITCH + u] = ok ? act : 0.f;
       stt[rr * RPA_HEAD_PITCH + u] = t;
       sins[rr * RPA_HEAD_PITCH + u] = (l > a.log_std_min && l < a.log_std_max) ? 1 : 0;
@@ -297,74 +257,36 @@ __device__ __forceinline__ void rpa_rows_tile(const rp_actor_step_args& a, const
       for (int u = 0; u < A; u++) s = s + sg[tid * RPA_HEAD_PITCH + u];
       const float lp = s - cs.logp_const;
       slp[tid] = lp;
-      if (l0 + tid < R && a.logp) a.logp[rows((long long)a.row_first + l0 + tid)] = lp;
+      if (l0 + tid < R && a.logp) a.logp[(long long)a.row_first + l0 + tid] = lp;
     }
     __syncthreads();
   }
 
   // 2. the critics, ascending, and the selection
-  rp_critic_step_args ca = {};   // what rpc_forward_rows reads
-  ca.round = a.round;
-  ca.seed_lo = a.seed_lo;
-  ca.seed_hi = a.seed_hi;
-  ca.keep_scale = a.keep_scale;
-  ca.drop_threshold = a.drop_threshold;
-  ca.ln_eps = a.ln_eps;
+  const RpdDrop drop = rpd_drop_of(a);
   float qm = 0.f;
   for (int i = 0; i < a.n_critics; i++) {
-    rp_critic_set C = cs.c[i];
+    const rp_droq_critic C = rpc_critic_of(cs.c[i], member, D + A, H1, H2);
+    RpdKept k1, k2;
+    const float q = rpd_critic_forward([&](int rr, int k) { return k < D ? xn(rr, k) : sact[rr * RPA_HEAD_PITCH + (k - D)]; }, D + A, H1, H2,
+                                       C, (uint32_t)e, RP_ACTOR_COUNTER + 2u * (uint32_t)i, drop, tl, k1, k2, nullptr);
+    const bool take = i == 0 || q < qm;
+    if (take) qm = q;
+    // st <- dout2 = w3 (dq = 1)
 #pragma unroll
-    for (int k = 0; k < RP_CRITIC_PARAMS; k++) C.t[k] += member * rpc_elems(k, D + A, H1, H2);
-    const uint32_t ctr = RP_ACTOR_COUNTER + 2u * (uint32_t)i;
-    float r1, r2;
-    rpc_layer<false>([&](int rr, int k) { return k < D ? xn(rr, k) : sact[rr * RPA_HEAD_PITCH + (k - D)]; },
-                     [&](int n, int k) { return C.t[RP_CRITIC_W1][(size_t)n * (D + A) + k]; }, D + A, H1, sa, sw, acc);
-    rpc_store(acc, C.t[RP_CRITIC_B1], H1, st);
-    const uint32_t bits1 = rpc_forward_rows(st, a1, n1, H1, C.t[RP_CRITIC_G1], C.t[RP_CRITIC_BE1], (uint32_t)e, ctr, ca, r1, nullptr);
-    rpc_layer<false>([&](int rr, int k) { return a1[rr * RPL_H_PITCH + k]; },
-                     [&](int n, int k) { return C.t[RP_CRITIC_W2][(size_t)n * H1 + k]; }, H1, H2, sa, sw, acc);
-    rpc_store(acc, C.t[RP_CRITIC_B2], H2, st);
-    const uint32_t bits2 = rpc_forward_rows(st, a2, n2, H2, C.t[RP_CRITIC_G2], C.t[RP_CRITIC_BE2], (uint32_t)e, ctr + 1u, ca, r2, nullptr);
-    // the head; st <- dout2 = w3 (dq = 1)
-    bool take;
-    {
-      const float* w3 = C.t[RP_CRITIC_W3];
-      const int groups = H2 >> 2;
-      float p = 0.f;
+    for (int g = 0; g < RPD_GROUPS; g++) {
+      const int grp = j + RPD_ROW_LANES * g;
+      if (grp < (H2 >> 2)) {
 #pragma unroll
-      for (int g = 0; g < RPD_GROUPS; g++) {
-        const int grp = j + RPD_ROW_LANES * g;
-        if (grp < groups) {
-#pragma unroll
-          for (int c = 0; c < 4; c++) {
-            const float t = a2[r * RPL_H_PITCH + 4 * grp + c] * w3[4 * grp + c];
-            p = p + t;
-          }
-        }
+        for (int c = 0; c < 4; c++) st[r * RPL_H_PITCH + 4 * grp + c] = C.net.w3[4 * grp + c];
       }
-      const float s = rpd_row_sum(p);
-      const float q = s + C.t[RP_CRITIC_B3][0];
-      take = i == 0 || q < qm;
-      if (take) qm = q;
-#pragma unroll
-      for (int g = 0; g < RPD_GROUPS; g++) {
-        const int grp = j + RPD_ROW_LANES * g;
-        if (grp < groups) {
-#pragma unroll
-          for (int c = 0; c < 4; c++) st[r * RPL_H_PITCH + 4 * grp + c] = w3[4 * grp + c];
-        }
-      }
-      __syncthreads();
     }
-    rpc_backward_rows(st, a2, n2, H2, C.t[RP_CRITIC_G2], bits2, r2, a.keep_scale, nullptr);
-    rpc_layer<true>([&](int rr, int k) { return st[rr * RPL_H_PITCH + k]; },
-                    [&](int n, int k) { return C.t[RP_CRITIC_W2][(size_t)k * H1 + n]; }, H2, H1, sa, sw, acc);
-    rpc_store(acc, nullptr, H1, st);
-    rpc_backward_rows(st, a1, n1, H1, C.t[RP_CRITIC_G1], bits1, r1, a.keep_scale, nullptr);
+    __syncthreads();
+    rpd_critic_backward(H1, H2, C, a.keep_scale, tl, k1, k2, nullptr, nullptr, [] {});
     // dqa: the A action columns of W1, transposed
-    rpc_layer<true>([&](int rr, int k) { return st[rr * RPL_H_PITCH + k]; },
-                    [&](int n, int k) { return C.t[RP_CRITIC_W1][(size_t)k * (D + A) + D + n]; }, H1, A, sa, sw, acc);
-    rpc_store(acc, nullptr, A, a2);
+    rpl_layer_of<true>([&](int rr, int k) { return st[rr * RPL_H_PITCH + k]; },
+                       [&](int n, int k) { return C.net.w1[(size_t)k * (D + A) + D + n]; }, H1, A, sa, sw, acc);
+    rpl_store_layer<false, false>(acc, nullptr, A, a2);
     if (take)
       for (int u = j; u < A; u += RPD_ROW_LANES) sdqa[r * RPA_HEAD_PITCH + u] = a2[r * RPL_H_PITCH + u];
   }
@@ -412,61 +334,28 @@ __device__ __forceinline__ void rpa_rows_tile(const rp_actor_step_args& a, const
   if (valid)
     for (int n = j; n < N3; n += RPD_ROW_LANES) ws[lay.dout + (size_t)(l0 + r) * N3 + n] = st[r * RPL_H_PITCH + n];
   rpa_column_sum(st, N3, part + H1 + H2);
-  rpc_layer<true>([&](int rr, int k) { return st[rr * RPL_H_PITCH + k]; },
-                  [&](int n, int k) { return P.t[RP_ACTOR_W3][(size_t)k * H2 + n]; }, N3, H2, sa, sw, acc);
-  rpc_store(acc, nullptr, H2, a1);
+  rpl_layer_of<true>([&](int rr, int k) { return st[rr * RPL_H_PITCH + k]; },
+                     [&](int n, int k) { return P.t[RP_ACTOR_W3][(size_t)k * H2 + n]; }, N3, H2, sa, sw, acc);
+  rpl_store_layer<false, false>(acc, nullptr, H2, a1);
   rpa_tanh_backward(a1, st, H2, valid ? ws + lay.h2 + (size_t)(l0 + r) * H2 : nullptr,
                     valid ? ws + lay.ds2 + (size_t)(l0 + r) * H2 : nullptr);
   rpa_column_sum(st, H2, part + H1);
-  rpc_layer<true>([&](int rr, int k) { return st[rr * RPL_H_PITCH + k]; },
-                  [&](int n, int k) { return P.t[RP_ACTOR_W2][(size_t)k * H1 + n]; }, H2, H1, sa, sw, acc);
-  rpc_store(acc, nullptr, H1, a1);
+  rpl_layer_of<true>([&](int rr, int k) { return st[rr * RPL_H_PITCH + k]; },
+                     [&](int n, int k) { return P.t[RP_ACTOR_W2][(size_t)k * H1 + n]; }, H2, H1, sa, sw, acc);
+  rpl_store_layer<false, false>(acc, nullptr, H1, a1);
   rpa_tanh_backward(a1, st, H1, valid ? ws + lay.h1 + (size_t)(l0 + r) * H1 : nullptr,
                     valid ? ws + lay.ds1 + (size_t)(l0 + r) * H1 : nullptr);
   rpa_column_sum(st, H1, part);
 }
 
-// Adam on one element with the gradient g (rp_critic.h's statements, without the Polyak step); the gradient to `pg` if given.
-__device__ inline void rpa_adam(const rp_actor_adam& o, float* pp, float* pm, float* pv, float* pg, float g) {
-  if (pg) *pg = g;
-  float m = *pm, v = *pv, p = *pp;
-  float x = g - m;
-  x = x * o.one_minus_beta1;
-  m = m + x;
-  float c = g * o.one_minus_beta2;
-  c = c * g;
-  v = v * o.beta2;
-  v = v + c;
-  float den = sqrtf(v);
-  den = den / o.bc2_sqrt;
-  den = den + o.eps;
-  float u = m / den;
-  u = u * o.step_size;
-  p = p - u;
-  *pm = m;
-  *pv = v;
-  *pp = p;
+__device__ inline RplAdam rpa_adam_of(const rp_actor_adam& o) {
+  return RplAdam{o.one_minus_beta1, o.beta2, o.one_minus_beta2, o.step_size, o.bc2_sqrt, o.eps};
 }
 
-// Adam on the 16 x N tile of a weight matrix [N][K] whose gradient `acc` holds (rpc_adam_tile's map).
-__device__ inline void rpa_adam_tile(const rp_actor_step_args& a, int which, const f32x4 (&acc)[RPL_ACC], int k0, int K, int N, size_t base) {
-  const int tid = (int)threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int r16 = lane & 15, kq = lane >> 4;
-#pragma unroll
-  for (int t = 0; t < RPL_ACC; t++) {
-    const int n = (wave + 4 * t) * 16 + r16;
-    if (n < N) {
-#pragma unroll
-      for (int reg = 0; reg < 4; reg++) {
-        const int k = k0 + 4 * kq + reg;
-        if (k < K) {
-          const size_t idx = base + (size_t)n * K + k;
-          rpa_adam(a.actor_adam, a.p.t[which] + idx, a.m.t[which] + idx, a.v.t[which] + idx,
-                   a.grad.t[which] ? a.grad.t[which] + idx : nullptr, acc[t][reg]);
-        }
-      }
-    }
-  }
+// Adam (rp_mlp_tile.hpp) on element `idx` of the actor's tensor `which` with the gradient g.
+__device__ inline void rpa_step(const rp_actor_step_args& a, int which, size_t idx, float g) {
+  rpl_adam_at(rpa_adam_of(a.actor_adam), a.p.t[which] + idx, a.m.t[which] + idx, a.v.t[which] + idx,
+           a.grad.t[which] ? a.grad.t[which] + idx : nullptr, g);
 }
 
 // The blocks of the apply launch: the column tiles of w1, w2 and w3, the blocks of bias elements, the scalar block.
@@ -474,10 +363,8 @@ __host__ __device__ inline int rpa_apply_blocks(int D, int H1, int H2, int A) {
   return ((D + 15) >> 4) + (H1 >> 4) + (H2 >> 4) + (H1 + H2 + 2 * A + RPL_BLOCK - 1) / RPL_BLOCK + 1;
 }
 
-// The apply launch: block `blk`.  `lds`: the two staging arrays of rpc_layer.
-template <typename Rows>
-__device__ __forceinline__ void rpa_apply_block(const rp_actor_step_args& a, const Rows rows, int blk, const float* ws, float* lds,
-                                                const size_t member = 0) {
+// The apply launch: block `blk`.  `lds`: the two staging arrays of the layer.
+__device__ __forceinline__ void rpa_apply_block(const rp_actor_step_args& a, int blk, const float* ws, float* lds, const size_t member = 0) {
   float* sa = lds;
   float* sw = sa + RPL_TILE_R * RPL_S_PITCH;
   const int D = a.D, A = a.A, H1 = a.H1, H2 = a.H2, R = a.row_count, N3 = 2 * a.A;
@@ -487,13 +374,14 @@ __device__ __forceinline__ void rpa_apply_block(const rp_actor_step_args& a, con
   if (blk < tiles1) {   // (block-uniform, as those below)
     const int k0 = blk * 16;
     const float* ds1 = ws + lay.ds1;
-    rpc_layer<true>(
+    rpl_layer_of<true>(
         [&](int rr, int l) {
           if (k0 + rr >= D) return 0.f;
-          return rpa_x(a, rows((long long)a.row_first + l), k0 + rr);
+          return rpa_x(a, (long long)a.row_first + l, k0 + rr);
         },
         [&](int n, int l) { return ds1[(size_t)l * H1 + n]; }, R, H1, sa, sw, acc);
-    rpa_adam_tile(a, RP_ACTOR_W1, acc, k0, D, H1, member * rpa_elems(RP_ACTOR_W1, D, H1, H2, A));
+    const size_t base = member * rpa_elems(RP_ACTOR_W1, D, H1, H2, A);
+    rpl_adam_tile(acc, k0, D, H1, [&a, base](size_t idx, float g) { rpa_step(a, RP_ACTOR_W1, base + idx, g); });
     return;
   }
   blk -= tiles1;
@@ -501,9 +389,10 @@ __device__ __forceinline__ void rpa_apply_block(const rp_actor_step_args& a, con
     const int k0 = blk * 16;
     const float* h1 = ws + lay.h1;
     const float* ds2 = ws + lay.ds2;
-    rpc_layer<true>([&](int rr, int l) { return h1[(size_t)l * H1 + k0 + rr]; },
-                    [&](int n, int l) { return ds2[(size_t)l * H2 + n]; }, R, H2, sa, sw, acc);
-    rpa_adam_tile(a, RP_ACTOR_W2, acc, k0, H1, H2, member * rpa_elems(RP_ACTOR_W2, D, H1, H2, A));
+    rpl_layer_of<true>([&](int rr, int l) { return h1[(size_t)l * H1 + k0 + rr]; },
+                       [&](int n, int l) { return ds2[(size_t)l * H2 + n]; }, R, H2, sa, sw, acc);
+    const size_t base = member * rpa_elems(RP_ACTOR_W2, D, H1, H2, A);
+    rpl_adam_tile(acc, k0, H1, H2, [&a, base](size_t idx, float g) { rpa_step(a, RP_ACTOR_W2, base + idx, g); });
     return;
   }
   blk -= tiles2;
@@ -511,9 +400,10 @@ __device__ __forceinline__ void rpa_apply_block(const rp_actor_step_args& a, con
     const int k0 = blk * 16;
     const float* h2 = ws + lay.h2;
     const float* dout = ws + lay.dout;
-    rpc_layer<true>([&](int rr, int l) { return h2[(size_t)l * H2 + k0 + rr]; },
-                    [&](int n, int l) { return dout[(size_t)l * N3 + n]; }, R, N3, sa, sw, acc);
-    rpa_adam_tile(a, RP_ACTOR_W3, acc, k0, H2, N3, member * rpa_elems(RP_ACTOR_W3, D, H1, H2, A));
+    rpl_layer_of<true>([&](int rr, int l) { return h2[(size_t)l * H2 + k0 + rr]; },
+                       [&](int n, int l) { return dout[(size_t)l * N3 + n]; }, R, N3, sa, sw, acc);
+    const size_t base = member * rpa_elems(RP_ACTOR_W3, D, H1, H2, A);
+    rpl_adam_tile(acc, k0, H2, N3, [&a, base](size_t idx, float g) { rpa_step(a, RP_ACTOR_W3, base + idx, g); });
     return;
   }
   blk -= tiles3;
@@ -527,8 +417,7 @@ __device__ __forceinline__ void rpa_apply_block(const rp_actor_step_args& a, con
     if (idx < H1) which = RP_ACTOR_B1;
     else if ((idx -= H1) < H2) which = RP_ACTOR_B2;
     else { idx -= H2; which = RP_ACTOR_B3; }
-    const size_t at = member * rpa_elems(which, D, H1, H2, A) + (size_t)idx;
-    rpa_adam(a.actor_adam, a.p.t[which] + at, a.m.t[which] + at, a.v.t[which] + at, a.grad.t[which] ? a.grad.t[which] + at : nullptr, g);
+    rpa_step(a, which, member * rpa_elems(which, D, H1, H2, A) + (size_t)idx, g);
     return;
   }
   // the temperature and the statistics: one thread
@@ -544,7 +433,7 @@ __device__ __forceinline__ void rpa_apply_block(const rp_actor_step_args& a, con
   }
   const float g = -sg;
   const float before = a.log_alpha[member];
-  rpa_adam(a.alpha_adam, a.log_alpha + member, a.log_alpha_m + member, a.log_alpha_v + member,
+  rpl_adam_at(rpa_adam_of(a.alpha_adam), a.log_alpha + member, a.log_alpha_m + member, a.log_alpha_v + member,
            a.log_alpha_grad ? a.log_alpha_grad + member : nullptr, g);
   float* stats = a.stats + member * RP_ACTOR_STATS;
   stats[RP_ACTOR_LOSS] = sl;

@@ -1,9 +1,9 @@
 // rp_critic.hip -- librp_critic.so: one critic step of DroQ (include/learn/rp_critic.h).
 //
 // The decomposition that ships: two launches per call, both with the critics side by side in grid.y.
-//   rp_critic_rows_kernel   grid (tiles of 16 rows, critics), four waves.  The tile of rp_mlp_tile.hpp with the weights
-//                           behind a loader (rpc_layer): layer 1 and layer 2 forward, each followed by a row epilogue that
-//                           keeps what the backward pass needs -- the output and the normalised value in LDS, 1 / sigma
+//   rp_critic_rows_kernel   grid (tiles of 16 rows, critics), four waves.  The tile of rp_mlp_tile.hpp, the critic of
+//                           rp_droq.hpp (rpd_critic_forward, rpd_critic_backward, which the actor step runs too):
+//                           layer 1 and layer 2 forward, each followed by a row epilogue that keeps what the backward pass needs -- the output and the normalised value in LDS, 1 / sigma
 //                           and the keep mask (16 bits: the lane's units) in registers of the sixteen lanes that own the
 //                           row.  The head is a row sum over those lanes.  Backward: layer 2's row pass, W2 transposed
 //                           through the same tile (staged along its contiguous index), layer 1's row pass.  Five [16][260]
@@ -34,12 +34,12 @@ namespace {
 
 __global__ __launch_bounds__(RPL_BLOCK) void rp_critic_rows_kernel(const rp_critic_step_args a, const RpcSets sets) {
   __shared__ __attribute__((aligned(16))) float lds[RPC_ROWS_LDS_FLOATS];
-  rpc_rows_tile(a, sets, RplRowIdentity{}, (int)blockIdx.x, (int)blockIdx.y, (float*)a.workspace, lds);
+  rpc_rows_tile(a, sets, (int)blockIdx.x, (int)blockIdx.y, (float*)a.workspace, lds);
 }
 
 __global__ __launch_bounds__(RPL_BLOCK) void rp_critic_apply_kernel(const rp_critic_step_args a, const RpcSets sets) {
   __shared__ __attribute__((aligned(16))) float lds[RPL_TILE_R * RPL_S_PITCH + RP_LEARN_MAX_H * RPL_S_PITCH];
-  rpc_apply_block(a, sets, RplRowIdentity{}, (int)blockIdx.x, (int)blockIdx.y, (const float*)a.workspace, lds);
+  rpc_apply_block(a, sets, (int)blockIdx.x, (int)blockIdx.y, (const float*)a.workspace, lds);
 }
 
 }  // namespace

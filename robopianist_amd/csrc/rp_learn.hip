@@ -149,16 +149,11 @@ __global__ __launch_bounds__(RPL_BLOCK) void rp_learn_act_kernel(const rp_learn_
   const long long e0 = (long long)a.row_first + (long long)blockIdx.x * RPL_TILE_R;
   const long long e_end = (long long)a.row_first + a.row_count;
   f32x4 acc[RPL_ACC];
-  const float clip = a.obs_clip, nclip = -a.obs_clip;
   rpl_layer(
       [&](int r, int k) {
         const long long e = e0 + r;
         if (e >= e_end) return 0.f;
-        const float x = a.obs[(size_t)e * a.D + k];
-        const float d = x - a.mean[k];
-        const float p = d * a.inv_std[k];
-        const float lo = fmaxf(p, nclip);
-        return fminf(lo, clip);
+        return rpl_xn(a.obs, a.mean, a.inv_std, a.obs_clip, e, a.D, k);
       },
       a.D, net.w1, a.H1, sa, sw, acc);
   rpl_store_layer<true>(acc, net.b1, a.H1, sh);

@@ -55,14 +55,14 @@ __global__ __launch_bounds__(RPL_BLOCK) void rp_pop_critic_rows_kernel(rp_critic
   __shared__ __attribute__((aligned(16))) float lds[RPC_ROWS_LDS_FLOATS];
   int p, t;
   float* ws = rppc_member(a, g, p, t);
-  rpc_rows_tile(a, sets, RplRowIdentity{}, t, (int)blockIdx.y, ws, lds, (size_t)p);
+  rpc_rows_tile(a, sets, t, (int)blockIdx.y, ws, lds, (size_t)p);
 }
 
 __global__ __launch_bounds__(RPL_BLOCK) void rp_pop_critic_apply_kernel(rp_critic_step_args a, const RpcSets sets, const RppcGrid g) {
   __shared__ __attribute__((aligned(16))) float lds[RPL_TILE_R * RPL_S_PITCH + RP_LEARN_MAX_H * RPL_S_PITCH];
   int p, t;
   const float* ws = rppc_member(a, g, p, t);
-  rpc_apply_block(a, sets, RplRowIdentity{}, t, (int)blockIdx.y, ws, lds, (size_t)p);
+  rpc_apply_block(a, sets, t, (int)blockIdx.y, ws, lds, (size_t)p);
 }
 
 }  // namespace

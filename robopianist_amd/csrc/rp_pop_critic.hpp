@@ -42,7 +42,7 @@ inline rp_critic_step_args rppc_as_critic_step(const rp_pop_critic_step_args* a)
 
 inline std::string rppc_check_workspace(const rp_pop_critic_workspace_args* a) {
   const std::string fn = "rp_pop_critic_workspace";
-  const std::string err = rpc_check_sizes(fn, a->n_critics, a->H1, a->H2);
+  const std::string err = rpd_check_sizes(fn, a->n_critics, a->H1, a->H2, 1);
   if (!err.empty()) return err;
   if (a->row_count < 0) return fn + ": row_count must be >= 0";
   if (a->member_count < 0) return fn + ": member_count must be >= 0";

@@ -58,7 +58,6 @@ __global__ __launch_bounds__(RPL_BLOCK) void rp_sac_target_kernel(const rp_sac_t
   const long long e0 = (long long)a.row_first + (long long)blockIdx.x * RPL_TILE_R;
   const long long e_end = (long long)a.row_first + a.row_count;
   f32x4 acc[RPL_ACC];
-  const float clip = a.obs_clip, nclip = -a.obs_clip;
 #pragma unroll 1
   for (int i = 0; i < a.n_critics; ++i) {   // (block-uniform)
     const rp_learn_mlp net = critics.net[i];
@@ -66,12 +65,7 @@ __global__ __launch_bounds__(RPL_BLOCK) void rp_sac_target_kernel(const rp_sac_t
         [&](int r, int k) {
           const long long e = e0 + r;
           if (e >= e_end) return 0.f;
-          if (k >= D) return a.action[(size_t)e * A + (k - D)];
-          const float x = a.next_obs[(size_t)e * D + k];
-          const float d = x - a.mean[k];
-          const float p = d * a.inv_std[k];
-          const float lo = fmaxf(p, nclip);
-          return fminf(lo, clip);
+          return rpl_xn_action(a.next_obs, a.action, a.mean, a.inv_std, a.obs_clip, e, D, A, k);
         },
         D + A, net.w1, a.H1, sa, sw, acc);
     rpl_store_layer<true>(acc, net.b1, a.H1, sh);

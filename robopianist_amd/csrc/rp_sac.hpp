@@ -160,16 +160,11 @@ __device__ __forceinline__ void rps_act_tile(const rp_sac_act_args& a, const Rps
   const rp_learn_mlp net = actor.net;
   const int A = a.A, N3 = 2 * a.A;
   f32x4 acc[RPL_ACC];
-  const float clip = a.obs_clip, nclip = -a.obs_clip;
   rpl_layer(
       [&](int r, int k) {
         const long long e = e0 + r;
         if (e >= e_end) return 0.f;
-        const float x = a.obs[(size_t)rows(e) * a.D + k];
-        const float d = x - a.mean[k];
-        const float p = d * a.inv_std[k];
-        const float lo = fmaxf(p, nclip);
-        return fminf(lo, clip);
+        return rpl_xn(a.obs, a.mean, a.inv_std, a.obs_clip, rows(e), a.D, k);
       },
       a.D, net.w1, a.H1, sa, sw, acc);
   rpl_store_layer<true>(acc, net.b1, a.H1, sh);
@@ -193,19 +188,7 @@ __device__ __forceinline__ void rps_act_tile(const rp_sac_act_args& a, const Rps
       const float sd = expf(ls);
       const float t = sd * zf;
       p = m + t;
-      const float w = -2.f * p;
-      const float aw = fabsf(w);
-      const float ex = expf(-aw);
-      const float l1 = log1pf(ex);
-      const float wp = fmaxf(w, 0.f);
-      const float sp = wp + l1;
-      const float c1 = actor.ln2 - p;
-      const float c2 = c1 - sp;
-      const float lg = 2.f * c2;
-      const float q = zf * zf;
-      const float h = -0.5f * q;
-      const float g0 = h - ls;
-      sg[r * RP_LEARN_MAX_A + u] = g0 - lg;
+      sg[r * RP_LEARN_MAX_A + u] = rpl_logp_term(p, zf, ls, actor.ln2);
     }
     const float act = tanhf(p);
     const size_t o = (size_t)e * A + u;

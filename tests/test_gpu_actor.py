@@ -305,6 +305,46 @@ def test_the_step_without_optional_pointers_is_the_step_with_them():
     assert all((with_[k] != POISON).all() for k in with_ if "grad" in k)
 
 
+@pytest.mark.parametrize("n", [1, 2])
+def test_q_min_has_the_bits_of_the_critic_steps_q_at_the_actors_action(n):
+    """The actor step and the critic step evaluate a critic through one device body, so without dropout (where the two
+    launches' Philox counters do not matter) q_min of the actor step is, bit for bit, the q that the critic step's rows
+    launch writes for the same observations, the same critics and the action the actor step wrote: q[0] with one critic,
+    the elementwise minimum of q[0] and q[1] with two.  The case: 17 rows (a full tile and a partial one), H1 = 48, H2 = 16,
+    D + A = 108, no multiple of 16."""
+    case = ac.CASES[1]
+    rows, D, H1, H2, A, _ = case
+    assert rows % 16 and rows > 16 and H1 != H2 and (D + A) % 16
+    p = ac.problem(case)
+    kw = p.twin_kw("off", n)
+    assert kw["threshold"] == 0 and kw["keep_scale"] == 1.0
+    got = _run_step(p, n, "off")
+    assert all(_same_bits(a, b) for net, before in zip(got["critics"], kw["critics"]) for a, b in zip(net, before))
+    dev = _dev()
+    d = {k: _up(kw[k]) for k in ("obs", "mask", "mean", "inv_std")}
+    action, y = _up(got["action_all"]), torch.zeros(rows, device=dev)
+    P = [[_up(a) for a in net] for net in kw["critics"]]
+    M, V, T = ([[torch.zeros_like(t) for t in net] for net in P] for _ in range(3))
+    q = torch.full((n, rows), POISON, device=dev)
+    nbytes = critic.workspace_bytes(n, H1, H2, rows)
+    ws = torch.full((max(nbytes // 4, 1),), float("nan"), device=dev)
+    sets = lambda group: [critic.set_entry(net) for net in group]
+    critic.step(d["obs"].data_ptr(), action.data_ptr(), y.data_ptr(), d["mask"].data_ptr(), d["mean"].data_ptr(),
+                d["inv_std"].data_ptr(), kw["clip"], sets(P), sets(M), sets(V), sets(T), q.data_ptr(), ws.data_ptr(), nbytes,
+                D, H1, H2, A, rows, 1e-3, 1.0, threshold=0, keep_scale=1.0, ln_eps=kw["ln_eps"], seed=kw["seed"], round_=ac.ROUND,
+                launches=critic.ROWS_ONLY, hip_stream=_stream())
+    torch.cuda.synchronize()
+    assert all(_same_bits(t.cpu().numpy(), a) for net, before in zip(P, kw["critics"]) for t, a in zip(net, before))
+    q = q.cpu().numpy()
+    assert (q != POISON).all() and np.isfinite(q).all()
+    want = q[0] if n == 1 else np.minimum(q[0], q[1])
+    if n == 2:
+        assert (q[0] < q[1]).any() and (q[1] < q[0]).any()          # each critic is the selected one on some row
+    print(f"actor step {case} critics {n}: q_min against the critic step's q at the actor's action: "
+          f"{int((got['q_min_all'].view(np.uint32) != want.view(np.uint32)).sum())} of {rows} rows differ in bits")
+    assert _same_bits(got["q_min_all"], want)
+
+
 # ---- the learner ---------------------------------------------------------------------------------------------------------
 def _learner_bits(d):
     torch.cuda.synchronize()
