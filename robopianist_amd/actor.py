@@ -11,13 +11,9 @@ Like the engine, the library has no CPU fallback: a missing library is an error.
 from __future__ import annotations
 
 import ctypes
-import os
 
 from robopianist_amd import _abi, critic, offpolicy
 from robopianist_amd.learning import LearnError
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("RP_ACTOR_LIB") or os.path.join(_HERE, "csrc", "librp_actor.so")
 
 EXPORTED_SYMBOLS = ("rp_actor_step", "rp_actor_workspace", "rp_actor_dim", "rp_actor_last_error")
 
@@ -28,8 +24,6 @@ LAUNCHES = 2
 STEP, ROWS_ONLY, APPLY_ONLY = 0, 1, 2   # `launches`: a step, or one of its two launches alone (for measurement)
 PARAMS = ("w1", "b1", "w2", "b2", "w3", "b3")   # the order of rp_actor_set
 STATS = ("actor_loss", "alpha_loss", "alpha", "entropy", "masked")   # the order of `stats`
-
-_lib = None
 
 _p, _i, _u32, _f, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_float, ctypes.c_size_t
 
@@ -63,22 +57,10 @@ class WorkspaceArgs(ctypes.Structure):
 _ARGS = {"step": StepArgs, "workspace": WorkspaceArgs}
 
 
-def load_library(path: str = LIB_PATH):
-    """Loads librp_actor.so; raises LearnError if it has not been built."""
-    global _lib
-    if _lib is None:
-        _lib = declare(_abi.open_library(path, "DroQ actor step", LearnError))
-    return _lib
-
-
-_entries = _abi.EntryTable("rp_actor_", _ARGS, LearnError, load_library)
-make_args, call_raw, last_error, dim, _call = (_entries.make_args, _entries.call_raw, _entries.last_error, _entries.dim,
-                                               _entries.call)
-
-
-def declare(L, prefix: str = "rp_actor_"):
-    """Declares the ABI's prototypes on a loaded library whose symbols start with `prefix`."""
-    return _entries.declare(L, prefix)
+_entries = _abi.EntryTable("rp_actor_", _ARGS, LearnError, "RP_ACTOR_LIB", "librp_actor.so", "DroQ actor step")
+LIB_PATH = _entries.path
+load_library, declare, make_args, call_raw, last_error, dim, _call = (
+    _entries.load, _entries.declare, _entries.make_args, _entries.call_raw, _entries.last_error, _entries.dim, _entries.call)
 
 
 def set_entry(tensors=None):

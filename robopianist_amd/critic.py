@@ -10,13 +10,9 @@ from __future__ import annotations
 
 import ctypes
 import math
-import os
 
 from robopianist_amd import _abi, offpolicy
 from robopianist_amd.learning import LearnError
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("RP_CRITIC_LIB") or os.path.join(_HERE, "csrc", "librp_critic.so")
 
 EXPORTED_SYMBOLS = ("rp_critic_step", "rp_critic_workspace", "rp_critic_dim", "rp_critic_last_error")
 
@@ -24,8 +20,6 @@ MAX_CRITICS = offpolicy.MAX_CRITICS
 COUNTER = 48   # the last Philox counter word of critic i, layer L is COUNTER + 2 i + L
 STEP, ROWS_ONLY, APPLY_ONLY = 0, 1, 2   # `launches`: a step, or one of its two launches alone (for measurement)
 PARAMS = ("w1", "b1", "w2", "b2", "w3", "b3", "g1", "be1", "g2", "be2")   # the order of rp_critic_set (droq.critic_entry's)
-
-_lib = None
 
 _p, _i, _u32, _f, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_float, ctypes.c_size_t
 
@@ -58,22 +52,10 @@ class WorkspaceArgs(ctypes.Structure):
 _ARGS = {"step": StepArgs, "workspace": WorkspaceArgs}
 
 
-def load_library(path: str = LIB_PATH):
-    """Loads librp_critic.so; raises LearnError if it has not been built."""
-    global _lib
-    if _lib is None:
-        _lib = declare(_abi.open_library(path, "DroQ critic step", LearnError))
-    return _lib
-
-
-_entries = _abi.EntryTable("rp_critic_", _ARGS, LearnError, load_library)
-make_args, call_raw, last_error, dim, _call = (_entries.make_args, _entries.call_raw, _entries.last_error, _entries.dim,
-                                               _entries.call)
-
-
-def declare(L, prefix: str = "rp_critic_"):
-    """Declares the ABI's prototypes on a loaded library whose symbols start with `prefix`."""
-    return _entries.declare(L, prefix)
+_entries = _abi.EntryTable("rp_critic_", _ARGS, LearnError, "RP_CRITIC_LIB", "librp_critic.so", "DroQ critic step")
+LIB_PATH = _entries.path
+load_library, declare, make_args, call_raw, last_error, dim, _call = (
+    _entries.load, _entries.declare, _entries.make_args, _entries.call_raw, _entries.last_error, _entries.dim, _entries.call)
 
 
 def set_entry(tensors):

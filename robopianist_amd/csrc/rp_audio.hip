@@ -11,22 +11,10 @@
 //                          chunk simply takes more rounds.  Rows are written coalesced.
 //   rp_audio_pcm_kernel    one workgroup per env: max |wave| of the row (wave shuffles, then LDS), then the int16 row.
 //                          No float atomics.
-#include <hip/hip_runtime.h>
-
-#include <string>
-
+#include "rp_abi_host.hpp"
 #include "rp_audio.hpp"
 
 namespace {
-
-thread_local std::string g_err;
-int fail(const std::string& s) { g_err = s; return -1; }
-#define HIP_OK(x)                                                                  \
-  do {                                                                             \
-    hipError_t e_ = (x);                                                           \
-    if (e_ != hipSuccess)                                                          \
-      return fail(std::string(#x) + ": " + hipGetErrorString(e_));                 \
-  } while (0)
 
 #define RPA_PCM_THREADS 256
 
@@ -165,32 +153,24 @@ int rp_audio_create(const void* blob, size_t bytes, int n_envs, int max_substeps
   const std::string err = a->tab.parse(blob, bytes);
   if (!err.empty()) { delete a; return fail("rp_audio_create: " + err); }
   a->n_envs = n_envs; a->max_substeps = max_substeps; a->max_notes = max_notes; a->device = device;
-  auto bail = [&](hipError_t e, const char* what) {
-    const std::string msg = std::string("rp_audio_create: ") + what + ": " + hipGetErrorString(e);
-    rp_audio_destroy(a);
-    return fail(msg);
-  };
-  hipError_t e;
-  if ((e = hipSetDevice(device)) != hipSuccess) return bail(e, "hipSetDevice");
-  const size_t nb = sizeof(RpaPartial) * a->tab.part.size();
-  if ((e = hipMalloc(&a->d_part, nb)) != hipSuccess) return bail(e, "hipMalloc");
-  if ((e = hipMemcpy(a->d_part, a->tab.part.data(), nb, hipMemcpyHostToDevice)) != hipSuccess) return bail(e, "hipMemcpy");
+  CreateGuard<rp_audio> guard{a, rp_audio_destroy};
+  HIP_OK_AS("rp_audio_create", "hipSetDevice", hipSetDevice(device));
+  if (upload("rp_audio_create", &a->d_part, a->tab.part.data(), a->tab.part.size())) return -1;
   a->M = a->tab.view(a->d_part);
-  *out = a;
+  *out = guard.release();
   return 0;
 }
 
 void rp_audio_destroy(rp_audio* a) {
   if (!a) return;
   (void)hipSetDevice(a->device);
-  if (a->d_part) (void)hipFree(a->d_part);
+  free_all({a->d_part});
   delete a;
 }
 
 int rp_audio_notes_from_trace(rp_audio* a, const rp_audio_notes_args* args) {
-  if (!a) return fail("rp_audio_notes_from_trace: handle is NULL");
-  const std::string err = rpa_check_notes_args(args, a->n_envs, a->max_substeps);
-  if (!err.empty()) return fail(err);
+  RP_HANDLE_HEAD(a, "rp_audio_notes_from_trace: handle is NULL");
+  RP_ARGS_CHECK(rpa_check_notes_args(args, a->n_envs, a->max_substeps));
   HIP_OK(hipSetDevice(a->device));
   const rp_audio_notes& n = args->notes;
   hipLaunchKernelGGL(rp_audio_notes_kernel, dim3((unsigned)args->env_count), dim3(RPA_THREADS), 0,
@@ -201,9 +181,8 @@ int rp_audio_notes_from_trace(rp_audio* a, const rp_audio_notes_args* args) {
 }
 
 int rp_audio_synthesize(rp_audio* a, const rp_audio_synth_args* args) {
-  if (!a) return fail("rp_audio_synthesize: handle is NULL");
-  const std::string err = rpa_check_synth_args(args, a->n_envs, a->max_substeps, a->tab.sr);
-  if (!err.empty()) return fail(err);
+  RP_HANDLE_HEAD(a, "rp_audio_synthesize: handle is NULL");
+  RP_ARGS_CHECK(rpa_check_synth_args(args, a->n_envs, a->max_substeps, a->tab.sr));
   HIP_OK(hipSetDevice(a->device));
   hipStream_t st = (hipStream_t)args->hip_stream;
   const rp_audio_notes& n = args->notes;

@@ -14,22 +14,10 @@
 //                            tables go through LDS RPH_TILE_K samples at a time, the next stage's loads in flight under the
 //                            current stage's MFMAs; rows past the env window and bins past B are loaded as zeros and
 //                            never stored.
-#include <hip/hip_runtime.h>
-
-#include <string>
-
+#include "rp_abi_host.hpp"
 #include "rp_hear.hpp"
 
 namespace {
-
-thread_local std::string g_err;
-int fail(const std::string& s) { g_err = s; return -1; }
-#define HIP_OK(x)                                                                  \
-  do {                                                                             \
-    hipError_t e_ = (x);                                                           \
-    if (e_ != hipSuccess)                                                          \
-      return fail(std::string(#x) + ": " + hipGetErrorString(e_));                 \
-  } while (0)
 
 #define RPH_ANALYSIS_THREADS 256
 
@@ -213,41 +201,27 @@ int rp_hear_create(const void* audio_blob, size_t audio_bytes, const void* analy
   if (err.empty()) err = h->ana.parse(analysis_blob, analysis_bytes);
   if (!err.empty()) { delete h; return fail("rp_hear_create: " + err); }
   h->n_envs = n_envs; h->max_substeps = max_substeps_per_call; h->device = device;
-  auto bail = [&](hipError_t e, const char* what) {
-    const std::string msg = std::string("rp_hear_create: ") + what + ": " + hipGetErrorString(e);
-    rp_hear_destroy(h);
-    return fail(msg);
-  };
-  hipError_t e;
-  if ((e = hipSetDevice(device)) != hipSuccess) return bail(e, "hipSetDevice");
-  const size_t nb = sizeof(RpaPartial) * h->tab.part.size();
-  const size_t nt = sizeof(float) * h->ana.C.size();
-  if ((e = hipMalloc(&h->d_part, nb)) != hipSuccess) return bail(e, "hipMalloc");
-  if ((e = hipMalloc(&h->d_C, nt)) != hipSuccess) return bail(e, "hipMalloc");
-  if ((e = hipMalloc(&h->d_S, nt)) != hipSuccess) return bail(e, "hipMalloc");
-  if ((e = hipMalloc(&h->d_window, sizeof(float) * (size_t)n_envs * h->ana.W)) != hipSuccess) return bail(e, "hipMalloc");
-  if ((e = hipMemcpy(h->d_part, h->tab.part.data(), nb, hipMemcpyHostToDevice)) != hipSuccess) return bail(e, "hipMemcpy");
-  if ((e = hipMemcpy(h->d_C, h->ana.C.data(), nt, hipMemcpyHostToDevice)) != hipSuccess) return bail(e, "hipMemcpy");
-  if ((e = hipMemcpy(h->d_S, h->ana.S.data(), nt, hipMemcpyHostToDevice)) != hipSuccess) return bail(e, "hipMemcpy");
+  CreateGuard<rp_hear> guard{h, rp_hear_destroy};
+  HIP_OK_AS("rp_hear_create", "hipSetDevice", hipSetDevice(device));
+  if (upload("rp_hear_create", &h->d_part, h->tab.part.data(), h->tab.part.size())) return -1;
+  if (upload("rp_hear_create", &h->d_C, h->ana.C.data(), h->ana.C.size())) return -1;
+  if (upload("rp_hear_create", &h->d_S, h->ana.S.data(), h->ana.S.size())) return -1;
+  HIP_OK_AS("rp_hear_create", "hipMalloc", hipMalloc(&h->d_window, sizeof(float) * (size_t)n_envs * h->ana.W));
   h->M = h->tab.view(h->d_part);
-  *out = h;
+  *out = guard.release();
   return 0;
 }
 
 void rp_hear_destroy(rp_hear* h) {
   if (!h) return;
   (void)hipSetDevice(h->device);
-  if (h->d_part) (void)hipFree(h->d_part);
-  if (h->d_C) (void)hipFree(h->d_C);
-  if (h->d_S) (void)hipFree(h->d_S);
-  if (h->d_window) (void)hipFree(h->d_window);
+  free_all({h->d_part, h->d_C, h->d_S, h->d_window});
   delete h;
 }
 
 int rp_hear_track(rp_hear* h, const rp_hear_track_args* args) {
-  if (!h) return fail("rp_hear_track: handle is NULL");
-  const std::string err = rph_check_track_args(args, h->n_envs, h->max_substeps);
-  if (!err.empty()) return fail(err);
+  RP_HANDLE_HEAD(h, "rp_hear_track: handle is NULL");
+  RP_ARGS_CHECK(rph_check_track_args(args, h->n_envs, h->max_substeps));
   HIP_OK(hipSetDevice(h->device));
   hipLaunchKernelGGL(rp_hear_track_kernel, dim3((unsigned)args->env_count), dim3(RPA_THREADS), 0,
                      (hipStream_t)args->hip_stream, h->M.rel_tail, args->trace, args->n_sub, args->pedal, args->restart,
@@ -257,9 +231,8 @@ int rp_hear_track(rp_hear* h, const rp_hear_track_args* args) {
 }
 
 int rp_hear_spectrum(rp_hear* h, const rp_hear_spectrum_args* args) {
-  if (!h) return fail("rp_hear_spectrum: handle is NULL");
-  const std::string err = rph_check_spectrum_args(args, h->n_envs);
-  if (!err.empty()) return fail(err);
+  RP_HANDLE_HEAD(h, "rp_hear_spectrum: handle is NULL");
+  RP_ARGS_CHECK(rph_check_spectrum_args(args, h->n_envs));
   HIP_OK(hipSetDevice(h->device));
   hipStream_t st = (hipStream_t)args->hip_stream;
   const int W = h->ana.W, B = h->ana.B;

@@ -5,22 +5,10 @@
 //                    a body in the tree walk, a dof column in the Jacobian and the update, a row in the 15 x 15
 //                    Cholesky solve and an actuator in the transmission (rp_ik.hpp: rpik_solve_env).  The hand's
 //                    frames, J, A and its factor sit in LDS; the K iterations run inside the launch.
-#include <hip/hip_runtime.h>
-
-#include <string>
-
+#include "rp_abi_host.hpp"
 #include "rp_ik.hpp"
 
 namespace {
-
-thread_local std::string g_err;
-int fail(const std::string& s) { g_err = s; return -1; }
-#define HIP_OK(x)                                                                  \
-  do {                                                                             \
-    hipError_t e_ = (x);                                                           \
-    if (e_ != hipSuccess)                                                          \
-      return fail(std::string(#x) + ": " + hipGetErrorString(e_));                 \
-  } while (0)
 
 #define RPIK_BLOCK (RPIK_MAX_HANDS * RPIK_LANES)   // 64: one wave
 
@@ -59,30 +47,23 @@ int rp_ik_create(const void* blob, size_t bytes, int n_envs, int device, int pre
   const std::string err = rpik_parse(blob, bytes, r->M);
   if (!err.empty()) { delete r; return fail("rp_ik_create: " + err); }
   r->n_envs = n_envs; r->device = device; r->precision = precision;
-  auto bail = [&](hipError_t e, const char* what) {
-    const std::string msg = std::string("rp_ik_create: ") + what + ": " + hipGetErrorString(e);
-    rp_ik_destroy(r);
-    return fail(msg);
-  };
-  hipError_t e;
-  if ((e = hipSetDevice(device)) != hipSuccess) return bail(e, "hipSetDevice");
-  if ((e = hipMalloc(&r->d_M, sizeof(RpikModel))) != hipSuccess) return bail(e, "hipMalloc");
-  if ((e = hipMemcpy(r->d_M, &r->M, sizeof(RpikModel), hipMemcpyHostToDevice)) != hipSuccess) return bail(e, "hipMemcpy");
-  *out = r;
+  CreateGuard<rp_ik> guard{r, rp_ik_destroy};
+  HIP_OK_AS("rp_ik_create", "hipSetDevice", hipSetDevice(device));
+  if (upload("rp_ik_create", &r->d_M, &r->M, 1)) return -1;
+  *out = guard.release();
   return 0;
 }
 
 void rp_ik_destroy(rp_ik* r) {
   if (!r) return;
   (void)hipSetDevice(r->device);
-  if (r->d_M) (void)hipFree(r->d_M);
+  free_all({r->d_M});
   delete r;
 }
 
 int rp_ik_solve(rp_ik* r, const rp_ik_args* a) {
-  if (!r) return fail("rp_ik_solve: solver is NULL");
-  const std::string err = rpik_check_args(a, r->n_envs, r->M);
-  if (!err.empty()) return fail(err);
+  RP_HANDLE_HEAD(r, "rp_ik_solve: solver is NULL");
+  RP_ARGS_CHECK(rpik_check_args(a, r->n_envs, r->M));
   HIP_OK(hipSetDevice(r->device));
   hipStream_t st = (hipStream_t)a->hip_stream;
   const RpikCall c = rpik_call(a, r->M);

@@ -6,22 +6,10 @@
 //                               world frame of every geom as 12 floats.
 //   rp_render_kernel            grid (ceil(H W / 256), env), thread = pixel: the workgroup stages its env's geom
 //                               frames in LDS, every thread casts its ray (rp_render.hpp: rpr_pixel).
-#include <hip/hip_runtime.h>
-
-#include <string>
-
+#include "rp_abi_host.hpp"
 #include "rp_render.hpp"
 
 namespace {
-
-thread_local std::string g_err;
-int fail(const std::string& s) { g_err = s; return -1; }
-#define HIP_OK(x)                                                                  \
-  do {                                                                             \
-    hipError_t e_ = (x);                                                           \
-    if (e_ != hipSuccess)                                                          \
-      return fail(std::string(#x) + ": " + hipGetErrorString(e_));                 \
-  } while (0)
 
 template <typename T>
 __global__ __launch_bounds__(RPR_MAX_BODIES) void rp_render_frames_kernel(
@@ -103,43 +91,30 @@ int rp_render_create(const void* blob, size_t bytes, int n_envs, int device, int
   const std::string err = r->tab.parse(blob, bytes);
   if (!err.empty()) { delete r; return fail("rp_render_create: " + err); }
   r->n_envs = n_envs; r->device = device; r->precision = precision;
-  auto bail = [&](hipError_t e, const char* what) {
-    const std::string msg = std::string("rp_render_create: ") + what + ": " + hipGetErrorString(e);
-    rp_render_destroy(r);
-    return fail(msg);
-  };
-  hipError_t e;
-  if ((e = hipSetDevice(device)) != hipSuccess) return bail(e, "hipSetDevice");
+  CreateGuard<rp_renderer> guard{r, rp_render_destroy};
+  HIP_OK_AS("rp_render_create", "hipSetDevice", hipSetDevice(device));
   const RprTables& t = r->tab;
-  // (+1: an empty table still gets a valid allocation)
-  if ((e = hipMalloc(&r->d_int, sizeof(int) * (t.I.size() + 1))) != hipSuccess) return bail(e, "hipMalloc");
-  if ((e = hipMalloc(&r->d_dbl, sizeof(double) * (t.D.size() + 1))) != hipSuccess) return bail(e, "hipMalloc");
-  if ((e = hipMalloc(&r->d_flt, sizeof(float) * (t.F.size() + 1))) != hipSuccess) return bail(e, "hipMalloc");
+  if (upload("rp_render_create", &r->d_int, t.I.data(), t.I.size())) return -1;
+  if (upload("rp_render_create", &r->d_dbl, t.D.data(), t.D.size())) return -1;
+  if (upload("rp_render_create", &r->d_flt, t.F.data(), t.F.size())) return -1;
   const size_t nfr = (size_t)n_envs * (size_t)(t.M.ngeom ? t.M.ngeom : 1) * RPR_FRAME;
-  if ((e = hipMalloc(&r->d_frames, sizeof(float) * nfr)) != hipSuccess) return bail(e, "hipMalloc (geom frames)");
-  if ((e = hipMemset(r->d_frames, 0, sizeof(float) * nfr)) != hipSuccess) return bail(e, "hipMemset");
-  if (!t.I.empty() && (e = hipMemcpy(r->d_int, t.I.data(), sizeof(int) * t.I.size(), hipMemcpyHostToDevice)) != hipSuccess) return bail(e, "hipMemcpy");
-  if (!t.D.empty() && (e = hipMemcpy(r->d_dbl, t.D.data(), sizeof(double) * t.D.size(), hipMemcpyHostToDevice)) != hipSuccess) return bail(e, "hipMemcpy");
-  if (!t.F.empty() && (e = hipMemcpy(r->d_flt, t.F.data(), sizeof(float) * t.F.size(), hipMemcpyHostToDevice)) != hipSuccess) return bail(e, "hipMemcpy");
+  HIP_OK_AS("rp_render_create", "hipMalloc (geom frames)", hipMalloc(&r->d_frames, sizeof(float) * nfr));
+  HIP_OK_AS("rp_render_create", "hipMemset", hipMemset(r->d_frames, 0, sizeof(float) * nfr));
   r->M = t.view(r->d_int, r->d_dbl, r->d_flt);
-  *out = r;
+  *out = guard.release();
   return 0;
 }
 
 void rp_render_destroy(rp_renderer* r) {
   if (!r) return;
   (void)hipSetDevice(r->device);
-  if (r->d_int) (void)hipFree(r->d_int);
-  if (r->d_dbl) (void)hipFree(r->d_dbl);
-  if (r->d_flt) (void)hipFree(r->d_flt);
-  if (r->d_frames) (void)hipFree(r->d_frames);
+  free_all({r->d_int, r->d_dbl, r->d_flt, r->d_frames});
   delete r;
 }
 
 int rp_render(rp_renderer* r, const rp_render_args* a) {
-  if (!r) return fail("rp_render: renderer is NULL");
-  const std::string err = rpr_check_args(a, r->n_envs);
-  if (!err.empty()) return fail(err);
+  RP_HANDLE_HEAD(r, "rp_render: renderer is NULL");
+  RP_ARGS_CHECK(rpr_check_args(a, r->n_envs));
   const long long npix = (long long)a->height * a->width;
   // (rpr_check_args bounds height and width by 16384: a pixel index fits an int; per-env bases are size_t)
   HIP_OK(hipSetDevice(r->device));

@@ -15,22 +15,10 @@
 //                               segment's place; writes the header and `length`.
 //   rp_video_entropy_kernel<1>  the same walk again, now writing the stuffed bytes and the segment's marker in place.
 // Every store into `bytes` is checked against bytes_cap.
-#include <hip/hip_runtime.h>
-
-#include <string>
-
+#include "rp_abi_host.hpp"
 #include "rp_video.hpp"
 
 namespace {
-
-thread_local std::string g_err;
-int fail(const std::string& s) { g_err = s; return -1; }
-#define HIP_OK(x)                                                                  \
-  do {                                                                             \
-    hipError_t e_ = (x);                                                           \
-    if (e_ != hipSuccess)                                                          \
-      return fail(std::string(#x) + ": " + hipGetErrorString(e_));                 \
-  } while (0)
 
 #define RPV_TRANSFORM_THREADS 256
 #define RPV_LDS_PITCH 65                                            /* words per coefficient pair: 64 lanes + 1, no bank conflicts */
@@ -216,42 +204,29 @@ int rp_video_create(int height, int width, int max_frames, int quality, int devi
   const std::string err = v->tab.build(height, width, max_frames, quality);
   if (!err.empty()) { delete v; return fail("rp_video_create: " + err); }
   v->max_frames = max_frames; v->device = device;
-  auto bail = [&](hipError_t e, const char* what) {
-    const std::string msg = std::string("rp_video_create: ") + what + ": " + hipGetErrorString(e);
-    rp_video_destroy(v);
-    return fail(msg);
-  };
+  CreateGuard<rp_video> guard{v, rp_video_destroy};
   const RpvGeom& G = v->tab.G;
   const size_t n_seg = (size_t)max_frames * G.nby;
-  hipError_t e;
-  if ((e = hipSetDevice(device)) != hipSuccess) return bail(e, "hipSetDevice");
-  if ((e = hipMalloc(&v->d_coef, n_seg * G.seg_blocks * 32 * sizeof(uint32_t))) != hipSuccess) return bail(e, "hipMalloc");
-  if ((e = hipMalloc(&v->d_seg_len, n_seg * sizeof(int))) != hipSuccess) return bail(e, "hipMalloc");
-  if ((e = hipMalloc(&v->d_seg_off, n_seg * sizeof(int))) != hipSuccess) return bail(e, "hipMalloc");
-  if ((e = hipMalloc(&v->d_huff, sizeof(RpvHuff))) != hipSuccess) return bail(e, "hipMalloc");
-  if ((e = hipMalloc(&v->d_header, v->tab.header.size())) != hipSuccess) return bail(e, "hipMalloc");
-  if ((e = hipMemcpy(v->d_huff, &v->tab.huff, sizeof(RpvHuff), hipMemcpyHostToDevice)) != hipSuccess) return bail(e, "hipMemcpy");
-  if ((e = hipMemcpy(v->d_header, v->tab.header.data(), v->tab.header.size(), hipMemcpyHostToDevice)) != hipSuccess)
-    return bail(e, "hipMemcpy");
-  *out = v;
+  HIP_OK_AS("rp_video_create", "hipSetDevice", hipSetDevice(device));
+  HIP_OK_AS("rp_video_create", "hipMalloc", hipMalloc(&v->d_coef, n_seg * G.seg_blocks * 32 * sizeof(uint32_t)));
+  HIP_OK_AS("rp_video_create", "hipMalloc", hipMalloc(&v->d_seg_len, n_seg * sizeof(int)));
+  HIP_OK_AS("rp_video_create", "hipMalloc", hipMalloc(&v->d_seg_off, n_seg * sizeof(int)));
+  if (upload("rp_video_create", &v->d_huff, &v->tab.huff, 1)) return -1;
+  if (upload("rp_video_create", &v->d_header, v->tab.header.data(), v->tab.header.size())) return -1;
+  *out = guard.release();
   return 0;
 }
 
 void rp_video_destroy(rp_video* v) {
   if (!v) return;
   (void)hipSetDevice(v->device);
-  if (v->d_coef) (void)hipFree(v->d_coef);
-  if (v->d_seg_len) (void)hipFree(v->d_seg_len);
-  if (v->d_seg_off) (void)hipFree(v->d_seg_off);
-  if (v->d_huff) (void)hipFree(v->d_huff);
-  if (v->d_header) (void)hipFree(v->d_header);
+  free_all({v->d_coef, v->d_seg_len, v->d_seg_off, v->d_huff, v->d_header});
   delete v;
 }
 
 int rp_video_encode(rp_video* v, const rp_video_encode_args* args) {
-  if (!v) return fail("rp_video_encode: handle is NULL");
-  const std::string err = rpv_check_args(args, v->max_frames);
-  if (!err.empty()) return fail(err);
+  RP_HANDLE_HEAD(v, "rp_video_encode: handle is NULL");
+  RP_ARGS_CHECK(rpv_check_args(args, v->max_frames));
   HIP_OK(hipSetDevice(v->device));
   hipStream_t st = (hipStream_t)args->hip_stream;
   const RpvGeom& G = v->tab.G;

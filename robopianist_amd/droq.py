@@ -16,21 +16,15 @@ number of learners is `DroQCore`, which
 from __future__ import annotations
 
 import ctypes
-import os
 
 from robopianist_amd import _abi, actor, critic, offpolicy
 from robopianist_amd.learning import LearnError, Mlp, _train_and_evaluate
 from robopianist_amd.offpolicy import SAC, _masked_mean, actor_loss, alpha_loss, critic_loss, squashed_gaussian
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("RP_DROQ_LIB") or os.path.join(_HERE, "csrc", "librp_droq.so")
-
 EXPORTED_SYMBOLS = ("rp_droq_target", "rp_droq_dim", "rp_droq_last_error")
 
 MAX_CRITICS = offpolicy.MAX_CRITICS
 COUNTER = 32   # the last Philox counter word of critic i, layer L is COUNTER + 2 i + L
-
-_lib = None
 
 _p, _i, _u32, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_float
 
@@ -52,22 +46,10 @@ class TargetArgs(ctypes.Structure):
 _ARGS = {"target": TargetArgs}
 
 
-def load_library(path: str = LIB_PATH):
-    """Loads librp_droq.so; raises LearnError if it has not been built."""
-    global _lib
-    if _lib is None:
-        _lib = declare(_abi.open_library(path, "DroQ target", LearnError))
-    return _lib
-
-
-_entries = _abi.EntryTable("rp_droq_", _ARGS, LearnError, load_library)
-make_args, call_raw, last_error, dim, _call = (_entries.make_args, _entries.call_raw, _entries.last_error, _entries.dim,
-                                               _entries.call)
-
-
-def declare(L, prefix: str = "rp_droq_"):
-    """Declares the ABI's prototypes on a loaded library whose symbols start with `prefix`."""
-    return _entries.declare(L, prefix)
+_entries = _abi.EntryTable("rp_droq_", _ARGS, LearnError, "RP_DROQ_LIB", "librp_droq.so", "DroQ target")
+LIB_PATH = _entries.path
+load_library, declare, make_args, call_raw, last_error, dim, _call = (
+    _entries.load, _entries.declare, _entries.make_args, _entries.call_raw, _entries.last_error, _entries.dim, _entries.call)
 
 
 def drop_threshold(p: float) -> int:

@@ -12,20 +12,14 @@ error.
 from __future__ import annotations
 
 import ctypes
-import os
 
 from robopianist_amd import _abi
 from robopianist_amd.learning import LearnError
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("RP_EVOLVE_LIB") or os.path.join(_HERE, "csrc", "librp_evolve.so")
 
 EXPORTED_SYMBOLS = ("rp_evolve_fold", "rp_evolve_plan", "rp_evolve_copy", "rp_evolve_dim", "rp_evolve_last_error")
 
 MAX_MEMBERS, MAX_COPY_MEMBERS, MAX_FIELDS, CHUNK_WORDS = 256, 65535, 64, 4096
 COUNTER = 96   # the last Philox counter word of the plan's draw
-
-_lib = None
 
 _p, _i, _u32, _f, _d, _ll = (ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_float, ctypes.c_double,
                              ctypes.c_longlong)
@@ -56,22 +50,10 @@ class CopyArgs(ctypes.Structure):
 _ARGS = {"fold": FoldArgs, "plan": PlanArgs, "copy": CopyArgs}
 
 
-def load_library(path: str = LIB_PATH):
-    """Loads librp_evolve.so; raises LearnError if it has not been built."""
-    global _lib
-    if _lib is None:
-        _lib = declare(_abi.open_library(path, "population-based training", LearnError))
-    return _lib
-
-
-_entries = _abi.EntryTable("rp_evolve_", _ARGS, LearnError, load_library)
-make_args, call_raw, last_error, dim, _call = (_entries.make_args, _entries.call_raw, _entries.last_error, _entries.dim,
-                                               _entries.call)
-
-
-def declare(L, prefix: str = "rp_evolve_"):
-    """Declares the ABI's prototypes on a loaded library whose symbols start with `prefix`."""
-    return _entries.declare(L, prefix)
+_entries = _abi.EntryTable("rp_evolve_", _ARGS, LearnError, "RP_EVOLVE_LIB", "librp_evolve.so", "population-based training")
+LIB_PATH = _entries.path
+load_library, declare, make_args, call_raw, last_error, dim, _call = (
+    _entries.load, _entries.declare, _entries.make_args, _entries.call_raw, _entries.last_error, _entries.dim, _entries.call)
 
 
 def field_table(fields):

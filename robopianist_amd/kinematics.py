@@ -10,22 +10,16 @@ fallback: a missing library is an error.
 from __future__ import annotations
 
 import ctypes
-import os
 
 import numpy as np
 
 from robopianist_amd import _abi
 from robopianist_amd.model import ik_tables
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("RP_IK_LIB") or os.path.join(_HERE, "csrc", "librp_ik.so")
-
 EXPORTED_SYMBOLS = ("rp_ik_create", "rp_ik_destroy", "rp_ik_solve", "rp_ik_dim", "rp_ik_last_error")
 
 DEFAULT_DAMPING = 0.03
 DEFAULT_MAX_STEP = 0.02
-
-_lib = None
 
 
 class IKError(RuntimeError):
@@ -58,66 +52,32 @@ def make_args(env_first, env_count, qpos=None, tree_offset=None, target=None, we
               damping=DEFAULT_DAMPING, max_step=DEFAULT_MAX_STEP, iterations=1, out=None, out_stride=0, q_target=None,
               residual=None, tips=None, hip_stream=None) -> IKArgs:
     """Fills an rp_ik_args; the array arguments are raw addresses (or None)."""
-    a = IKArgs()
-    a.struct_size = ctypes.sizeof(IKArgs)
-    a.qpos, a.tree_offset, a.target, a.weight, a.dof_weight = qpos, tree_offset, target, weight, dof_weight
-    a.delta, a.iterations = int(bool(delta)), int(iterations)
-    a.damping, a.max_step = float(damping), float(max_step)
-    a.out, a.out_stride = out, int(out_stride)
-    a.q_target, a.residual, a.tips = q_target, residual, tips
-    a.env_first, a.env_count = int(env_first), int(env_count)
-    a.hip_stream = hip_stream
-    return a
+    return _abi.fill(IKArgs, qpos=qpos, tree_offset=tree_offset, target=target, weight=weight, dof_weight=dof_weight,
+                     delta=int(bool(delta)), iterations=int(iterations), damping=float(damping), max_step=float(max_step),
+                     out=out, out_stride=int(out_stride), q_target=q_target, residual=residual, tips=tips,
+                     env_first=int(env_first), env_count=int(env_count), hip_stream=hip_stream)
 
 
-def declare(L, prefix: str = "rp_ik_"):
-    """Declares the ABI's prototypes on a loaded library whose symbols start with `prefix`."""
-    f = lambda name: getattr(L, prefix + name)
-    f("last_error").restype = ctypes.c_char_p
-    f("create").argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                            ctypes.POINTER(ctypes.c_void_p)]
-    f("destroy").argtypes = [ctypes.c_void_p]
-    f("destroy").restype = None
-    f("solve").argtypes = [ctypes.c_void_p, ctypes.POINTER(IKArgs)]
-    f("dim").argtypes = [ctypes.c_void_p, ctypes.c_char_p]
-    return L
+_table = _abi.HandleTable("rp_ik_", {"solve": IKArgs}, IKError, "RP_IK_LIB", "librp_ik.so", "inverse-kinematics",
+                          create=[ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.c_int])
+LIB_PATH = _table.path
+load_library, declare = _table.load, _table.declare
 
 
-def load_library(path: str = LIB_PATH):
-    """Loads librp_ik.so; raises IKError if it has not been built."""
-    global _lib
-    if _lib is None:
-        _lib = declare(_abi.open_library(path, "inverse-kinematics", IKError))
-    return _lib
-
-
-class FingertipIK:
+class FingertipIK(_abi.Owner):
     """Batched fingertip IK of one compiled scene (`scene_info`: model/scene.py SceneInfo)."""
 
     def __init__(self, scene_info, n_envs: int, device_id: int = 0, precision: int = 64):
-        self._L = load_library()
         self.model = scene_info.model
         self.n_envs, self.device_id, self.precision = int(n_envs), int(device_id), int(precision)
         self.tables = ik_tables.build_ik_tables(scene_info)
         self.blob = ik_tables.make_ik_blob(scene_info, tables=self.tables)
-        self._h = ctypes.c_void_p()
-        rc = self._L.rp_ik_create(self.blob, len(self.blob), self.n_envs, self.device_id, self.precision,
-                                  ctypes.byref(self._h))
-        if rc != 0:
-            raise IKError(self._L.rp_ik_last_error().decode())
-        dim = lambda name: self._L.rp_ik_dim(self._h, name)
-        self.n_hands, self.n_tips, self.n_act, self.n_dof = dim(b"n_hands"), dim(b"n_tips"), dim(b"n_act"), dim(b"n_dof")
-        self.ntree = dim(b"ntree")
+        self._handle = _abi.Handle(_table, self.blob, len(self.blob), self.n_envs, self.device_id, self.precision)
+        dim = self._handle.dim
+        self.n_hands, self.n_tips, self.n_act, self.n_dof = dim("n_hands"), dim("n_tips"), dim("n_act"), dim("n_dof")
+        self.ntree = dim("ntree")
         self._out = {}
         self._keep = None
-
-    def __del__(self):
-        try:
-            if self._h:
-                self._L.rp_ik_destroy(self._h)
-                self._h = ctypes.c_void_p()
-        except Exception:
-            pass
 
     # -- cached tensors ----------------------------------------------------------------------------------------------
     def _cached(self, name, shape, dtype):
@@ -142,10 +102,7 @@ class FingertipIK:
 
     def solve_raw(self, args: IKArgs) -> int:
         """rp_ik_solve with a caller-made argument block; returns the C return code (see last_error())."""
-        return self._L.rp_ik_solve(self._h, ctypes.byref(args))
-
-    def last_error(self) -> str:
-        return self._L.rp_ik_last_error().decode()
+        return self._handle.call_raw("solve", args)
 
     def _device_f64(self, x, shape, what, nonnegative=False):
         """`x` as a contiguous float64 device tensor of `shape`.  Host data (numpy, lists, CPU tensors) is checked and
@@ -200,15 +157,14 @@ class FingertipIK:
         elif (not out.is_cuda or out.dtype != self.dtype or out.dim() != 2 or out.shape[0] != E or out.shape[1] < self.n_act
               or out.stride(1) != 1 or out.stride(0) < out.shape[1]):
             raise IKError(f"solve: out must be a device tensor [{E}, >= {self.n_act}] of {self.dtype} with contiguous rows")
-        a = make_args(env_first, E - env_first if env_count is None else env_count, qpos=qpos.data_ptr(),
-                      tree_offset=tree_offset.data_ptr() if tree_offset is not None else None,
-                      target=targets.data_ptr(), weight=weights.data_ptr() if weights is not None else None,
-                      dof_weight=dw.ctypes.data if dw is not None else None, delta=delta, damping=damping,
-                      max_step=max_step, iterations=iterations, out=out.data_ptr(), out_stride=out.stride(0),
-                      q_target=o_q.data_ptr() if want_q else None, residual=o_res.data_ptr() if want_residual else None,
-                      tips=o_tips.data_ptr() if want_tips else None, hip_stream=hip_stream)
-        if self._L.rp_ik_solve(self._h, ctypes.byref(a)) != 0:
-            raise IKError(self.last_error())
+        self._handle.call("solve", make_args(
+            env_first, E - env_first if env_count is None else env_count, qpos=qpos.data_ptr(),
+            tree_offset=tree_offset.data_ptr() if tree_offset is not None else None,
+            target=targets.data_ptr(), weight=weights.data_ptr() if weights is not None else None,
+            dof_weight=dw.ctypes.data if dw is not None else None, delta=delta, damping=damping,
+            max_step=max_step, iterations=iterations, out=out.data_ptr(), out_stride=out.stride(0),
+            q_target=o_q.data_ptr() if want_q else None, residual=o_res.data_ptr() if want_residual else None,
+            tips=o_tips.data_ptr() if want_tips else None, hip_stream=hip_stream))
         self._keep = (targets, weights)   # alive until the kernel has run
         extra = [t for t, want in ((o_q, want_q), (o_res, want_residual), (o_tips, want_tips)) if want]
         return (out, *extra) if extra else out

@@ -13,14 +13,10 @@ from __future__ import annotations
 import copy
 import ctypes
 import math
-import os
 
 import numpy as np
 
 from robopianist_amd import _abi
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("RP_LEARN_LIB") or os.path.join(_HERE, "csrc", "librp_learn.so")
 
 EXPORTED_SYMBOLS = ("rp_learn_pack", "rp_learn_act", "rp_learn_gae", "rp_learn_moments", "rp_learn_dim",
                     "rp_learn_last_error")
@@ -30,8 +26,6 @@ MAX_HIDDEN = 256
 MAX_ACTIONS = 128
 F32, F64 = 0, 1
 STEP_FIRST, STEP_MID, STEP_LAST = 0, 1, 2
-
-_lib = None
 
 
 class LearnError(RuntimeError):
@@ -82,22 +76,10 @@ class MomentsArgs(ctypes.Structure):
 _ARGS = {"pack": PackArgs, "act": ActArgs, "gae": GaeArgs, "moments": MomentsArgs}
 
 
-def load_library(path: str = LIB_PATH):
-    """Loads librp_learn.so; raises LearnError if it has not been built."""
-    global _lib
-    if _lib is None:
-        _lib = declare(_abi.open_library(path, "learner", LearnError))
-    return _lib
-
-
-_entries = _abi.EntryTable("rp_learn_", _ARGS, LearnError, load_library)
-make_args, call_raw, last_error, dim, _call = (_entries.make_args, _entries.call_raw, _entries.last_error, _entries.dim,
-                                               _entries.call)
-
-
-def declare(L, prefix: str = "rp_learn_"):
-    """Declares the ABI's prototypes on a loaded library whose symbols start with `prefix`."""
-    return _entries.declare(L, prefix)
+_entries = _abi.EntryTable("rp_learn_", _ARGS, LearnError, "RP_LEARN_LIB", "librp_learn.so", "learner")
+LIB_PATH = _entries.path
+load_library, declare, make_args, call_raw, last_error, dim, _call = (
+    _entries.load, _entries.declare, _entries.make_args, _entries.call_raw, _entries.last_error, _entries.dim, _entries.call)
 
 
 def field_table(fields):

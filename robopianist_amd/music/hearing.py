@@ -12,7 +12,6 @@ from __future__ import annotations
 
 import ctypes
 import math
-import os
 import struct
 from typing import Optional, Tuple
 
@@ -22,9 +21,6 @@ from robopianist_amd import _abi
 from robopianist_amd.music import constants as consts
 from robopianist_amd.music import synthesizer
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("RP_HEAR_LIB") or os.path.join(os.path.dirname(_HERE), "csrc", "librp_hear.so")
-
 EXPORTED_SYMBOLS = ("rp_hear_create", "rp_hear_destroy", "rp_hear_track", "rp_hear_spectrum", "rp_hear_dim",
                     "rp_hear_last_error")
 
@@ -33,8 +29,6 @@ N_SLOTS = 2              # notes kept per key: the newest and the one before
 N_STATE = 8              # state words per env (rp_hear.h)
 MIN_WINDOW, MAX_WINDOW, MAX_BINS = 64, 4096, 128
 _BLOB_MAGIC, _BLOB_VERSION = 0x41485052, 1
-
-_lib = None
 
 
 class HearingError(RuntimeError):
@@ -122,31 +116,15 @@ class SpectrumArgs(ctypes.Structure):
     ]
 
 
-def declare(L, prefix: str = "rp_hear_"):
-    """argtypes of the C ABI on a loaded library (the host build of the tests exports the same calls)."""
-    getattr(L, prefix + "last_error").restype = ctypes.c_char_p
-    getattr(L, prefix + "create").argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_size_t,
-                                              ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]
-    getattr(L, prefix + "destroy").argtypes = [ctypes.c_void_p]
-    getattr(L, prefix + "destroy").restype = None
-    getattr(L, prefix + "track").argtypes = [ctypes.c_void_p, ctypes.POINTER(TrackArgs)]
-    getattr(L, prefix + "spectrum").argtypes = [ctypes.c_void_p, ctypes.POINTER(SpectrumArgs)]
-    getattr(L, prefix + "dim").argtypes = [ctypes.c_void_p, ctypes.c_char_p]
+_table = _abi.HandleTable("rp_hear_", {"track": TrackArgs, "spectrum": SpectrumArgs}, HearingError, "RP_HEAR_LIB",
+                          "librp_hear.so", "hearing",
+                          create=[ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_int,
+                                  ctypes.c_int])
+LIB_PATH = _table.path
+load_library, declare = _table.load, _table.declare
 
 
-def load_library(path: Optional[str] = None):
-    """Loads librp_hear.so; raises HearingError if it has not been built."""
-    global _lib
-    if _lib is not None and path is None:
-        return _lib
-    L = _abi.open_library(LIB_PATH if path is None else path, "hearing", HearingError)
-    declare(L)
-    if path is None:
-        _lib = L
-    return L
-
-
-class Hearing:
+class Hearing(_abi.Owner):
     """Batched audio observation.  `analysis` is a (C, S) pair of `make_analysis` (default: the 88 key fundamentals at
     `sample_rate` over `window` samples); `timbre` defaults to the synthesiser's.  The voice bank lives in device tensors
     of this object: `t_on`, `t_off` float64 [E, 88, 2] and `state` int32 [E, 8] (rp_hear.h); a new object's bank is empty."""
@@ -155,7 +133,6 @@ class Hearing:
                  timbre: Optional[dict] = None, physics_timestep: float = 0.005, max_substeps_per_call: int = 64,
                  device_id: int = 0):
         import torch
-        self._L = load_library()
         self.n_envs, self.sample_rate, self.device_id = int(n_envs), sample_rate, int(device_id)
         self.physics_timestep = float(physics_timestep)
         self.max_substeps_per_call = int(max_substeps_per_call)
@@ -164,11 +141,8 @@ class Hearing:
         self.audio_blob = synthesizer.make_audio_blob(self.timbre, sample_rate)
         self.analysis_blob = make_analysis_blob(*self.analysis)
         self.window, self.n_bins = (int(n) for n in np.asarray(self.analysis[0]).shape)
-        self._h = ctypes.c_void_p()
-        rc = self._L.rp_hear_create(self.audio_blob, len(self.audio_blob), self.analysis_blob, len(self.analysis_blob),
-                                    self.n_envs, self.max_substeps_per_call, self.device_id, ctypes.byref(self._h))
-        if rc != 0:
-            raise HearingError(self._L.rp_hear_last_error().decode())
+        self._handle = _abi.Handle(_table, self.audio_blob, len(self.audio_blob), self.analysis_blob, len(self.analysis_blob),
+                                   self.n_envs, self.max_substeps_per_call, self.device_id)
         dev = self.device = torch.device("cuda", self.device_id)
         E = self.n_envs
         self.t_on = torch.full((E, N_KEYS, N_SLOTS), -1.0, dtype=torch.float64, device=dev)
@@ -176,18 +150,7 @@ class Hearing:
         self.state = torch.zeros((E, N_STATE), dtype=torch.int32, device=dev)
         self._out = None
 
-    def __del__(self):
-        try:
-            if self._h:
-                self._L.rp_hear_destroy(self._h)
-                self._h = ctypes.c_void_p()
-        except Exception:
-            pass
-
     # -- helpers ---------------------------------------------------------------------------------------------
-    def last_error(self) -> str:
-        return self._L.rp_hear_last_error().decode()
-
     @property
     def forgotten(self):
         """[n_envs] int32 device view: the voices that were pushed out of the bank while they still sounded."""
@@ -227,35 +190,26 @@ class Hearing:
 
     # -- the two calls -----------------------------------------------------------------------------------------
     def track_args(self, trace, pedal=None, restart=None, dt=None, env_first=0, env_count=None, hip_stream=None) -> TrackArgs:
-        a = TrackArgs()
-        a.struct_size = ctypes.sizeof(TrackArgs)
-        a.trace, a.n_sub = trace.data_ptr(), int(trace.shape[1])
-        a.pedal = None if pedal is None else pedal.data_ptr()
-        a.restart = None if restart is None else restart.data_ptr()
-        a.dt = float(self.physics_timestep if dt is None else dt)
-        a.bank = self._bank()
-        a.env_first, a.env_count = self._env_window(env_first, env_count)
-        a.hip_stream = self._stream(hip_stream)
-        return a
+        first, count = self._env_window(env_first, env_count)
+        return _abi.fill(TrackArgs, trace=trace.data_ptr(), n_sub=int(trace.shape[1]),
+                         pedal=None if pedal is None else pedal.data_ptr(),
+                         restart=None if restart is None else restart.data_ptr(),
+                         dt=float(self.physics_timestep if dt is None else dt), bank=self._bank(), env_first=first,
+                         env_count=count, hip_stream=self._stream(hip_stream))
 
     def spectrum_args(self, spectrum, window=None, dt=None, env_first=0, env_count=None, hip_stream=None) -> SpectrumArgs:
-        a = SpectrumArgs()
-        a.struct_size = ctypes.sizeof(SpectrumArgs)
-        a.bank = self._bank()
-        a.dt = float(self.physics_timestep if dt is None else dt)
-        a.env_first, a.env_count = self._env_window(env_first, env_count)
-        a.window = None if window is None else window.data_ptr()
-        a.spectrum = None if spectrum is None else spectrum.data_ptr()
-        a.hip_stream = self._stream(hip_stream)
-        return a
+        first, count = self._env_window(env_first, env_count)
+        return _abi.fill(SpectrumArgs, bank=self._bank(), dt=float(self.physics_timestep if dt is None else dt),
+                         env_first=first, env_count=count, window=None if window is None else window.data_ptr(),
+                         spectrum=None if spectrum is None else spectrum.data_ptr(), hip_stream=self._stream(hip_stream))
 
     def track_raw(self, args: TrackArgs) -> int:
         """rp_hear_track with a caller-made argument block; returns the C return code."""
-        return self._L.rp_hear_track(self._h, ctypes.byref(args))
+        return self._handle.call_raw("track", args)
 
     def spectrum_raw(self, args: SpectrumArgs) -> int:
         """rp_hear_spectrum with a caller-made argument block; returns the C return code."""
-        return self._L.rp_hear_spectrum(self._h, ctypes.byref(args))
+        return self._handle.call_raw("spectrum", args)
 
     def _check_trace(self, trace):
         import torch
@@ -270,17 +224,14 @@ class Hearing:
         tensors of any integer or bool type, or None."""
         self._check_trace(trace)
         pedal, restart = self._flags(pedal, "pedal"), self._flags(restart, "restart")   # (kept alive until the launch)
-        if self.track_raw(self.track_args(trace, pedal, restart, dt, env_first, env_count, hip_stream)) != 0:
-            raise HearingError(self.last_error())
+        self._handle.call("track", self.track_args(trace, pedal, restart, dt, env_first, env_count, hip_stream))
 
     def spectrum(self, window=False, env_first=0, env_count=None, dt=None, hip_stream=None):
         """The magnitudes [E, B] of the newest `window` samples of what the bank sounds like, or (magnitudes, samples
         [E, W]) with `window=True`.  The tensors are this object's cached buffers and are overwritten by the next
         call; envs outside the window keep their rows."""
         spec, wave = self.outputs()
-        a = self.spectrum_args(spec, wave if window else None, dt, env_first, env_count, hip_stream)
-        if self.spectrum_raw(a) != 0:
-            raise HearingError(self.last_error())
+        self._handle.call("spectrum", self.spectrum_args(spec, wave if window else None, dt, env_first, env_count, hip_stream))
         return (spec, wave) if window else spec
 
     def observe(self, trace, pedal=None, restart=None, window=False, env_first=0, env_count=None, dt=None, hip_stream=None):

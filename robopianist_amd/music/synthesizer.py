@@ -11,7 +11,6 @@ from __future__ import annotations
 
 import ctypes
 import math
-import os
 import struct
 from typing import List, Optional, Sequence, Tuple
 
@@ -21,9 +20,6 @@ from robopianist_amd import _abi
 from robopianist_amd.music import constants as consts
 from robopianist_amd.music import midi_module
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("RP_AUDIO_LIB") or os.path.join(os.path.dirname(_HERE), "csrc", "librp_audio.so")
-
 EXPORTED_SYMBOLS = ("rp_audio_create", "rp_audio_destroy", "rp_audio_notes_from_trace", "rp_audio_synthesize",
                     "rp_audio_dim", "rp_audio_last_error")
 
@@ -32,8 +28,6 @@ MAX_PARTIALS = 8
 PEDAL_BIT = 88           # bit of the trace that carries the sustain pedal
 TAIL_SECONDS = 1.0       # the reference's second of silence after the last event
 _BLOB_MAGIC, _BLOB_VERSION = 0x55415052, 1
-
-_lib = None
 
 
 class AudioError(RuntimeError):
@@ -179,31 +173,14 @@ def n_samples(sample_rate: float, substeps: int, dt: float) -> int:
     return int(math.ceil(float(sample_rate) * (float(substeps) * float(dt) + TAIL_SECONDS)))
 
 
-def declare(L, prefix: str = "rp_audio_"):
-    """argtypes of the C ABI on a loaded library (the host build of the tests exports the same calls)."""
-    getattr(L, prefix + "last_error").restype = ctypes.c_char_p
-    getattr(L, prefix + "create").argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_int,
-                                              ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]
-    getattr(L, prefix + "destroy").argtypes = [ctypes.c_void_p]
-    getattr(L, prefix + "destroy").restype = None
-    getattr(L, prefix + "notes_from_trace").argtypes = [ctypes.c_void_p, ctypes.POINTER(NotesArgs)]
-    getattr(L, prefix + "synthesize").argtypes = [ctypes.c_void_p, ctypes.POINTER(SynthArgs)]
-    getattr(L, prefix + "dim").argtypes = [ctypes.c_void_p, ctypes.c_char_p]
+_table = _abi.HandleTable("rp_audio_", {"notes_from_trace": NotesArgs, "synthesize": SynthArgs}, AudioError, "RP_AUDIO_LIB",
+                          "librp_audio.so", "audio",
+                          create=[ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int])
+LIB_PATH = _table.path
+load_library, declare = _table.load, _table.declare
 
 
-def load_library(path: Optional[str] = None):
-    """Loads librp_audio.so; raises AudioError if it has not been built."""
-    global _lib
-    if _lib is not None and path is None:
-        return _lib
-    L = _abi.open_library(LIB_PATH if path is None else path, "audio", AudioError)
-    declare(L)
-    if path is None:
-        _lib = L
-    return L
-
-
-class Synthesizer:
+class Synthesizer(_abi.Owner):
     """Batched synthesiser.  `physics_timestep` is the dt of the traces it is given (synthesize_trace can override
     it per call); `timbre` defaults to DEFAULT_TIMBRE.  The note lists live in device tensors of this object
     (`notes`): rp_audio_notes_from_trace fills them, `set_notes` writes one from the host."""
@@ -212,17 +189,13 @@ class Synthesizer:
                  max_notes: int = 2048, device_id: int = 0, physics_timestep: float = 0.005,
                  timbre: Optional[dict] = None):
         import torch
-        self._L = load_library()
         self.n_envs, self.sample_rate = int(n_envs), sample_rate
         self.max_substeps, self.max_notes, self.device_id = int(max_substeps), int(max_notes), int(device_id)
         self.physics_timestep = float(physics_timestep)
         self.timbre = DEFAULT_TIMBRE if timbre is None else timbre
         self.blob = make_audio_blob(self.timbre, sample_rate)
-        self._h = ctypes.c_void_p()
-        rc = self._L.rp_audio_create(self.blob, len(self.blob), self.n_envs, self.max_substeps, self.max_notes,
-                                     self.device_id, ctypes.byref(self._h))
-        if rc != 0:
-            raise AudioError(self._L.rp_audio_last_error().decode())
+        self._handle = _abi.Handle(_table, self.blob, len(self.blob), self.n_envs, self.max_substeps, self.max_notes,
+                                   self.device_id)
         dev = self.device = torch.device("cuda", self.device_id)
         E, N = self.n_envs, self.max_notes
         self.notes = dict(key=torch.zeros((E, N), dtype=torch.int32, device=dev),
@@ -233,18 +206,7 @@ class Synthesizer:
                           dropped=torch.zeros(E, dtype=torch.int32, device=dev))
         self._out = {}
 
-    def __del__(self):
-        try:
-            if self._h:
-                self._L.rp_audio_destroy(self._h)
-                self._h = ctypes.c_void_p()
-        except Exception:
-            pass
-
     # -- helpers ---------------------------------------------------------------------------------------------
-    def last_error(self) -> str:
-        return self._L.rp_audio_last_error().decode()
-
     @property
     def dropped(self):
         """[n_envs] int32 device tensor: the notes of the last list of every env that did not fit max_notes."""
@@ -288,33 +250,24 @@ class Synthesizer:
 
     # -- the two calls -----------------------------------------------------------------------------------------
     def notes_args(self, trace, lengths, dt, env_first=0, env_count=None, hip_stream=None) -> NotesArgs:
-        a = NotesArgs()
-        a.struct_size = ctypes.sizeof(NotesArgs)
-        a.trace, a.lengths, a.trace_substeps = trace.data_ptr(), lengths.data_ptr(), int(trace.shape[1])
-        a.env_first, a.env_count = self._window(env_first, env_count)
-        a.dt = float(dt)
-        a.notes = self._notes_struct()
-        a.hip_stream = self._stream(hip_stream)
-        return a
+        first, count = self._window(env_first, env_count)
+        return _abi.fill(NotesArgs, trace=trace.data_ptr(), lengths=lengths.data_ptr(), trace_substeps=int(trace.shape[1]),
+                         env_first=first, env_count=count, dt=float(dt), notes=self._notes_struct(),
+                         hip_stream=self._stream(hip_stream))
 
     def synth_args(self, lengths, dt, substeps_cap, wave, pcm, env_first=0, env_count=None, hip_stream=None) -> SynthArgs:
-        a = SynthArgs()
-        a.struct_size = ctypes.sizeof(SynthArgs)
-        a.notes = self._notes_struct()
-        a.lengths, a.substeps_cap, a.n_cap = lengths.data_ptr(), int(substeps_cap), int(wave.shape[1])
-        a.env_first, a.env_count = self._window(env_first, env_count)
-        a.dt = float(dt)
-        a.wave, a.pcm = wave.data_ptr(), (None if pcm is None else pcm.data_ptr())
-        a.hip_stream = self._stream(hip_stream)
-        return a
+        first, count = self._window(env_first, env_count)
+        return _abi.fill(SynthArgs, notes=self._notes_struct(), lengths=lengths.data_ptr(), substeps_cap=int(substeps_cap),
+                         n_cap=int(wave.shape[1]), env_first=first, env_count=count, dt=float(dt), wave=wave.data_ptr(),
+                         pcm=None if pcm is None else pcm.data_ptr(), hip_stream=self._stream(hip_stream))
 
     def notes_raw(self, args: NotesArgs) -> int:
         """rp_audio_notes_from_trace with a caller-made argument block; returns the C return code."""
-        return self._L.rp_audio_notes_from_trace(self._h, ctypes.byref(args))
+        return self._handle.call_raw("notes_from_trace", args)
 
     def synthesize_raw(self, args: SynthArgs) -> int:
         """rp_audio_synthesize with a caller-made argument block; returns the C return code."""
-        return self._L.rp_audio_synthesize(self._h, ctypes.byref(args))
+        return self._handle.call_raw("synthesize", args)
 
     def _check_trace(self, trace):
         import torch
@@ -326,9 +279,8 @@ class Synthesizer:
         """Fills `notes` (and `dropped`) of the envs of the window from `trace` [E, T, 4]; returns `notes`."""
         self._check_trace(trace)
         lengths = self._lengths(lengths, int(trace.shape[1]))
-        a = self.notes_args(trace, lengths, self.physics_timestep if dt is None else dt, env_first, env_count, hip_stream)
-        if self.notes_raw(a) != 0:
-            raise AudioError(self.last_error())
+        self._handle.call("notes_from_trace", self.notes_args(trace, lengths, self.physics_timestep if dt is None else dt,
+                                                              env_first, env_count, hip_stream))
         return self.notes
 
     def synthesize_notes(self, lengths, substeps_cap, dt=None, pcm=True, env_first=0, env_count=None, hip_stream=None,
@@ -337,9 +289,8 @@ class Synthesizer:
         dt = self.physics_timestep if dt is None else dt
         lengths = self._lengths(lengths, int(substeps_cap))
         wave, pcm_t = self.outputs(self.n_samples(substeps_cap, dt), cache)
-        a = self.synth_args(lengths, dt, substeps_cap, wave, pcm_t if pcm else None, env_first, env_count, hip_stream)
-        if self.synthesize_raw(a) != 0:
-            raise AudioError(self.last_error())
+        self._handle.call("synthesize", self.synth_args(lengths, dt, substeps_cap, wave, pcm_t if pcm else None, env_first,
+                                                        env_count, hip_stream))
         return wave, (pcm_t if pcm else None)
 
     def synthesize_trace(self, trace, lengths, pcm=True, env_first=0, env_count=None, dt=None, hip_stream=None):

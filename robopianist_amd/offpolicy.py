@@ -14,23 +14,17 @@ from __future__ import annotations
 import copy
 import ctypes
 import math
-import os
 
 from robopianist_amd import _abi
 from robopianist_amd.learning import (F32, F64, MAX_ACTIONS, MAX_FIELDS, MAX_HIDDEN, STEP_FIRST, STEP_LAST, STEP_MID,  # noqa: F401
                                       LOG_2PI, DeviceLearner, LearnError, Mlp, _train_and_evaluate, _unwrap, field_table,
                                       mlp_table, moments, pack)
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("RP_SAC_LIB") or os.path.join(_HERE, "csrc", "librp_sac.so")
-
 EXPORTED_SYMBOLS = ("rp_sac_sample", "rp_sac_act", "rp_sac_target", "rp_sac_dim", "rp_sac_last_error")
 
 MAX_CRITICS = 4
 SAMPLE_TRIES = 4
 LN_2 = math.log(2.0)
-
-_lib = None
 
 _p, _i, _u32, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_float
 
@@ -61,22 +55,10 @@ class TargetArgs(ctypes.Structure):
 _ARGS = {"sample": SampleArgs, "act": ActArgs, "target": TargetArgs}
 
 
-def load_library(path: str = LIB_PATH):
-    """Loads librp_sac.so; raises LearnError if it has not been built."""
-    global _lib
-    if _lib is None:
-        _lib = declare(_abi.open_library(path, "off-policy learner", LearnError))
-    return _lib
-
-
-_entries = _abi.EntryTable("rp_sac_", _ARGS, LearnError, load_library)
-make_args, call_raw, last_error, dim, _call = (_entries.make_args, _entries.call_raw, _entries.last_error, _entries.dim,
-                                               _entries.call)
-
-
-def declare(L, prefix: str = "rp_sac_"):
-    """Declares the ABI's prototypes on a loaded library whose symbols start with `prefix`."""
-    return _entries.declare(L, prefix)
+_entries = _abi.EntryTable("rp_sac_", _ARGS, LearnError, "RP_SAC_LIB", "librp_sac.so", "off-policy learner")
+LIB_PATH = _entries.path
+load_library, declare, make_args, call_raw, last_error, dim, _call = (
+    _entries.load, _entries.declare, _entries.make_args, _entries.call_raw, _entries.last_error, _entries.dim, _entries.call)
 
 
 def critic_table(critics):

@@ -10,22 +10,16 @@ library has no CPU fallback: a missing library is an error.
 from __future__ import annotations
 
 import ctypes
-import os
 
 import numpy as np
 
 from robopianist_amd import _abi
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("RP_PLAN_LIB") or os.path.join(_HERE, "csrc", "librp_plan.so")
 
 EXPORTED_SYMBOLS = ("rp_plan_fork", "rp_plan_sample", "rp_plan_action", "rp_plan_accumulate", "rp_plan_select",
                     "rp_plan_shift", "rp_plan_dim", "rp_plan_last_error")
 
 MAX_FIELDS = 64
 SPLINES = {"zero": 0, "linear": 1}
-
-_lib = None
 
 
 class PlanError(RuntimeError):
@@ -78,22 +72,10 @@ _ARGS = {"fork": ForkArgs, "sample": SampleArgs, "action": ActionArgs, "accumula
          "shift": ShiftArgs}
 
 
-def load_library(path: str = LIB_PATH):
-    """Loads librp_plan.so; raises PlanError if it has not been built."""
-    global _lib
-    if _lib is None:
-        _lib = declare(_abi.open_library(path, "planner", PlanError))
-    return _lib
-
-
-_entries = _abi.EntryTable("rp_plan_", _ARGS, PlanError, load_library)
-make_args, call_raw, last_error, dim, _call = (_entries.make_args, _entries.call_raw, _entries.last_error, _entries.dim,
-                                               _entries.call)
-
-
-def declare(L, prefix: str = "rp_plan_"):
-    """Declares the ABI's prototypes on a loaded library whose symbols start with `prefix`."""
-    return _entries.declare(L, prefix)
+_entries = _abi.EntryTable("rp_plan_", _ARGS, PlanError, "RP_PLAN_LIB", "librp_plan.so", "planner")
+LIB_PATH = _entries.path
+load_library, declare, make_args, call_raw, last_error, dim, _call = (
+    _entries.load, _entries.declare, _entries.make_args, _entries.call_raw, _entries.last_error, _entries.dim, _entries.call)
 
 
 def field_table(fields):

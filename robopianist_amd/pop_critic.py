@@ -10,20 +10,14 @@ learner that uses it.  Like the engine, the library has no CPU fallback: a missi
 from __future__ import annotations
 
 import ctypes
-import os
 
 from robopianist_amd import _abi, critic
 from robopianist_amd.critic import APPLY_ONLY, COUNTER, MAX_CRITICS, PARAMS, ROWS_ONLY, STEP, Set, adam_scalars, set_entry, set_table  # noqa: F401
 from robopianist_amd.learning import LearnError
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("RP_POP_CRITIC_LIB") or os.path.join(_HERE, "csrc", "librp_pop_critic.so")
-
 EXPORTED_SYMBOLS = ("rp_pop_critic_step", "rp_pop_critic_workspace", "rp_pop_critic_dim", "rp_pop_critic_last_error")
 
 TILE_MAJOR, MEMBER_MAJOR = 0, 1      # the workgroup order of both launches (speed only): population's
-
-_lib = None
 
 _i, _sz = ctypes.c_int, ctypes.c_size_t
 
@@ -40,22 +34,10 @@ class WorkspaceArgs(ctypes.Structure):
 _ARGS = {"step": StepArgs, "workspace": WorkspaceArgs}
 
 
-def load_library(path: str = LIB_PATH):
-    """Loads librp_pop_critic.so; raises LearnError if it has not been built."""
-    global _lib
-    if _lib is None:
-        _lib = declare(_abi.open_library(path, "population critic step", LearnError))
-    return _lib
-
-
-_entries = _abi.EntryTable("rp_pop_critic_", _ARGS, LearnError, load_library)
-make_args, call_raw, last_error, dim, _call = (_entries.make_args, _entries.call_raw, _entries.last_error, _entries.dim,
-                                               _entries.call)
-
-
-def declare(L, prefix: str = "rp_pop_critic_"):
-    """Declares the ABI's prototypes on a loaded library whose symbols start with `prefix`."""
-    return _entries.declare(L, prefix)
+_entries = _abi.EntryTable("rp_pop_critic_", _ARGS, LearnError, "RP_POP_CRITIC_LIB", "librp_pop_critic.so", "population critic step")
+LIB_PATH = _entries.path
+load_library, declare, make_args, call_raw, last_error, dim, _call = (
+    _entries.load, _entries.declare, _entries.make_args, _entries.call_raw, _entries.last_error, _entries.dim, _entries.call)
 
 
 def workspace_bytes(n_critics, H1, H2, row_count, member_count) -> int:

@@ -20,7 +20,6 @@ from __future__ import annotations
 
 import ctypes
 import math
-import os
 
 import numpy as np
 import torch
@@ -32,15 +31,10 @@ from robopianist_amd.droq import Critic, DroQCore
 from robopianist_amd.learning import STEP_FIRST, LearnError, Mlp, _train_and_evaluate, mlp_table
 from robopianist_amd.offpolicy import ReplayLearner, squashed_gaussian
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("RP_POP_LIB") or os.path.join(_HERE, "csrc", "librp_pop.so")
-
 EXPORTED_SYMBOLS = ("rp_pop_act", "rp_pop_sample", "rp_pop_target", "rp_pop_moments", "rp_pop_dim", "rp_pop_last_error")
 
 INTERLEAVED, BLOCKED = 0, 1          # row j of member p is array row p + P j / p rows + j
 TILE_MAJOR, MEMBER_MAJOR = 0, 1      # the workgroup order of act and target (speed only)
-
-_lib = None
 
 _p, _i, _u32, _f, _d = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_float, ctypes.c_double
 
@@ -81,22 +75,10 @@ class MomentsArgs(ctypes.Structure):
 _ARGS = {"act": ActArgs, "sample": SampleArgs, "target": TargetArgs, "moments": MomentsArgs}
 
 
-def load_library(path: str = LIB_PATH):
-    """Loads librp_pop.so; raises LearnError if it has not been built."""
-    global _lib
-    if _lib is None:
-        _lib = declare(_abi.open_library(path, "population", LearnError))
-    return _lib
-
-
-_entries = _abi.EntryTable("rp_pop_", _ARGS, LearnError, load_library)
-make_args, call_raw, last_error, dim, _call = (_entries.make_args, _entries.call_raw, _entries.last_error, _entries.dim,
-                                               _entries.call)
-
-
-def declare(L, prefix: str = "rp_pop_"):
-    """Declares the ABI's prototypes on a loaded library whose symbols start with `prefix`."""
-    return _entries.declare(L, prefix)
+_entries = _abi.EntryTable("rp_pop_", _ARGS, LearnError, "RP_POP_LIB", "librp_pop.so", "population")
+LIB_PATH = _entries.path
+load_library, declare, make_args, call_raw, last_error, dim, _call = (
+    _entries.load, _entries.declare, _entries.make_args, _entries.call_raw, _entries.last_error, _entries.dim, _entries.call)
 
 
 def _order(grid_order):

@@ -8,20 +8,14 @@ render_tables.py).  Like the engine, it has no CPU fallback: a missing library i
 from __future__ import annotations
 
 import ctypes
-import os
 
 import numpy as np
 
 from robopianist_amd import _abi
 from robopianist_amd.model import cameras, render_tables
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("RP_RENDER_LIB") or os.path.join(_HERE, "csrc", "librp_render.so")
-
 EXPORTED_SYMBOLS = ("rp_render_create", "rp_render_destroy", "rp_render", "rp_render_geom_frames", "rp_render_dim",
                     "rp_render_last_error")
-
-_lib = None
 
 
 class RenderError(RuntimeError):
@@ -51,43 +45,25 @@ def make_args(camera, height, width, env_first, env_count, qpos=None, tree_offse
               depth=None, segmentation=None, hip_stream=None) -> RenderArgs:
     """Fills an rp_render_args; the array arguments are raw addresses (or None)."""
     cam = cameras.resolve(camera)
-    a = RenderArgs()
-    a.struct_size = ctypes.sizeof(RenderArgs)
-    a.qpos, a.tree_offset, a.key_rgb = qpos, tree_offset, key_rgb
-    a.cam_pos = (ctypes.c_double * 3)(*[float(x) for x in cam.pos])
-    a.cam_rot = (ctypes.c_double * 9)(*[float(x) for x in np.asarray(cam.rot).reshape(-1)])
-    a.fovy_deg = float(cam.fovy)
-    a.height, a.width = int(height), int(width)
-    a.env_first, a.env_count = int(env_first), int(env_count)
-    a.rgb, a.depth, a.segmentation = rgb, depth, segmentation
-    a.hip_stream = hip_stream
-    return a
+    return _abi.fill(RenderArgs, qpos=qpos, tree_offset=tree_offset, key_rgb=key_rgb,
+                     cam_pos=(ctypes.c_double * 3)(*[float(x) for x in cam.pos]),
+                     cam_rot=(ctypes.c_double * 9)(*[float(x) for x in np.asarray(cam.rot).reshape(-1)]),
+                     fovy_deg=float(cam.fovy), height=int(height), width=int(width), env_first=int(env_first),
+                     env_count=int(env_count), rgb=rgb, depth=depth, segmentation=segmentation, hip_stream=hip_stream)
 
 
-def load_library(path: str = LIB_PATH):
-    """Loads librp_render.so; raises RenderError if it has not been built."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    L = _abi.open_library(path, "render", RenderError)
-    L.rp_render_last_error.restype = ctypes.c_char_p
-    L.rp_render_create.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                   ctypes.POINTER(ctypes.c_void_p)]
-    L.rp_render_destroy.argtypes = [ctypes.c_void_p]
-    L.rp_render_destroy.restype = None
-    L.rp_render.argtypes = [ctypes.c_void_p, ctypes.POINTER(RenderArgs)]
-    L.rp_render_geom_frames.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
-    L.rp_render_dim.argtypes = [ctypes.c_void_p, ctypes.c_char_p]
-    _lib = L
-    return L
+_table = _abi.HandleTable("rp_render_", {"": RenderArgs}, RenderError, "RP_RENDER_LIB", "librp_render.so", "render",
+                          create=[ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.c_int],
+                          extra={"geom_frames": [ctypes.c_void_p]})
+LIB_PATH = _table.path
+load_library, declare = _table.load, _table.declare
 
 
-class Renderer:
+class Renderer(_abi.Owner):
     """Batched camera renderer of one compiled scene (`scene_info`: model/scene.py SceneInfo)."""
 
     def __init__(self, scene_info, n_envs: int, device_id: int = 0, precision: int = 64,
                  colorize_fingertips: bool = False):
-        self._L = load_library()
         m = scene_info.model
         self.model = m
         self.n_envs, self.device_id, self.precision = int(n_envs), int(device_id), int(precision)
@@ -96,23 +72,10 @@ class Renderer:
                                                    colorize_fingertips=colorize_fingertips)
         self.blob = render_tables.make_render_blob(m, scene_info.key_joint_ids, scene_info.key_geom_ids,
                                                    colorize_fingertips=colorize_fingertips, tables=tables)
-        self._h = ctypes.c_void_p()
-        rc = self._L.rp_render_create(self.blob, len(self.blob), self.n_envs, self.device_id, self.precision,
-                                      ctypes.byref(self._h))
-        if rc != 0:
-            raise RenderError(self._L.rp_render_last_error().decode())
-        self.ngeom = self._L.rp_render_dim(self._h, b"ngeom")
-        self.ntree = self._L.rp_render_dim(self._h, b"ntree")
+        self._handle = _abi.Handle(_table, self.blob, len(self.blob), self.n_envs, self.device_id, self.precision)
+        self.ngeom, self.ntree = self._handle.dim("ngeom"), self._handle.dim("ntree")
         self.geom_id = np.asarray(tables["rnd_geom_id"], np.int64)   # model geom id of the renderer's geom i
         self._out = {}
-
-    def __del__(self):
-        try:
-            if self._h:
-                self._L.rp_render_destroy(self._h)
-                self._h = ctypes.c_void_p()
-        except Exception:
-            pass
 
     def outputs(self, height: int, width: int):
         """The cached output tensors of this image size: (rgb uint8 [E,H,W,3], depth float32 [E,H,W],
@@ -129,10 +92,7 @@ class Renderer:
 
     def render_raw(self, args: RenderArgs) -> int:
         """rp_render with a caller-made argument block; returns the C return code (see last_error())."""
-        return self._L.rp_render(self._h, ctypes.byref(args))
-
-    def last_error(self) -> str:
-        return self._L.rp_render_last_error().decode()
+        return self._handle.call_raw("", args)
 
     def render(self, qpos, height: int, width: int, camera=-1, tree_offset=None, key_rgb=None, rgb=True,
                depth=False, segmentation=False, env_first: int = 0, env_count=None, hip_stream=None):
@@ -154,16 +114,14 @@ class Renderer:
                 raise RenderError(f"render: qpos / tree_offset must be {want}")
         o_rgb, o_depth, o_seg = self.outputs(height, width) if height > 0 and width > 0 else (None, None, None)
         cam = cameras.resolve(camera, self.piano_size)
-        a = make_args(cam, height, width, env_first, self.n_envs - env_first if env_count is None else env_count,
-                      qpos=qpos.data_ptr() if qpos is not None else None,
-                      tree_offset=tree_offset.data_ptr() if tree_offset is not None else None,
-                      key_rgb=key_rgb.data_ptr() if key_rgb is not None else None,
-                      rgb=o_rgb.data_ptr() if (rgb and o_rgb is not None) else None,
-                      depth=o_depth.data_ptr() if (depth and o_depth is not None) else None,
-                      segmentation=o_seg.data_ptr() if (segmentation and o_seg is not None) else None,
-                      hip_stream=hip_stream)
-        if self._L.rp_render(self._h, ctypes.byref(a)) != 0:
-            raise RenderError(self.last_error())
+        self._handle.call("", make_args(
+            cam, height, width, env_first, self.n_envs - env_first if env_count is None else env_count,
+            qpos=qpos.data_ptr() if qpos is not None else None,
+            tree_offset=tree_offset.data_ptr() if tree_offset is not None else None,
+            key_rgb=key_rgb.data_ptr() if key_rgb is not None else None,
+            rgb=o_rgb.data_ptr() if (rgb and o_rgb is not None) else None,
+            depth=o_depth.data_ptr() if (depth and o_depth is not None) else None,
+            segmentation=o_seg.data_ptr() if (segmentation and o_seg is not None) else None, hip_stream=hip_stream))
         return (o_rgb if rgb else None, o_depth if depth else None, o_seg if segmentation else None)
 
     def geom_frames(self) -> np.ndarray:

@@ -11,7 +11,6 @@ video stream, PCM audio stream, `idx1` index).
 from __future__ import annotations
 
 import ctypes
-import os
 import struct
 from pathlib import Path
 from typing import Optional, Sequence, Tuple, Union
@@ -20,13 +19,8 @@ import numpy as np
 
 from robopianist_amd import _abi
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("RP_VIDEO_LIB") or os.path.join(_HERE, "csrc", "librp_video.so")
-
 EXPORTED_SYMBOLS = ("rp_video_create", "rp_video_destroy", "rp_video_encode", "rp_video_max_bytes", "rp_video_header",
                     "rp_video_dim", "rp_video_last_error")
-
-_lib = None
 
 
 class VideoError(RuntimeError):
@@ -48,37 +42,15 @@ class EncodeArgs(ctypes.Structure):
 
 def make_args(frame_first, frame_count, bytes_cap, rgb=None, out_bytes=None, length=None, hip_stream=None) -> EncodeArgs:
     """Fills an rp_video_encode_args; the array arguments are raw addresses (or None)."""
-    a = EncodeArgs()
-    a.struct_size = ctypes.sizeof(EncodeArgs)
-    a.rgb, a.bytes, a.length = rgb, out_bytes, length
-    a.frame_first, a.frame_count, a.bytes_cap = int(frame_first), int(frame_count), int(bytes_cap)
-    a.hip_stream = hip_stream
-    return a
+    return _abi.fill(EncodeArgs, rgb=rgb, bytes=out_bytes, length=length, frame_first=int(frame_first),
+                     frame_count=int(frame_count), bytes_cap=int(bytes_cap), hip_stream=hip_stream)
 
 
-def declare(L, prefix: str = "rp_video_"):
-    """argtypes of the C ABI on a loaded library (the host build of the tests exports the same calls)."""
-    getattr(L, prefix + "last_error").restype = ctypes.c_char_p
-    getattr(L, prefix + "create").argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                              ctypes.POINTER(ctypes.c_void_p)]
-    getattr(L, prefix + "destroy").argtypes = [ctypes.c_void_p]
-    getattr(L, prefix + "destroy").restype = None
-    getattr(L, prefix + "encode").argtypes = [ctypes.c_void_p, ctypes.POINTER(EncodeArgs)]
-    getattr(L, prefix + "max_bytes").argtypes = [ctypes.c_void_p]
-    getattr(L, prefix + "header").argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]
-    getattr(L, prefix + "dim").argtypes = [ctypes.c_void_p, ctypes.c_char_p]
-
-
-def load_library(path: Optional[str] = None):
-    """Loads librp_video.so; raises VideoError if it has not been built."""
-    global _lib
-    if _lib is not None and path is None:
-        return _lib
-    L = _abi.open_library(LIB_PATH if path is None else path, "video", VideoError)
-    declare(L)
-    if path is None:
-        _lib = L
-    return L
+_table = _abi.HandleTable("rp_video_", {"encode": EncodeArgs}, VideoError, "RP_VIDEO_LIB", "librp_video.so", "video",
+                          create=[ctypes.c_int] * 5,
+                          extra={"max_bytes": [], "header": [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]})
+LIB_PATH = _table.path
+load_library, declare = _table.load, _table.declare
 
 
 def read_header(L, handle, prefix: str = "rp_video_") -> bytes:
@@ -91,29 +63,16 @@ def read_header(L, handle, prefix: str = "rp_video_") -> bytes:
     return bytes(buf)
 
 
-class Encoder:
+class Encoder(_abi.Owner):
     """Batched JPEG encoder of `max_frames` frames of one size and quality."""
 
     def __init__(self, height: int, width: int, max_frames: int, quality: int = 90, device_id: int = 0):
-        self._L = load_library()
         self.height, self.width, self.max_frames = int(height), int(width), int(max_frames)
         self.quality, self.device_id = int(quality), int(device_id)
-        self._h = ctypes.c_void_p()
-        rc = self._L.rp_video_create(self.height, self.width, self.max_frames, self.quality, self.device_id,
-                                     ctypes.byref(self._h))
-        if rc != 0:
-            raise VideoError(self._L.rp_video_last_error().decode())
+        self._handle = _abi.Handle(_table, self.height, self.width, self.max_frames, self.quality, self.device_id)
         self.max_bytes = self._L.rp_video_max_bytes(self._h)   # a frame never needs more: the default row size
         self.header = read_header(self._L, self._h)
         self._out = {}
-
-    def __del__(self):
-        try:
-            if self._h:
-                self._L.rp_video_destroy(self._h)
-                self._h = ctypes.c_void_p()
-        except Exception:
-            pass
 
     def outputs(self, bytes_cap: Optional[int] = None):
         """The cached output tensors of this row size: (bytes uint8 [N,bytes_cap], length int32 [N]), allocated at
@@ -128,10 +87,7 @@ class Encoder:
 
     def encode_raw(self, args: EncodeArgs) -> int:
         """rp_video_encode with a caller-made argument block; returns the C return code (see last_error())."""
-        return self._L.rp_video_encode(self._h, ctypes.byref(args))
-
-    def last_error(self) -> str:
-        return self._L.rp_video_last_error().decode()
+        return self._handle.call_raw("encode", args)
 
     def encode(self, rgb, frame_first: int = 0, frame_count: Optional[int] = None, bytes_cap: Optional[int] = None,
                hip_stream=None):
@@ -147,11 +103,9 @@ class Encoder:
         if hip_stream is None:
             hip_stream = torch.cuda.current_stream(torch.device("cuda", self.device_id)).cuda_stream
         out, length = self.outputs(bytes_cap)
-        a = make_args(frame_first, self.max_frames - frame_first if frame_count is None else frame_count,
-                      out.shape[1], rgb=rgb.data_ptr(), out_bytes=out.data_ptr(), length=length.data_ptr(),
-                      hip_stream=hip_stream)
-        if self._L.rp_video_encode(self._h, ctypes.byref(a)) != 0:
-            raise VideoError(self.last_error())
+        self._handle.call("encode", make_args(
+            frame_first, self.max_frames - frame_first if frame_count is None else frame_count, out.shape[1],
+            rgb=rgb.data_ptr(), out_bytes=out.data_ptr(), length=length.data_ptr(), hip_stream=hip_stream))
         return out, length
 
     def frames(self, rgb, frame_first: int = 0, frame_count: Optional[int] = None, bytes_cap: Optional[int] = None):

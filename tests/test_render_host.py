@@ -373,11 +373,7 @@ def test_render_abi_struct_and_symbols_match_the_header():
     assert names[0] == "struct_size"
     assert sorted(set(re.findall(r"\b(rp_render[a-z_0-9]*)\s*\(", src))) == sorted(render.EXPORTED_SYMBOLS)
     with pytest.raises(render.RenderError, match="not found"):
-        saved, render._lib = render._lib, None
-        try:
-            render.load_library(os.path.join(rr.ROOT, "no_such_dir", "librp_render.so"))
-        finally:
-            render._lib = saved
+        render.load_library(os.path.join(rr.ROOT, "no_such_dir", "librp_render.so"))
 
 
 def test_closed_forms_grazing_the_bounding_sphere():
