@@ -18,18 +18,12 @@ torch's step in the same job.
     python tools/gpu/actor_bench.py [--envs 4096] [--capacity 64] [--batch 4096] [--utd 20] [--out profiles/actor_bench.json]
 """
 import argparse
-import json
 import os
-import sys
-import time
-import warnings
 
-import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, ROOT)
-from robopianist_amd import actor, critic, droq, suite  # noqa: E402
+from _measure import HANDS, ROOT, alternate, host_per_call, load_twinkle, write_report   # (puts ROOT on sys.path)
+from robopianist_amd import actor, critic, droq
 
 
 def main():
@@ -42,18 +36,13 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "actor_bench.json"))
     args = ap.parse_args()
     E, C, B, U = args.envs, args.capacity, args.batch, args.utd
-    with warnings.catch_warnings():
-        warnings.simplefilter("ignore")
-        env = suite.load("RoboPianist-debug-TwinkleTwinkleRousseau-v0", seed=12345, n_envs=E, precision=64,
-                         task_kwargs=dict(trim_silence=True, control_timestep=0.05, gravity_compensation=True,
-                                          reduced_action_space=False, n_steps_lookahead=10))
+    env = load_twinkle(E, precision=64, **HANDS)
     utds = sorted({1, 4, U})
     modes = [(c, a) for c in ("torch", "fused") for a in ("torch", "fused")]
     learners = {(c, a, u): droq.DroQ(env, capacity=C, batch_size=B, seed=1, utd=u, critic_step=c, actor_step=a)
                 for c, a in modes for u in utds}
     plain, fused = learners["torch", "torch", 1], learners["torch", "fused", 1]
     dev = env.physics.device
-    sync = torch.cuda.synchronize
     for l in learners.values():   # every ring is full from here on
         l.collect(C)
     st = torch.cuda.current_stream(dev).cuda_stream
@@ -84,13 +73,6 @@ def main():
                 learners[key].update(1)
         return run
 
-    def timed(fn):
-        sync()
-        t0 = time.perf_counter()
-        fn()
-        sync()
-        return time.perf_counter() - t0
-
     work = {"fused_step": (fused_steps(actor.STEP), 200), "torch_step": (torch_steps, 200),
             "fused_rows": (fused_steps(actor.ROWS_ONLY), 200), "fused_apply": (fused_steps(actor.APPLY_ONLY), 200)}
     name = lambda c, a, u: f"update_{c}_{a}_utd{u}"
@@ -98,38 +80,24 @@ def main():
         n = max(2, 120 // (3 * u))
         for c, a in modes:
             work[name(c, a, u)] = (updates((c, a, u), n), n)
-    for fn, _ in work.values():   # warm-up of every shape
-        timed(fn)
-    times = {k: [] for k in work}
-    for _ in range(args.windows):
-        for k, (fn, n) in work.items():
-            times[k].append(timed(fn) / n)
-    med = {k: float(np.median(v)) for k, v in times.items()}
-    lo, hi = {k: float(min(v)) for k, v in times.items()}, {k: float(max(v)) for k, v in times.items()}
-    apart = lambda a, b: bool(hi[a] < lo[b])   # a's slowest window below b's fastest: more than both spreads
+    t = alternate(work, args.windows, host_per_call)
     out = {
         "task": "RoboPianist-debug-TwinkleTwinkleRousseau-v0, hull fingertips, precision 64",
         "n_envs": E, "capacity": C, "batch": B, "obs_dim": f.D, "action_dim": f.A, "hidden": [f.H1, f.H2],
         "n_critics": f.n_critics, "dropout": f.dropout, "utd": U, "windows": args.windows,
-        "us": {k: {"median": 1e6 * med[k], "lowest": 1e6 * lo[k], "highest": 1e6 * hi[k]}
-               for k in ("fused_step", "torch_step", "fused_rows", "fused_apply")},
-        "update_ms": {f"{c}_critic_{a}_actor": {str(u): {"median": 1e3 * med[name(c, a, u)], "lowest": 1e3 * lo[name(c, a, u)],
-                                                          "highest": 1e3 * hi[name(c, a, u)]} for u in utds} for c, a in modes},
-        "fused_step_is_faster": apart("fused_step", "torch_step"),
-        "fused_step_is_slower": apart("torch_step", "fused_step"),
-        "fused_actor_update_is_faster": {c: {str(u): apart(name(c, "fused", u), name(c, "torch", u)) for u in utds}
+        "us": {k: t.stat(k, 1e6) for k in ("fused_step", "torch_step", "fused_rows", "fused_apply")},
+        "update_ms": {f"{c}_critic_{a}_actor": {str(u): t.stat(name(c, a, u), 1e3) for u in utds} for c, a in modes},
+        "fused_step_is_faster": t.apart("fused_step", "torch_step"),
+        "fused_step_is_slower": t.apart("torch_step", "fused_step"),
+        "fused_actor_update_is_faster": {c: {str(u): t.apart(name(c, "fused", u), name(c, "torch", u)) for u in utds}
                                          for c in ("torch", "fused")},
-        "fused_actor_update_is_slower": {c: {str(u): apart(name(c, "torch", u), name(c, "fused", u)) for u in utds}
+        "fused_actor_update_is_slower": {c: {str(u): t.apart(name(c, "torch", u), name(c, "fused", u)) for u in utds}
                                          for c in ("torch", "fused")},
         "method": "host clock around work that ends in a device synchronise; every workload warmed up once, then "
                   "alternating windows in one process; medians with the lowest and highest window; faster / slower only "
                   "where the two sets of windows do not overlap",
     }
-    print(json.dumps(out, indent=1))
-    os.makedirs(os.path.dirname(args.out), exist_ok=True)
-    with open(args.out, "w") as fh:
-        json.dump(out, fh, indent=1)
-        fh.write("\n")
+    write_report(out, args.out, indent=1)
 
 
 if __name__ == "__main__":

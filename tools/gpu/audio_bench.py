@@ -16,37 +16,22 @@ sample.
     rocprofv3 --kernel-trace --stats --output-format csv -- python tools/gpu/audio_bench.py --windows 1 --seconds 0.3
 """
 import argparse
-import json
 import os
-import sys
-import warnings
 
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, ROOT)
+from _measure import ROOT, alternate, event_window, load_twinkle, scripted_replay, write_report
 
 
 def record_replay_trace():
     """([T][4] int32 trace with the pedal in bit 88, dt) of env 0 over the scripted replay."""
-    from robopianist_amd import suite
     from robopianist_amd.music import synthesizer
-    from robopianist_amd.suite.scripted import ScriptedActions
-    from robopianist_amd.wrappers import CanonicalSpecWrapper
-    with warnings.catch_warnings():
-        warnings.simplefilter("ignore")
-        base = suite.load("RoboPianist-debug-TwinkleTwinkleRousseau-v0", seed=12345, n_envs=2, record_key_trace=True,
-                          task_kwargs=dict(trim_silence=True, control_timestep=0.05, gravity_compensation=True,
-                                           primitive_fingertip_collisions=True))
-    env = CanonicalSpecWrapper(base)
-    dev = base.physics.device
-    actions = np.load(os.path.join(ROOT, "tests", "golden", "twinkle_twinkle_actions.npy"))
-    script = ScriptedActions(torch.as_tensor(actions, dtype=base.physics.dtype, device=dev),
-                             torch.zeros(2, dtype=torch.long, device=dev))
+    base = load_twinkle(2, record_key_trace=True, control_timestep=0.05, primitive_fingertip_collisions=True)
+    env, script, n_steps = scripted_replay(base)
     env.reset()
     rows = []
-    for _ in range(len(actions)):
+    for _ in range(n_steps):
         ts = env.step(script)
         r = base.key_trace[0].clone()
         r[:, synthesizer.PEDAL_BIT // 32] |= base.task.piano.sustain_activation[0, 0].to(torch.int32) << (synthesizer.PEDAL_BIT % 32)
@@ -83,29 +68,12 @@ def main():
     work = {"notes": lambda: call(s.notes_raw, a_notes), "synth": lambda: call(s.synthesize_raw, a_synth),
             "synth_pcm": lambda: call(s.synthesize_raw, a_both)}
 
-    def window(fn, seconds):
-        """ms per call over a window of at least `seconds` (device events around the whole window)."""
-        n, calls, total = 2, 0, 0.0
-        while total < seconds * 1e3:
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            for _ in range(n):
-                fn()
-            b.record()
-            b.synchronize()
-            total += a.elapsed_time(b); calls += n
-            n *= 2
-        return total / calls
-
     for fn in work.values():   # warm-up (code objects)
         for _ in range(3):
             fn()
     torch.cuda.synchronize()
-    res = {k: [] for k in work}
-    for _ in range(args.windows):   # alternating
-        for k, fn in work.items():
-            res[k].append(window(fn, args.seconds))
-    med = {k: float(np.median(v)) for k, v in res.items()}
+    times = alternate(work, args.windows, lambda fn: event_window(fn, args.seconds, first=2), warm=False)
+    med, res = dict(times.median), times.windows
     med["pcm"] = med["synth_pcm"] - med["synth"]
 
     # what the synthesis kernel had to sum: audible voice-partials per sample of env 0's list
@@ -136,10 +104,7 @@ def main():
         "synth_voice_partial_samples_per_s": samples * voice_partials / (med["synth"] * 1e-3),
         "windows_ms": res,
     }
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as fh:
-        json.dump(out, fh, indent=1)
-    print(json.dumps({k: v for k, v in out.items() if k != "windows_ms"}))
+    write_report(out, args.out, printed={k: v for k, v in out.items() if k != "windows_ms"})
 
 
 if __name__ == "__main__":

@@ -17,18 +17,12 @@ The fused step counts as faster only where the medians differ by more than both 
     python tools/gpu/critic_bench.py [--envs 4096] [--capacity 64] [--batch 4096] [--utd 20] [--out profiles/critic_bench.json]
 """
 import argparse
-import json
 import os
-import sys
-import time
-import warnings
 
-import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, ROOT)
-from robopianist_amd import critic, droq, suite  # noqa: E402
+from _measure import HANDS, ROOT, alternate, host_per_call, load_twinkle, write_report   # (puts ROOT on sys.path)
+from robopianist_amd import critic, droq
 
 
 def main():
@@ -41,17 +35,12 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "critic_bench.json"))
     args = ap.parse_args()
     E, C, B, U = args.envs, args.capacity, args.batch, args.utd
-    with warnings.catch_warnings():
-        warnings.simplefilter("ignore")
-        env = suite.load("RoboPianist-debug-TwinkleTwinkleRousseau-v0", seed=12345, n_envs=E, precision=64,
-                         task_kwargs=dict(trim_silence=True, control_timestep=0.05, gravity_compensation=True,
-                                          reduced_action_space=False, n_steps_lookahead=10))
+    env = load_twinkle(E, precision=64, **HANDS)
     utds = sorted({1, 4, U})
     modes = ("torch", "fused")
     learners = {(m, u): droq.DroQ(env, capacity=C, batch_size=B, seed=1, utd=u, critic_step=m) for m in modes for u in utds}
     plain, fused = learners["torch", 1], learners["fused", 1]
     dev = env.physics.device
-    sync = torch.cuda.synchronize
     for l in learners.values():   # every ring is full from here on
         l.collect(C)
     st = torch.cuda.current_stream(dev).cuda_stream
@@ -82,49 +71,28 @@ def main():
                 learners[key].update(1)
         return run
 
-    def timed(fn):
-        sync()
-        t0 = time.perf_counter()
-        fn()
-        sync()
-        return time.perf_counter() - t0
-
     work = {"fused_step": (fused_steps(critic.STEP), 200), "torch_step": (torch_steps, 200),
             "fused_rows": (fused_steps(critic.ROWS_ONLY), 200), "fused_apply": (fused_steps(critic.APPLY_ONLY), 200)}
     for u in utds:
         n = max(2, 120 // (3 * u))
         for m in modes:
             work[f"update_{m}_utd{u}"] = (updates((m, u), n), n)
-    for fn, _ in work.values():   # warm-up of every shape
-        timed(fn)
-    times = {k: [] for k in work}
-    for _ in range(args.windows):
-        for k, (fn, n) in work.items():
-            times[k].append(timed(fn) / n)
-    med = {k: float(np.median(v)) for k, v in times.items()}
-    lo, hi = {k: float(min(v)) for k, v in times.items()}, {k: float(max(v)) for k, v in times.items()}
-    apart = lambda a, b: bool(hi[a] < lo[b])   # a's slowest window below b's fastest: more than both spreads
+    t = alternate(work, args.windows, host_per_call)
     out = {
         "task": "RoboPianist-debug-TwinkleTwinkleRousseau-v0, hull fingertips, precision 64",
         "n_envs": E, "capacity": C, "batch": B, "obs_dim": fused.D, "action_dim": fused.A, "hidden": [fused.H1, fused.H2],
         "n_critics": fused.n_critics, "dropout": fused.dropout, "utd": U, "windows": args.windows,
-        "us": {k: {"median": 1e6 * med[k], "lowest": 1e6 * lo[k], "highest": 1e6 * hi[k]}
-               for k in ("fused_step", "torch_step", "fused_rows", "fused_apply")},
-        "update_ms": {m: {str(u): {"median": 1e3 * med[f"update_{m}_utd{u}"], "lowest": 1e3 * lo[f"update_{m}_utd{u}"],
-                                   "highest": 1e3 * hi[f"update_{m}_utd{u}"]} for u in utds} for m in modes},
-        "fused_step_is_faster": apart("fused_step", "torch_step"),
-        "fused_step_is_slower": apart("torch_step", "fused_step"),
-        "fused_update_is_faster": {str(u): apart(f"update_fused_utd{u}", f"update_torch_utd{u}") for u in utds},
-        "fused_update_is_slower": {str(u): apart(f"update_torch_utd{u}", f"update_fused_utd{u}") for u in utds},
+        "us": {k: t.stat(k, 1e6) for k in ("fused_step", "torch_step", "fused_rows", "fused_apply")},
+        "update_ms": {m: {str(u): t.stat(f"update_{m}_utd{u}", 1e3) for u in utds} for m in modes},
+        "fused_step_is_faster": t.apart("fused_step", "torch_step"),
+        "fused_step_is_slower": t.apart("torch_step", "fused_step"),
+        "fused_update_is_faster": {str(u): t.apart(f"update_fused_utd{u}", f"update_torch_utd{u}") for u in utds},
+        "fused_update_is_slower": {str(u): t.apart(f"update_torch_utd{u}", f"update_fused_utd{u}") for u in utds},
         "method": "host clock around work that ends in a device synchronise; every workload warmed up once, then "
                   "alternating windows in one process; medians with the lowest and highest window; faster / slower only "
                   "where the two sets of windows do not overlap",
     }
-    print(json.dumps(out, indent=1))
-    os.makedirs(os.path.dirname(args.out), exist_ok=True)
-    with open(args.out, "w") as f:
-        json.dump(out, f, indent=1)
-        f.write("\n")
+    write_report(out, args.out, indent=1)
 
 
 if __name__ == "__main__":

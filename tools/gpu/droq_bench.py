@@ -18,18 +18,12 @@ one process, windows of about half a second, medians over the windows and their 
     python tools/gpu/droq_bench.py [--envs 4096] [--capacity 64] [--batch 4096] [--utd 20] [--out profiles/droq_bench.json]
 """
 import argparse
-import json
 import os
-import sys
-import time
-import warnings
 
-import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, ROOT)
-from robopianist_amd import droq, offpolicy, suite  # noqa: E402
+from _measure import HANDS, ROOT, alternate, host_per_call, load_twinkle, write_report   # (puts ROOT on sys.path)
+from robopianist_amd import droq, offpolicy
 
 
 def main():
@@ -44,17 +38,12 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "droq_bench.json"))
     args = ap.parse_args()
     E, C, B, U, T, R = args.envs, args.capacity, args.batch, args.utd, args.horizon, args.rollouts
-    with warnings.catch_warnings():
-        warnings.simplefilter("ignore")
-        env = suite.load("RoboPianist-debug-TwinkleTwinkleRousseau-v0", seed=12345, n_envs=E, precision=64,
-                         task_kwargs=dict(trim_silence=True, control_timestep=0.05, gravity_compensation=True,
-                                          reduced_action_space=False, n_steps_lookahead=10))
+    env = load_twinkle(E, precision=64, **HANDS)
     utds = sorted({1, 4, U})
     sac = offpolicy.SAC(env, capacity=C, batch_size=B, seed=1)
     learners = {u: droq.DroQ(env, capacity=C, batch_size=B, seed=1, utd=u) for u in utds}
     one, big = learners[1], learners[U]
     dev, D, A = env.physics.device, sac.D, sac.A
-    sync = torch.cuda.synchronize
     for l in [sac] + list(learners.values()):   # every ring is full from here on
         l.collect(C)
     st = torch.cuda.current_stream(dev).cuda_stream
@@ -115,26 +104,14 @@ def main():
                 l.collect(T)
         return run
 
-    def timed(fn):
-        sync()
-        t0 = time.perf_counter()
-        fn()
-        sync()
-        return time.perf_counter() - t0
-
     work = {"droq_target": (droq_targets, 1000), "torch_droq_target": (torch_droq_targets, 1000),
             "sac_target": (sac_targets, 1000), "draw_and_act_utd": (draws_utd, 20), "draw_and_act_separate": (draws_separate, 20),
             "droq_collect": (collects(big), R * T), "sac_collect": (collects(sac), R * T)}
     for u in utds:
         n = max(2, 120 // (3 * u))
         work[f"update_utd{u}"] = (updates(u, n), n)
-    for fn, _ in work.values():   # warm-up of every shape
-        timed(fn)
-    times = {k: [] for k in work}
-    for _ in range(args.windows):
-        for k, (fn, n) in work.items():
-            times[k].append(timed(fn) / n)
-    med = {k: float(np.median(v)) for k, v in times.items()}
+    times = alternate(work, args.windows, host_per_call)
+    med = times.median
     out = {
         "task": "RoboPianist-debug-TwinkleTwinkleRousseau-v0, hull fingertips, precision 64",
         "n_envs": E, "capacity": C, "batch": B, "obs_dim": D, "action_dim": A, "hidden": [one.H1, one.H2],
@@ -147,15 +124,11 @@ def main():
         "update_ms": {str(u): 1e3 * med[f"update_utd{u}"] for u in utds},
         "update_share_of_round": {str(u): med[f"update_utd{u}"] / (med["droq_collect"] * T + med[f"update_utd{u}"])
                                   for u in utds},
-        "spread": {k: [float(min(v) / med[k]), float(max(v) / med[k])] for k, v in times.items()},
+        "spread": {k: times.spread(k) for k in work},
         "method": "host clock around work that ends in a device synchronise; every workload warmed up once, then "
                   "alternating windows in one process; medians",
     }
-    print(json.dumps(out, indent=1))
-    os.makedirs(os.path.dirname(args.out), exist_ok=True)
-    with open(args.out, "w") as f:
-        json.dump(out, f, indent=1)
-        f.write("\n")
+    write_report(out, args.out, indent=1)
 
 
 if __name__ == "__main__":

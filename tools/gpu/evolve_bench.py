@@ -21,18 +21,13 @@ Every figure: a warm-up, then --windows repeats; the median with the lowest and 
     python tools/gpu/evolve_bench.py [--envs 4096] [--members 8,16] [--batch 4096] [--out profiles/evolve_bench.json]
 """
 import argparse
-import json
 import os
-import sys
-import time
-import warnings
 
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, ROOT)
-from robopianist_amd import evolve, population, suite  # noqa: E402
+from _measure import HANDS, ROOT, Times, event_time, host_time, load_twinkle, write_report   # (puts ROOT on sys.path)
+from robopianist_amd import evolve, population
 
 HBM_PEAK = 8.0e12   # bytes / s
 
@@ -51,41 +46,22 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "evolve_bench.json"))
     args = ap.parse_args()
     E, C = args.envs, args.capacity
-    with warnings.catch_warnings():
-        warnings.simplefilter("ignore")
-        env = suite.load("RoboPianist-debug-TwinkleTwinkleRousseau-v0", seed=12345, n_envs=E, precision=64,
-                         task_kwargs=dict(trim_silence=True, control_timestep=0.05, gravity_compensation=True,
-                                          reduced_action_space=False, n_steps_lookahead=10))
+    env = load_twinkle(E, precision=64, **HANDS)
     dev = env.physics.device
-    sync = torch.cuda.synchronize
     st = torch.cuda.current_stream(dev).cuda_stream
-
-    def stat(values, scale):
-        return {"median": scale * float(np.median(values)), "lowest": scale * float(min(values)),
-                "highest": scale * float(max(values))}
-
-    def device_time(fn, n):
-        """Seconds per call of n back-to-back calls, by HIP events."""
-        start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        sync()
-        start.record()
-        for _ in range(n):
-            fn()
-        end.record()
-        end.synchronize()
-        return start.elapsed_time(end) * 1e-3 / n
-
-    def host_time(fn, n=1):
-        sync()
-        t0 = time.perf_counter()
-        for _ in range(n):
-            fn()
-        sync()
-        return (time.perf_counter() - t0) / n
 
     def repeats(measure):
         measure()   # warm-up
         return [measure() for _ in range(args.windows)]
+
+    def device_s(fn):
+        def measure():
+            torch.cuda.synchronize()
+            return event_time(fn, args.calls) * 1e-3
+        return repeats(measure)
+
+    def host_s(fn, n):
+        return repeats(lambda: host_time(fn, n) / n)
 
     out = {"task": "RoboPianist-debug-TwinkleTwinkleRousseau-v0, hull fingertips, precision 64", "n_envs": E, "capacity": C,
            "batch_all_members": args.batch, "utd": args.utd, "steps_per_round": args.steps, "rounds_per_window": args.rounds,
@@ -99,7 +75,7 @@ def main():
         for pop in (on, off):
             pop.collect(C)
             pop.update(1)      # (the torch optimisers of the actor and the temperature now hold their moments)
-        sync()
+        torch.cuda.synchronize()
         table = on._field_table()
         names = [n for n, _ in on._member_fields()]
         words = sum(w for _, w in table)
@@ -154,38 +130,35 @@ def main():
 
         r = {"fields": len(table), "copy_launches": copy(), "words_per_member": words, "members_replaced": quarter,
              "largest_field": {"name": names[big], "words_per_member": table[big][1]}}
-        r["fold_us"] = stat(repeats(lambda: device_time(fold, args.calls)), 1e6)
-        r["refill_us"] = stat(repeats(lambda: device_time(refill, args.calls)), 1e6)
-        r["plan_us"] = stat(repeats(lambda: device_time(plan, args.calls)), 1e6)
-        r["copy_us"] = stat(repeats(lambda: device_time(copy, args.calls)), 1e6)
-        largest = repeats(lambda: device_time(copy_largest, args.calls))
-        r["copy_largest_us"] = stat(largest, 1e6)
-        moved = 2 * 4 * table[big][1] * quarter                                         # read and written
-        r["copy_largest_bytes"] = moved
-        r["copy_largest_share_of_hbm_peak"] = moved / float(np.median(largest)) / HBM_PEAK
-        r["copy_bytes"] = 2 * 4 * words * quarter
-        r["event_us"] = stat(repeats(lambda: host_time(event, 20)), 1e6)
-        r["torch_event_us"] = stat(repeats(lambda: host_time(torch_event, 5)), 1e6)
+        times = Times({"fold": device_s(fold), "refill": device_s(refill), "plan": device_s(plan), "copy": device_s(copy),
+                       "copy_largest": device_s(copy_largest), "event": host_s(event, 20),
+                       "torch_event": host_s(torch_event, 5)})                        # seconds per call
         on._fit_sum.zero_()
         on._fit_count.zero_()
         # train(): alternating windows, the option off and on
-        rate = {"off": [], "every10": []}
-        for w in range(args.windows + 1):
-            for key, pop in (("off", off), ("every10", on)):
+        rate = {"rounds_per_s_off": [], "rounds_per_s_every10": []}
+        for i in range(args.windows + 1):
+            for key, pop in (("rounds_per_s_off", off), ("rounds_per_s_every10", on)):
                 t = host_time(lambda: pop.train(args.rounds, args.steps, 1))
-                if w:   # (the first window is the warm-up)
+                if i:   # (the first window is the warm-up)
                     rate[key].append(args.rounds / t)
-        r["rounds_per_s_off"], r["rounds_per_s_every10"] = stat(rate["off"], 1.0), stat(rate["every10"], 1.0)
+        rates = Times(rate)
+        for k in ("fold", "refill", "plan", "copy", "copy_largest"):
+            r[f"{k}_us"] = times.stat(k, 1e6)
+        moved = 2 * 4 * table[big][1] * quarter                                         # read and written
+        r["copy_largest_bytes"] = moved
+        r["copy_largest_share_of_hbm_peak"] = moved / times.median["copy_largest"] / HBM_PEAK
+        r["copy_bytes"] = 2 * 4 * words * quarter
+        for k in ("event", "torch_event"):
+            r[f"{k}_us"] = times.stat(k, 1e6)
+        for k in rate:
+            r[k] = rates.stat(k, 1.0)
         r["generations"] = on.generation
         round_s = 1.0 / r["rounds_per_s_off"]["median"]
         r["event_share_of_ten_rounds"] = r["event_us"]["median"] * 1e-6 / (10.0 * round_s)
         out["members"][str(P)] = r
         del on, off
-    print(json.dumps(out, indent=1))
-    os.makedirs(os.path.dirname(args.out), exist_ok=True)
-    with open(args.out, "w") as f:
-        json.dump(out, f, indent=1)
-        f.write("\n")
+    write_report(out, args.out, indent=1)
 
 
 if __name__ == "__main__":

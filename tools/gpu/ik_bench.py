@@ -16,18 +16,13 @@ with --no-resources).  Writes profiles/ik_bench.json.
     python tools/gpu/ik_bench.py [--envs 4096] [--windows 3] [--out profiles/ik_bench.json]
 """
 import argparse
-import json
 import os
 import re
 import subprocess
-import sys
-import warnings
 
-import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, ROOT)
+from _measure import HANDS, ROOT, Times, event_window, load_twinkle, staggered_replay, write_report
 
 
 def kernel_resources():
@@ -61,31 +56,15 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "ik_bench.json"))
     args = ap.parse_args()
 
-    from robopianist_amd import suite
-    from robopianist_amd.suite.scripted import ScriptedActions
-    from robopianist_amd.wrappers import CanonicalSpecWrapper, FingertipActionWrapper
+    from robopianist_amd.wrappers import FingertipActionWrapper
     E = args.envs
-    with warnings.catch_warnings():
-        warnings.simplefilter("ignore")
-        base = suite.load("RoboPianist-debug-TwinkleTwinkleRousseau-v0", seed=12345, n_envs=E,
-                          task_kwargs=dict(trim_silence=True, control_timestep=0.05, gravity_compensation=True,
-                                           reduced_action_space=False, n_steps_lookahead=10,
-                                           primitive_fingertip_collisions=False,   # hull fingertips, as bench.py's config 2
-                                           change_color_on_activation=True))
-    env = CanonicalSpecWrapper(base)
+    base = load_twinkle(E, **HANDS, primitive_fingertip_collisions=False,   # hull fingertips, as bench.py's config 2
+                        change_color_on_activation=True)
     tip_env = FingertipActionWrapper(base)          # (K = 1, delta mode: the defaults)
     ik = tip_env.ik
     phys = base.physics
     dev = phys.device
-    actions = np.load(os.path.join(ROOT, "tests", "golden", "twinkle_twinkle_actions.npy"))
-    T = actions.shape[0]
-    script = ScriptedActions(torch.as_tensor(actions, dtype=phys.dtype, device=dev),
-                             torch.zeros(E, dtype=torch.long, device=dev))
-    env.reset()
-    phase = torch.arange(E, device=dev) % T
-    for j in range(T):   # untimed prologue: spreads the envs over the episode
-        base.request_reset(phase == (T - 1 - j))
-        env.step(script)
+    env, script, _ = staggered_replay(base)
 
     targets = torch.zeros((E, ik.n_tips, 3), dtype=torch.float64, device=dev)
     up = torch.zeros_like(targets); up[..., 2] = 0.01
@@ -110,20 +89,6 @@ def main():
     def wrapped_step():
         tip_env.step(deltas)
 
-    def window(fn, seconds):
-        """ms per call over a window of at least `seconds` (device events around the whole window)."""
-        n, calls, total = 8, 0, 0.0
-        while total < seconds * 1e3:
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            for _ in range(n):
-                fn()
-            b.record()
-            b.synchronize()
-            total += a.elapsed_time(b); calls += n
-            n *= 2
-        return total / calls
-
     retarget()
     for fn in (step_only, solve_k(1), solve_k(4), step_plus_solve):   # warm-up (allocations)
         for _ in range(5):
@@ -131,16 +96,16 @@ def main():
     torch.cuda.synchronize()
     res = {"step": [], "solve_k1": [], "solve_k4": [], "step_plus_solve": [], "wrapped_step": []}
     for _ in range(args.windows):   # alternating
-        res["step"].append(window(step_only, args.seconds))
+        res["step"].append(event_window(step_only, args.seconds))
         retarget()
-        res["solve_k1"].append(window(solve_k(1), args.seconds))
-        res["solve_k4"].append(window(solve_k(4), args.seconds))
-        res["step_plus_solve"].append(window(step_plus_solve, args.seconds))
+        res["solve_k1"].append(event_window(solve_k(1), args.seconds))
+        res["solve_k4"].append(event_window(solve_k(4), args.seconds))
+        res["step_plus_solve"].append(event_window(step_plus_solve, args.seconds))
     for _ in range(5):
         wrapped_step()
     for _ in range(args.windows):
-        res["wrapped_step"].append(window(wrapped_step, args.seconds))
-    med = {k: float(np.median(v)) for k, v in res.items()}
+        res["wrapped_step"].append(event_window(wrapped_step, args.seconds))
+    med = Times(res).median
 
     out = {
         "device": torch.cuda.get_device_name(dev),
@@ -158,10 +123,7 @@ def main():
         "windows_ms": res,
         "kernel_resources": kernel_resources() if args.resources else None,
     }
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        json.dump(out, f, indent=1)
-    print(json.dumps({k: v for k, v in out.items() if k != "windows_ms"}))
+    write_report(out, args.out, printed={k: v for k, v in out.items() if k != "windows_ms"})
 
 
 if __name__ == "__main__":

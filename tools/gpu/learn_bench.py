@@ -22,18 +22,12 @@ Every timed window does `--rollouts` rollouts' worth of control steps (default 4
     python tools/gpu/learn_bench.py [--envs 4096] [--horizon 16] [--out profiles/learn_bench.json]
 """
 import argparse
-import json
 import os
-import sys
-import time
-import warnings
 
-import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, ROOT)
-from robopianist_amd import learning, suite  # noqa: E402
+from _measure import HANDS, ROOT, alternate, host_per_call, load_twinkle, write_report   # (puts ROOT on sys.path)
+from robopianist_amd import learning
 
 
 def main():
@@ -45,14 +39,9 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "learn_bench.json"))
     args = ap.parse_args()
     E, T, R = args.envs, args.horizon, args.rollouts
-    with warnings.catch_warnings():
-        warnings.simplefilter("ignore")
-        env = suite.load("RoboPianist-debug-TwinkleTwinkleRousseau-v0", seed=12345, n_envs=E, precision=64,
-                         task_kwargs=dict(trim_silence=True, control_timestep=0.05, gravity_compensation=True,
-                                          reduced_action_space=False, n_steps_lookahead=10))
+    env = load_twinkle(E, precision=64, **HANDS)
     ppo = learning.PPO(env, horizon=T, seed=1)
     dev, D, A = env.physics.device, ppo.D, ppo.A
-    sync = torch.cuda.synchronize
     bounds = ppo._bounds
     ua = torch.zeros((E, A), dtype=env.physics.dtype, device=dev)
 
@@ -119,23 +108,11 @@ def main():
         for _ in range(n):
             ppo.update_normalizer()
 
-    def timed(fn, *a):
-        sync()
-        t0 = time.perf_counter()
-        fn(*a)
-        sync()
-        return time.perf_counter() - t0
-
     # (collect right before update: the update reads the rollout the collection left in the storage)
     work = {"random": (random_steps, R * T), "collect": (collects, R * T), "update": (updates, R), "moments": (moments, 20),
             "replay": (replay_steps, R * T), "torch": (torch_steps, R * T), "act": (acts, 2000), "pack": (packs, 5000)}
-    for fn, _ in work.values():   # warm-up of every shape
-        timed(fn)
-    times = {k: [] for k in work}
-    for _ in range(args.windows):
-        for k, (fn, n) in work.items():
-            times[k].append(timed(fn) / n)
-    med = {k: float(np.median(v)) for k, v in times.items()}
+    times = alternate(work, args.windows, host_per_call)
+    med = times.median
     rate = lambda k: E / med[k]
     out = {
         "task": "RoboPianist-debug-TwinkleTwinkleRousseau-v0, hull fingertips, precision 64",
@@ -149,15 +126,11 @@ def main():
         "moments_ms": 1e3 * med["moments"],
         "rollout_ms": 1e3 * med["collect"] * T, "update_over_rollout": med["update"] / (med["collect"] * T),
         "update_and_moments_over_rollout": (med["update"] + med["moments"]) / (med["collect"] * T),
-        "spread": {k: [float(min(v) / med[k]), float(max(v) / med[k])] for k, v in times.items()},
+        "spread": {k: times.spread(k) for k in work},
         "method": "host clock around work that ends in a device synchronise; every workload warmed up once, then "
                   "alternating windows in one process; medians",
     }
-    print(json.dumps(out, indent=1))
-    os.makedirs(os.path.dirname(args.out), exist_ok=True)
-    with open(args.out, "w") as f:
-        json.dump(out, f, indent=1)
-        f.write("\n")
+    write_report(out, args.out, indent=1)
 
 
 if __name__ == "__main__":

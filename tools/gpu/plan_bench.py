@@ -17,18 +17,13 @@ workloads alternating in one process, medians over the windows:
     python tools/gpu/plan_bench.py --profile     # three plans and nothing else, for a kernel trace
 """
 import argparse
-import json
 import os
-import sys
-import time
-import warnings
 
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, ROOT)
-from robopianist_amd import planning, suite  # noqa: E402
+from _measure import ROOT, Times, host_time, load_twinkle, write_report   # (puts ROOT on sys.path)
+from robopianist_amd import planning
 
 
 def main():
@@ -44,10 +39,7 @@ def main():
     G, K, H, P = args.groups, args.candidates, args.horizon, args.knots
 
     def load(n):
-        with warnings.catch_warnings():
-            warnings.simplefilter("ignore")
-            return suite.load("RoboPianist-debug-TwinkleTwinkleRousseau-v0", n_envs=n, seed=3,
-                              task_kwargs=dict(trim_silence=True, gravity_compensation=True, n_steps_lookahead=10))
+        return load_twinkle(n, seed=3, n_steps_lookahead=10)
 
     real = load(G)
     s = planning.PredictiveSampler(real, load, n_candidates=K, horizon=H, n_knots=P, sigma=0.2, seed=1)
@@ -67,13 +59,8 @@ def main():
         print("3 plans")
         return
 
-    def timed(fn, n):
-        sync()
-        t0 = time.perf_counter()
-        for _ in range(n):
-            fn()
-        sync()
-        return 1e3 * (time.perf_counter() - t0) / n
+    def ms_per_call(fn, n):
+        return 1e3 * host_time(fn, n) / n
 
     def steps():
         for _ in range(H):
@@ -105,20 +92,17 @@ def main():
     s.plan()
     quiet_knots = s.nominal.repeat_interleave(K, dim=0).contiguous()
     for _, fn, _ in work:   # warm every shape
-        timed(fn, 2)
+        ms_per_call(fn, 2)
     windows = []
     for _ in range(args.windows):
-        windows.append({name: timed(fn, n) for name, fn, n in work})
+        windows.append({name: ms_per_call(fn, n) for name, fn, n in work})
         print(windows[-1], flush=True)
-    med = {k: float(np.median([w[k] for w in windows])) for k in windows[0]}
+    med = Times({k: [w[k] for w in windows] for k in windows[0]}).median
     out = dict(device=torch.cuda.get_device_name(0), G=G, K=K, H=H, P=P, nu=s.nu, planning_envs=s.E, fields=len(s._fields),
                fork_bytes_per_row=sum(rb for *_, rb in s._fields), median=med, windows=windows,
                kernels_share_of_plan=med["kernels_ms"] / med["plan_ms"], plan_over_steps=med["plan_ms"] / med["steps_ms"],
                warn=int(plan_env.physics.warn.max()))
-    print(json.dumps(out))
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        json.dump(out, f, indent=1)
+    write_report(out, args.out)
 
 
 if __name__ == "__main__":

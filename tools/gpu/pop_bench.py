@@ -20,18 +20,12 @@ the windows themselves are stored.  For every P of --members (B = --batch / P ro
     python tools/gpu/pop_bench.py [--envs 4096] [--members 1,8,16] [--batch 4096] [--utd 20] [--out profiles/pop_bench.json]
 """
 import argparse
-import json
 import os
-import sys
-import time
-import warnings
 
-import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, ROOT)
-from robopianist_amd import droq, learning, offpolicy, population, suite  # noqa: E402
+from _measure import HANDS, ROOT, alternate, host_per_call, load_twinkle, write_report   # (puts ROOT on sys.path)
+from robopianist_amd import droq, learning, offpolicy, population
 
 
 def main():
@@ -47,15 +41,10 @@ def main():
     args = ap.parse_args()
     E, C, B, U, T = args.envs, args.capacity, args.batch, args.utd, args.horizon
     members = [int(p) for p in args.members.split(",")]
-    with warnings.catch_warnings():
-        warnings.simplefilter("ignore")
-        env = suite.load("RoboPianist-debug-TwinkleTwinkleRousseau-v0", seed=12345, n_envs=E, precision=64,
-                         task_kwargs=dict(trim_silence=True, control_timestep=0.05, gravity_compensation=True,
-                                          reduced_action_space=False, n_steps_lookahead=10))
+    env = load_twinkle(E, precision=64, **HANDS)
     single = droq.DroQ(env, capacity=C, batch_size=B, seed=1, utd=U)
     pops = {P: population.DroQPopulation(env, P, capacity=C, batch_size=B // P, seed=1, utd=U) for P in members}
     dev, D, A = env.physics.device, single.D, single.A
-    sync = torch.cuda.synchronize
     for l in [single] + list(pops.values()):   # every ring is full from here on
         l.collect(C)
         l.update(1)                            # ... and every minibatch buffer holds rows, policy outputs and y
@@ -173,20 +162,8 @@ def main():
     for P, pop in pops.items():
         add(P, pop)
 
-    def timed(fn):
-        sync()
-        t0 = time.perf_counter()
-        fn()
-        sync()
-        return time.perf_counter() - t0
-
-    for fn, _ in work.values():   # warm-up of every shape
-        timed(fn)
-    times = {k: [] for k in work}
-    for _ in range(args.windows):
-        for k, (fn, n) in work.items():
-            times[k].append(timed(fn) / n)
-    med = {k: float(np.median(v)) for k, v in times.items()}
+    times = alternate(work, args.windows, host_per_call)
+    med = times.median
     us = lambda k: 1e6 * med[k]
     out = {
         "task": "RoboPianist-debug-TwinkleTwinkleRousseau-v0, hull fingertips, precision 64",
@@ -205,16 +182,12 @@ def main():
             "collect_ms_per_control_step": 1e3 * med[f"pop_collect_P{P}"],
             "collect_env_steps_per_s": E / med[f"pop_collect_P{P}"], "update_ms": 1e3 * med[f"pop_update_P{P}"]}
             for P in members},
-        "seconds_per_call_windows": times,
-        "spread": {k: [float(min(v) / med[k]), float(max(v) / med[k])] for k, v in times.items()},
+        "seconds_per_call_windows": times.windows,
+        "spread": {k: times.spread(k) for k in work},
         "method": "host clock around work that ends in a device synchronise; every workload warmed up once, then "
                   "alternating windows in one process; medians of the windows, which are stored",
     }
-    print(json.dumps({k: v for k, v in out.items() if k != "seconds_per_call_windows"}, indent=1))
-    os.makedirs(os.path.dirname(args.out), exist_ok=True)
-    with open(args.out, "w") as f:
-        json.dump(out, f, indent=1)
-        f.write("\n")
+    write_report(out, args.out, printed={k: v for k, v in out.items() if k != "seconds_per_call_windows"}, indent=1)
 
 
 if __name__ == "__main__":

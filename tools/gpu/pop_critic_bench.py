@@ -19,18 +19,12 @@ A difference counts only where the two sets of windows do not overlap.
                                          [--out profiles/pop_critic_bench.json]
 """
 import argparse
-import json
 import os
-import sys
-import time
-import warnings
 
-import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, ROOT)
-from robopianist_amd import critic, droq, pop_critic, population, suite  # noqa: E402
+from _measure import HANDS, ROOT, alternate, host_per_call, load_twinkle, write_report   # (puts ROOT on sys.path)
+from robopianist_amd import critic, droq, pop_critic, population
 
 
 def main():
@@ -45,18 +39,13 @@ def main():
     args = ap.parse_args()
     E, C, B, U = args.envs, args.capacity, args.batch, args.utd
     members = [int(p) for p in args.members.split(",")]
-    with warnings.catch_warnings():
-        warnings.simplefilter("ignore")
-        env = suite.load("RoboPianist-debug-TwinkleTwinkleRousseau-v0", seed=12345, n_envs=E, precision=64,
-                         task_kwargs=dict(trim_silence=True, control_timestep=0.05, gravity_compensation=True,
-                                          reduced_action_space=False, n_steps_lookahead=10))
+    env = load_twinkle(E, precision=64, **HANDS)
     utds = sorted({1, 4, U})
     modes = ("torch", "fused")
     singles = {u: droq.DroQ(env, capacity=C, batch_size=B, seed=1, utd=u, critic_step="fused") for u in utds}
     pops = {(P, m, u): population.DroQPopulation(env, P, capacity=C, batch_size=B // P, seed=1, utd=u, critic_step=m)
             for P in members for m in modes for u in utds}
     dev = env.physics.device
-    sync = torch.cuda.synchronize
     for l in list(singles.values()) + list(pops.values()):   # every ring is full from here on
         l.collect(C)
         l.update(1)                                          # ... and every minibatch buffer holds rows and y
@@ -99,13 +88,6 @@ def main():
                 l.update(1)
         return run
 
-    def timed(fn):
-        sync()
-        t0 = time.perf_counter()
-        fn()
-        sync()
-        return time.perf_counter() - t0
-
     work = {"single_step": (single_steps(critic.STEP), 200), "single_rows": (single_steps(critic.ROWS_ONLY), 200),
             "single_apply": (single_steps(critic.APPLY_ONLY), 200)}
     for P in members:
@@ -120,17 +102,8 @@ def main():
         for P in members:
             for m in modes:
                 work[f"update_{m}_utd{u}_P{P}"] = (updates(pops[P, m, u], n), n)
-    for fn, _ in work.values():   # warm-up of every shape
-        timed(fn)
-    times = {k: [] for k in work}
-    for _ in range(args.windows):
-        for k, (fn, n) in work.items():
-            times[k].append(timed(fn) / n)
-    med = {k: float(np.median(v)) for k, v in times.items()}
-    lo, hi = {k: float(min(v)) for k, v in times.items()}, {k: float(max(v)) for k, v in times.items()}
-    apart = lambda a, b: bool(hi[a] < lo[b])   # a's slowest window below b's fastest
-    verdict = lambda a, b: "faster" if apart(a, b) else "slower" if apart(b, a) else "windows overlap"
-    stat = lambda k, scale: {"median": scale * med[k], "lowest": scale * lo[k], "highest": scale * hi[k]}
+    times = alternate(work, args.windows, host_per_call)
+    stat, verdict = times.stat, times.verdict
     out = {
         "task": "RoboPianist-debug-TwinkleTwinkleRousseau-v0, hull fingertips, precision 64",
         "n_envs": E, "capacity": C, "batch_all_members": B, "obs_dim": D, "action_dim": A, "hidden": [H1, H2],
@@ -154,11 +127,7 @@ def main():
                   "alternating windows in one process; medians with the lowest and highest window; faster / slower only "
                   "where the two sets of windows do not overlap",
     }
-    print(json.dumps(out, indent=1))
-    os.makedirs(os.path.dirname(args.out), exist_ok=True)
-    with open(args.out, "w") as f:
-        json.dump(out, f, indent=1)
-        f.write("\n")
+    write_report(out, args.out, indent=1)
 
 
 if __name__ == "__main__":

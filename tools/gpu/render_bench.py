@@ -14,16 +14,11 @@ plus a 64-env 240 x 320 render on its own.  Writes profiles/render_bench.json (m
         (kernel table: profiles/render_kernel_stats.csv)
 """
 import argparse
-import json
 import os
-import sys
-import warnings
 
-import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, ROOT)
+from _measure import HANDS, ROOT, alternate, event_window, load_twinkle, staggered_replay, write_report
 
 
 def main():
@@ -34,29 +29,12 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "render_bench.json"))
     args = ap.parse_args()
 
-    from robopianist_amd import suite
-    from robopianist_amd.suite.scripted import ScriptedActions
-    from robopianist_amd.wrappers import CanonicalSpecWrapper
     E = args.envs
-    with warnings.catch_warnings():
-        warnings.simplefilter("ignore")
-        base = suite.load("RoboPianist-debug-TwinkleTwinkleRousseau-v0", seed=12345, n_envs=E,
-                          task_kwargs=dict(trim_silence=True, control_timestep=0.05, gravity_compensation=True,
-                                           reduced_action_space=False, n_steps_lookahead=10,
-                                           primitive_fingertip_collisions=False,   # hull fingertips, as bench.py's config 2
-                                           change_color_on_activation=True))
-    env = CanonicalSpecWrapper(base)
+    base = load_twinkle(E, **HANDS, primitive_fingertip_collisions=False,   # hull fingertips, as bench.py's config 2
+                        change_color_on_activation=True)
     phys, task = base.physics, base.task
     dev = phys.device
-    actions = np.load(os.path.join(ROOT, "tests", "golden", "twinkle_twinkle_actions.npy"))
-    T = actions.shape[0]
-    script = ScriptedActions(torch.as_tensor(actions, dtype=phys.dtype, device=dev),
-                             torch.zeros(E, dtype=torch.long, device=dev))
-    env.reset()
-    phase = torch.arange(E, device=dev) % T
-    for j in range(T):   # untimed prologue: spreads the envs over the episode
-        base.request_reset(phase == (T - 1 - j))
-        env.step(script)
+    env, script, _ = staggered_replay(base)
 
     def step_only():
         env.step(script)
@@ -68,43 +46,23 @@ def main():
     def render_only():
         phys.render(84, 84, "piano/back", key_rgb=task.key_rgb(phys), colorize_fingertips=task.colorize_fingertips)
 
-    def window(fn, seconds):
-        """ms per call over a window of at least `seconds` (device events around the whole window)."""
-        n, calls, total = 8, 0, 0.0
-        while total < seconds * 1e3:
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            for _ in range(n):
-                fn()
-            b.record()
-            b.synchronize()
-            total += a.elapsed_time(b); calls += n
-            n *= 2
-        return total / calls
-
-    for fn in (step_only, step_and_render, render_only):   # warm-up (allocations, the renderer's creation)
+    work = {"step": step_only, "step_render": step_and_render, "render": render_only}
+    for fn in work.values():   # warm-up (allocations, the renderer's creation)
         for _ in range(5):
             fn()
     torch.cuda.synchronize()
-    res = {"step": [], "step_render": [], "render": []}
-    for _ in range(args.windows):   # alternating
-        res["step"].append(window(step_only, args.seconds))
-        res["step_render"].append(window(step_and_render, args.seconds))
-        res["render"].append(window(render_only, args.seconds))
-    med = {k: float(np.median(v)) for k, v in res.items()}
+    measure = lambda fn: event_window(fn, args.seconds)
+    times = alternate(work, args.windows, measure, warm=False)
+    med, res = times.median, times.windows
 
     # 64 envs, 240 x 320 (dm_control's default image size)
-    with warnings.catch_warnings():
-        warnings.simplefilter("ignore")
-        small = suite.load("RoboPianist-debug-TwinkleTwinkleRousseau-v0", seed=1, n_envs=64,
-                           task_kwargs=dict(trim_silence=True, gravity_compensation=True,
-                                            primitive_fingertip_collisions=False))
+    small = load_twinkle(64, seed=1, primitive_fingertip_collisions=False)
     small.reset()
     big = lambda: small.physics.render(240, 320, "piano/back")
     for _ in range(5):
         big()
     torch.cuda.synchronize()
-    big_ms = float(np.median([window(big, args.seconds) for _ in range(args.windows)]))
+    big_ms = alternate({"big": big}, args.windows, measure, warm=False).median["big"]
 
     out = {
         "device": torch.cuda.get_device_name(dev),
@@ -122,10 +80,7 @@ def main():
         "render_240x320_pixels_per_s": 64 * 240 * 320 / (big_ms * 1e-3),
         "camera": "piano/back", "includes": "task.key_rgb (torch) + rp_render (two launches)",
     }
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        json.dump(out, f, indent=1)
-    print(json.dumps({k: v for k, v in out.items() if k != "windows_ms"}))
+    write_report(out, args.out, printed={k: v for k, v in out.items() if k != "windows_ms"})
 
 
 if __name__ == "__main__":

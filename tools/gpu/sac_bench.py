@@ -24,18 +24,12 @@ The env is shared by the two learners (each continues from its own last TimeStep
     python tools/gpu/sac_bench.py [--envs 4096] [--capacity 64] [--batch 4096] [--out profiles/sac_bench.json]
 """
 import argparse
-import json
 import os
-import sys
-import time
-import warnings
 
-import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, ROOT)
-from robopianist_amd import learning, offpolicy, suite  # noqa: E402
+from _measure import HANDS, ROOT, alternate, host_per_call, load_twinkle, write_report   # (puts ROOT on sys.path)
+from robopianist_amd import learning, offpolicy
 
 HBM_PEAK = {"spec": 8.0e12, "measured_float4_copy": 6.29e12}   # bytes/s, MI355X
 
@@ -52,15 +46,10 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "sac_bench.json"))
     args = ap.parse_args()
     E, C, B, T, G, R = args.envs, args.capacity, args.batch, args.horizon, args.grad_steps, args.rollouts
-    with warnings.catch_warnings():
-        warnings.simplefilter("ignore")
-        env = suite.load("RoboPianist-debug-TwinkleTwinkleRousseau-v0", seed=12345, n_envs=E, precision=64,
-                         task_kwargs=dict(trim_silence=True, control_timestep=0.05, gravity_compensation=True,
-                                          reduced_action_space=False, n_steps_lookahead=10))
+    env = load_twinkle(E, precision=64, **HANDS)
     sac = offpolicy.SAC(env, capacity=C, batch_size=B, seed=1)
     ppo = learning.PPO(env, horizon=T, seed=1)
     dev, D, A = env.physics.device, sac.D, sac.A
-    sync = torch.cuda.synchronize
     sac.collect(C)   # the ring is full from here on
     recorded = sac.ring()["action"][:T].to(env.physics.dtype).clone()
 
@@ -140,23 +129,11 @@ def main():
         for _ in range(R):
             sac.update(G)
 
-    def timed(fn, *a):
-        sync()
-        t0 = time.perf_counter()
-        fn(*a)
-        sync()
-        return time.perf_counter() - t0
-
     work = {"sac_collect": (sac_collects, R * T), "replay": (replay_steps, R * T), "ppo_collect": (ppo_collects, R * T),
             "sample": (samples, 4000), "torch_sample": (torch_samples, 400), "act_target": (act_targets, 1000),
             "torch_target": (torch_targets, 1000), "grad_step": (grad_steps, 40), "update": (updates, R)}
-    for fn, _ in work.values():   # warm-up of every shape
-        timed(fn)
-    times = {k: [] for k in work}
-    for _ in range(args.windows):
-        for k, (fn, n) in work.items():
-            times[k].append(timed(fn) / n)
-    med = {k: float(np.median(v)) for k, v in times.items()}
+    times = alternate(work, args.windows, host_per_call)
+    med = times.median
     rate = lambda k: E / med[k]
     sample_bytes = 2 * 4 * B * (2 * D + A + 2) + 4 * B * (2 * offpolicy.SAMPLE_TRIES + 1)   # rows read and written; step types, mask
     round_s = med["sac_collect"] * T + med["update"]
@@ -164,7 +141,7 @@ def main():
         "task": "RoboPianist-debug-TwinkleTwinkleRousseau-v0, hull fingertips, precision 64",
         "n_envs": E, "capacity": C, "batch": B, "obs_dim": D, "action_dim": A, "hidden": [sac.H1, sac.H2],
         "n_critics": sac.n_critics, "steps_per_round": T, "grad_steps_per_round": G, "windows": args.windows,
-        "seconds_per_window": {k: float(np.median(v)) * n for (k, v), (_, n) in zip(times.items(), work.values())},
+        "seconds_per_window": {k: med[k] * n for k, (_, n) in work.items()},
         "env_steps_per_s": {"sac_collect": rate("sac_collect"), "replay_of_recorded_actions": rate("replay"),
                             "ppo_collect": rate("ppo_collect")},
         "ms_per_control_step": {k: 1e3 * med[k] for k in ("sac_collect", "replay", "ppo_collect")},
@@ -174,15 +151,11 @@ def main():
         "act_target_us": 1e6 * med["act_target"], "torch_target_us": 1e6 * med["torch_target"],
         "grad_step_ms": 1e3 * med["grad_step"], "update_ms": 1e3 * med["update"],
         "round_ms": 1e3 * round_s, "update_share_of_round": med["update"] / round_s,
-        "spread": {k: [float(min(v) / med[k]), float(max(v) / med[k])] for k, v in times.items()},
+        "spread": {k: times.spread(k) for k in work},
         "method": "host clock around work that ends in a device synchronise; every workload warmed up once, then "
                   "alternating windows in one process; medians",
     }
-    print(json.dumps(out, indent=1))
-    os.makedirs(os.path.dirname(args.out), exist_ok=True)
-    with open(args.out, "w") as f:
-        json.dump(out, f, indent=1)
-        f.write("\n")
+    write_report(out, args.out, indent=1)
 
 
 if __name__ == "__main__":

@@ -13,36 +13,21 @@ of voices that can sound in a window) over that time.
     python tools/gpu/time_hearing.py [--envs 4096] [--windows 3] [--out profiles/hearing_timing.json]
 """
 import argparse
-import json
+import itertools
 import os
-import sys
-import warnings
 
-import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, ROOT)
+from _measure import ROOT, Times, event_time, load_twinkle, scripted_replay, write_report
 
 
 def record_replay_steps():
     """(rows [n_steps][n_sub][4] int32, sustain [n_steps] int32, dt) of env 0 over the scripted replay."""
-    from robopianist_amd import suite
-    from robopianist_amd.suite.scripted import ScriptedActions
-    from robopianist_amd.wrappers import CanonicalSpecWrapper
-    with warnings.catch_warnings():
-        warnings.simplefilter("ignore")
-        base = suite.load("RoboPianist-debug-TwinkleTwinkleRousseau-v0", seed=12345, n_envs=2, record_key_trace=True,
-                          task_kwargs=dict(trim_silence=True, control_timestep=0.05, gravity_compensation=True,
-                                           primitive_fingertip_collisions=True))
-    env = CanonicalSpecWrapper(base)
-    dev = base.physics.device
-    actions = np.load(os.path.join(ROOT, "tests", "golden", "twinkle_twinkle_actions.npy"))
-    script = ScriptedActions(torch.as_tensor(actions, dtype=base.physics.dtype, device=dev),
-                             torch.zeros(2, dtype=torch.long, device=dev))
+    base = load_twinkle(2, record_key_trace=True, control_timestep=0.05, primitive_fingertip_collisions=True)
+    env, script, n_steps = scripted_replay(base)
     env.reset()
     rows, sustain = [], []
-    for _ in range(len(actions)):
+    for _ in range(n_steps):
         ts = env.step(script)
         rows.append(base.key_trace[0].clone())
         sustain.append(base.task.piano.sustain_activation[0, 0].to(torch.int32))
@@ -95,25 +80,21 @@ def main():
             if h.spectrum_raw(spec_args) != 0:
                 raise RuntimeError(h.last_error())
 
-    def timed(which, calls):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for t in range(calls):
-            run(which, t)
-        b.record()
-        b.synchronize()
-        return a.elapsed_time(b) / calls
+    def measure(which, calls):
+        """ms per call of `calls` calls of the workload, at steps 0, 1, ... of the recording."""
+        t = itertools.count()
+        return event_time(lambda: run(which, next(t)), calls)
 
     names = ("observe", "track", "spectrum")
     calls = {}
     for w in names:   # size every window to --seconds from a short probe
-        ms = timed(w, 20)
+        ms = measure(w, 20)
         calls[w] = max(20, int(args.seconds * 1000.0 / ms))
     ms = {w: [] for w in names}
     for _ in range(args.windows):
         for w in names:
-            ms[w].append(timed(w, calls[w]))
-    med = {w: float(np.median(v)) for w, v in ms.items()}
+            ms[w].append(measure(w, calls[w]))
+    med = Times(ms).median
 
     W, B, H = h.window, h.n_bins, int(h.timbre["H"])
     analysis_flop = 2.0 * E * W * 2 * B
@@ -136,11 +117,7 @@ def main():
         "window_gflop_per_call_phasor_steps_only": window_flop / 1e9,
         "spectrum_tflops_counted": (analysis_flop + window_flop) / (med["spectrum"] * 1e-3) / 1e12,
     }
-    os.makedirs(os.path.dirname(args.out), exist_ok=True)
-    with open(args.out, "w") as fh:
-        json.dump(result, fh, indent=1)
-        fh.write("\n")
-    print(json.dumps(result))
+    write_report(result, args.out)
 
 
 if __name__ == "__main__":

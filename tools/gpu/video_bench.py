@@ -15,31 +15,13 @@ Writes profiles/video_bench.json: ms per call, frames/s, input and output MB/s, 
 import argparse
 import json
 import os
-import sys
-import warnings
 
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, ROOT)
+from _measure import ROOT, alternate, event_window, load_twinkle, scripted_replay
 
 WORKLOADS = ((4096, 84, 84), (64, 240, 320), (4, 480, 640))
-
-
-def window(fn, seconds):
-    """ms per call over a window of at least `seconds` (device events around the whole window)."""
-    n, calls, total = 4, 0, 0.0
-    while total < seconds * 1e3:
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(n):
-            fn()
-        b.record()
-        b.synchronize()
-        total += a.elapsed_time(b); calls += n
-        n *= 2
-    return total / calls
 
 
 def main():
@@ -50,22 +32,11 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "video_bench.json"))
     args = ap.parse_args()
 
-    from robopianist_amd import suite
-    from robopianist_amd.suite.scripted import ScriptedActions
-    from robopianist_amd.wrappers import CanonicalSpecWrapper
-    actions = np.load(os.path.join(ROOT, "tests", "golden", "twinkle_twinkle_actions.npy"))
     results = []
     for E, H, W in WORKLOADS:
-        with warnings.catch_warnings():
-            warnings.simplefilter("ignore")
-            base = suite.load("RoboPianist-debug-TwinkleTwinkleRousseau-v0", seed=12345, n_envs=E,
-                              task_kwargs=dict(trim_silence=True, control_timestep=0.05, gravity_compensation=True,
-                                               primitive_fingertip_collisions=True, change_color_on_activation=True))
-        env = CanonicalSpecWrapper(base)
+        base = load_twinkle(E, control_timestep=0.05, primitive_fingertip_collisions=True, change_color_on_activation=True)
         phys, task = base.physics, base.task
-        dev = phys.device
-        script = ScriptedActions(torch.as_tensor(actions, dtype=phys.dtype, device=dev),
-                                 torch.zeros(E, dtype=torch.long, device=dev))
+        env, script, _ = scripted_replay(base)
         env.reset()
         for _ in range(40):   # untimed: the hands are over the keys, some keys are down and coloured
             env.step(script)
@@ -83,14 +54,12 @@ def main():
             for _ in range(3):
                 fn()
         torch.cuda.synchronize()
-        r_ms, e_ms = [], []
-        for _ in range(args.windows):
-            r_ms.append(window(render, args.seconds))
-            e_ms.append(window(encode, args.seconds))
+        times = alternate({"render": render, "encode": encode}, args.windows,
+                          lambda fn: event_window(fn, args.seconds, first=4), warm=False)
         _, length = enc.encode(rgb)
         n = length.cpu().numpy().astype(np.int64)
         assert (n > 0).all()
-        r, e = float(np.median(r_ms)), float(np.median(e_ms))
+        r, e = times.median["render"], times.median["encode"]
         results.append({
             "frames": E, "height": H, "width": W, "quality": args.quality,
             "render_ms": r, "encode_ms": e, "encode_over_render": e / r,
@@ -99,7 +68,7 @@ def main():
             "encode_output_MB_per_s": float(n.sum()) / (e * 1e-3) / 1e6,
             "bytes_per_frame_mean": float(n.mean()), "bytes_per_frame_max": int(n.max()), "bytes_cap": enc.max_bytes,
             "compression": E * H * W * 3 / float(n.sum()),
-            "windows_ms": {"render": r_ms, "encode": e_ms},
+            "windows_ms": times.windows,
         })
         del env, base, enc, rgb
         torch.cuda.empty_cache()
@@ -111,8 +80,9 @@ def main():
         "workloads": results,
     }
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
+    with open(args.out, "w") as f:   # (its own writer: one printed line per workload, not the report)
         json.dump(out, f, indent=1)
+        f.write("\n")
     for w in results:
         print(json.dumps({k: v for k, v in w.items() if k != "windows_ms"}))
 
